@@ -13,6 +13,17 @@ over the time to finish all K.  `single_frame` reports one frame at a time
 Fast mode: one render kernel per frame; cuda mode (the CUDA port's semantics) likewise.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode parity|fast] [--inflight 1|2]
+                  [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the
+line (`value`, `ms_per_step`, the configuration, and what the timed launches themselves left
+behind: their phase times, the rooflines derived from those, their carry hand-off words).
+--dump-outputs DIR then writes the image the last timed step rendered (what a caller of the
+timed path receives) as DIR/image.npy, float32; an image above OUTPUT_BUDGET bytes as a fixed,
+seeded sample of its pixels (sample_output), the same pixels on every run.  Everything below
+that takes launches, copies or processes of its own — the byte and md5 checks of every timed
+frame, `single_frame` (whose phases the rooflines then use), `end_to_end`, `rates`,
+`resolver_diag`, `cpu_baseline`, `sharded_single_image` — runs only with --full.
 
 Multi-GPU (torchrun, one rank per GPU, RANK/LOCAL_RANK/WORLD_SIZE from the env): every rank
 joins an rc_group (the library's own RCCL communicator; rank 0's ncclUniqueId shared over
@@ -31,9 +42,9 @@ three rates side by side: frames in flight on the device (`value`), one frame at
 device (`single_frame`), and the drop-in raycast() call end to end — scene upload, kernels and
 the copy into the caller's fresh pageable pixmap (`end_to_end`, SURVEY.md §8d's rate).
 
-Rank 0 prints one JSON line with `roofline` (the dominant kernel, timed live with HIP events
-on its stream through rc_profile_begin/end), per-phase times and `cpu_baseline` (the reference
-C/ build from oracle/_ref on one host core; N=1 only).
+Rank 0 prints one JSON line; with --full it carries `roofline` (the dominant kernel, timed
+live with HIP events on its stream through rc_profile_begin/end), per-phase times and
+`cpu_baseline` (the reference C/ build from oracle/_ref on one host core; N=1 only).
 """
 import argparse
 import importlib.util
@@ -65,6 +76,9 @@ PEAK_FP64_TFLOPS = 78.6    # MI355X vector FP64 (MI355X_MICROARCH.md: FP32 157.3
 PEAK_HBM_GBS = 8000.0      # MI355X HBM3E
 GOLDEN_MD5 = os.path.join(ROOT, "tests", "golden", "md5.json")   # the reference's own outputs
 LEG_TIMEOUT_EXIT = 3       # exit status when the sharded leg's watchdog fires
+OUTPUT_BUDGET = 48 << 20   # --dump-outputs: bytes of float32 written at most
+OUTPUT_SEED = 20240607     # the sampled pixels of a larger image: fixed, the same on every run
+PLAIN_RING = 64            # output images a plain run rotates through (--full: one per step)
 
 
 def load_pkg():
@@ -161,6 +175,27 @@ def golden_md5(scene, W, H, depth, mode):
     except OSError:
         return None
     return e["md5"] if e else None
+
+
+def sample_output(img, budget=OUTPUT_BUDGET, seed=OUTPUT_SEED):
+    """What --dump-outputs writes for an [H, W, 3] uint8 image: the whole image as float32 when
+    that fits in `budget` bytes, else [n, 3] float32, the pixels at n = budget // 12 distinct
+    raster positions drawn once from a generator seeded with `seed` and sorted — a function
+    of (H, W, budget, seed) only, so two builds dump the same pixels."""
+    import numpy as np
+    h, w, c = img.shape
+    n = budget // (4 * c)
+    if h * w <= n:
+        return img.astype(np.float32)
+    idx = np.sort(np.random.default_rng(seed).choice(h * w, size=n, replace=False))
+    return img.reshape(h * w, c)[idx].astype(np.float32)
+
+
+def dump_outputs(directory, img):
+    """DIR/image.npy (sample_output of the last timed step's image)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "image.npy"), sample_output(img))
 
 
 def verify_frames(pkg, bufs, want_md5):
@@ -439,11 +474,18 @@ def main():
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--depth", type=int, default=6)
     ap.add_argument("--scene", default="quadric")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: byte and md5 checks of every "
+                         "timed frame, single-frame and end-to-end rates, rooflines, resolver "
+                         "diagnostics, the CPU baseline, the sharded leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's image to DIR/image.npy "
+                         "(float32; above 48 MiB a fixed seeded sample of its pixels)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--timed-only", action="store_true",
-                    help="launch nothing but the warmup and timed steps (no single-frame, "
-                         "end-to-end or CPU legs): the command profiled under rocprofv3, so its "
-                         "per-kernel averages are those of the timed launches")
+                    help="with --full: launch nothing but the warmup and timed steps (no "
+                         "single-frame, end-to-end or CPU legs), keep the frame checks and the "
+                         "rooflines; a plain run launches nothing else anyway")
     ap.add_argument("--inflight", type=int, default=2, choices=[1, 2],
                     help="parity frames in flight: 2 = rc_frame_submit (the next frame's pixel "
                          "phases beside this frame's resolver), 1 = one rc_render_device per step")
@@ -457,6 +499,8 @@ def main():
                     help="N>1 parity: time the row-sharded single image (rc_render_sharded) as "
                          "the step instead of N replicas")
     args = ap.parse_args()
+    full = args.full
+    legs = full and not args.timed_only   # the legs that launch renders of their own
 
     try:
         world, spawn = resolve_world(args.gpus, os.environ)
@@ -533,12 +577,14 @@ def main():
     want_md5 = golden_md5(args.scene, W, H, args.depth, mode) if mode != "cuda" else None
 
     piped = parity and args.inflight == 2 and not sharded
-    # every frame of the timed region gets its own output image, so that all of them can be
-    # byte-checked afterwards (the sharded step's image is the root's)
+    # --full: every frame of the timed region gets its own output image, so that all of them
+    # can be byte-checked afterwards (the sharded step's image is the root's); a plain run
+    # rotates through at most PLAIN_RING of them, so its set-up does not grow with --steps
     outs = None
     if not sharded:
         outs = [torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
-                for _ in range(max(args.steps, 1))]
+                for _ in range(max(args.steps, 1) if full else
+                               min(max(args.steps, 1), PLAIN_RING))]
         torch.cuda.synchronize()
     frame_no = [0]
 
@@ -562,7 +608,7 @@ def main():
     pipe_tim = {}
     single = None
     side0 = None
-    if piped and not args.timed_only:
+    if piped and legs:
         # latency and per-phase times of a lone frame (rc_render_device, the raycast() path),
         # taken before the frame pipeline's CU-partitioned streams exist
         for _ in range(2):
@@ -631,17 +677,22 @@ def main():
     # hand-offs: every parity frame's latched carry hand-off words (rc_frames_wait /
     # rc_lone_frames_check); bytes: every frame's image against frame 0's on the device, and
     # frame 0's P3 md5 against the reference's golden
+    # A plain run reads the hand-off words only (rc_frames_wait has latched them by now);
+    # the byte and md5 checks are --full's.
     diag = None   # the timed frames' own resolver record (rc_resolver_stats_get)
     if piped:
         hand = {"checked": int(pipe_tim.get("frames_checked", 0)),
                 "failed": int(pipe_tim.get("frames_failed", 0))}
-        diag = pkg.resolver_stats(lone=False)
+        diag = pkg.resolver_stats(lone=False) if full else None
     elif parity and not sharded:
         hand = pkg.lone_frames_check()
-        diag = pkg.resolver_stats(lone=True)
+        diag = pkg.resolver_stats(lone=True) if full else None
     else:
         hand = None   # no carry hand-off in this mode (sharded: checked inside each call)
-    if sharded:
+    if not full:
+        nframes = 1 if sharded else min(args.steps, len(outs))
+        equal, md5, gold = nframes, None, None
+    elif sharded:
         equal, md5, gold = (1, *verify_frames(pkg, [out], want_md5)[1:]) if rank == 0 else \
             (1, None, None)
         nframes = 1
@@ -654,13 +705,19 @@ def main():
     okt = torch.tensor([ok, nframes], dtype=torch.int64, device=cdev)
     if multi and not sharded:
         dist.all_reduce(okt)
-    verified = {"frames": f"{int(okt[0])}/{int(okt[1])}",
-                "bytes_equal_frame0": f"{equal}/{nframes}",
-                "frame0_md5": md5,
-                "frame0_vs_reference": ("equal" if gold else "MISMATCH" if gold is False
-                                        else "no golden for this configuration"),
-                "hand_offs": (f"{hand['checked'] - hand['failed']}/{args.steps}" if hand
-                              else "n/a")}
+    frames_ok = int(okt[0]) == int(okt[1])
+    hand_offs = f"{hand['checked'] - hand['failed']}/{args.steps}" if hand else "n/a"
+    if full:
+        verified = {"frames": f"{int(okt[0])}/{int(okt[1])}",
+                    "bytes_equal_frame0": f"{equal}/{nframes}",
+                    "frame0_md5": md5,
+                    "frame0_vs_reference": ("equal" if gold else "MISMATCH" if gold is False
+                                            else "no golden for this configuration"),
+                    "hand_offs": hand_offs}
+    else:
+        verified = {"hand_offs": hand_offs,
+                    "note": "carry hand-off words only; --full checks every frame's bytes and "
+                            "frame 0's md5 against the reference's"}
 
     tim = {}
     shard_stats = group.stats() if sharded else None
@@ -674,10 +731,13 @@ def main():
                   "image_ms": shard_stats["image_ms"], "total_ms": shard_stats["device_ms"],
                   "render_ms": shard_stats["local_ms"] if not parity else 0.0,
                   "phase_a_ms": shard_stats["local_ms"] if parity else 0.0}
-    elif not args.timed_only:
+    elif legs:
         pkg.render_device(scene, W, H, out.data_ptr(), stream.cuda_stream, depth=args.depth,
                           mode=mode, timing=tim)
     torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:   # the image the last timed step rendered
+        last = out if sharded else outs[(args.steps - 1) % len(outs)]
+        dump_outputs(args.dump_outputs, last.cpu().numpy())
     line = None
     if rank == 0:
         images = 1 if sharded else world
@@ -801,7 +861,7 @@ def main():
         if sharded:
             line["shard_stats"] = {k: (round(v, 4) if isinstance(v, float) else v)
                                    for k, v in shard_stats.items()}
-        if world == 1 and not args.timed_only:
+        if world == 1 and legs:
             line["end_to_end"] = end_to_end(pkg, scene, W, H, args.depth, mode)
             rates = {"value_is": ("frames_in_flight_device" if piped else "one_frame_device"),
                      "dropin_rate_is": "raycast_end_to_end (SURVEY.md §8d: upload + kernels + D2H)"}
@@ -815,7 +875,7 @@ def main():
             rates["raycast_end_to_end"] = {"value": line["end_to_end"]["value"],
                                            "ms": line["end_to_end"]["ms"]}
             line["rates"] = rates
-        if world == 1 and not args.no_cpu_baseline and not args.timed_only and mode != "cuda":
+        if world == 1 and not args.no_cpu_baseline and legs and mode != "cuda":
             line["cpu_baseline"] = cpu_baseline(scene_path, args.size, args.depth)
     # N>1 parity replicas: the sharded single image as well, reported beside (never as) value.
     # It is the only multi-process RCCL exchange of the run, so a watchdog bounds it: if it has
@@ -871,8 +931,7 @@ def main():
             print(json.dumps(line), flush=True)
 
     shard_leg_res = None
-    if (multi and backend == "nccl" and not sharded and not args.timed_only
-            and group_err is None):
+    if multi and backend == "nccl" and not sharded and legs and group_err is None:
         shard_leg_res = run_leg_with_watchdog(shard_leg, LEG_TIMEOUT_S, leg_timed_out)
     if rank == 0:
         if shard_leg_res and "group_error" in shard_leg_res:
@@ -889,7 +948,7 @@ def main():
         group.close()
     if multi:
         dist.destroy_process_group()
-    if verified["frames"].split("/")[0] != verified["frames"].split("/")[1]:
+    if not frames_ok:
         sys.exit(4)   # a timed frame failed its checks: the line is printed, the run fails
 
 

@@ -4,6 +4,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 from helpers import ROOT
 
 sys.path.insert(0, ROOT)
@@ -59,6 +61,81 @@ def test_golden_lookup():
     assert bench.golden_md5("quadric", 4096, 4096, 6, "parity") == "3bf1c59fc7cf7e508e5b1796348e9726"
     assert bench.golden_md5("quadric", 4096, 4096, 6, "fast") == "7b6a08a014498b1c3b81df44fce9b776"
     assert bench.golden_md5("quadric", 123, 4096, 6, "parity") is None
+
+
+# ---- bench.py --dump-outputs: what is written, and that it is the same on every run ----
+
+def test_sample_output_whole_image_when_it_fits():
+    import numpy as np
+    img = np.arange(5 * 7 * 3, dtype=np.uint8).reshape(5, 7, 3)
+    s = bench.sample_output(img)
+    assert s.dtype == np.float32 and s.shape == img.shape
+    np.testing.assert_array_equal(s, img)
+
+
+def test_sample_output_fixed_sample_of_a_larger_image():
+    """Above the budget: budget // 12 distinct pixels in raster order, the same ones on every
+    call, taken from the image itself; never more bytes than the budget."""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    img = rng.integers(0, 256, size=(37, 53, 3), dtype=np.uint8)
+    budget = 1200   # 100 pixels of 37 * 53
+    a = bench.sample_output(img, budget=budget)
+    assert a.dtype == np.float32 and a.shape == (100, 3) and a.nbytes <= budget
+    np.testing.assert_array_equal(a, bench.sample_output(img.copy(), budget=budget))
+    # the positions: recovered from an image whose pixels carry their own raster index
+    tag = np.arange(37 * 53, dtype=np.uint32)
+    idx_img = np.stack([tag & 255, tag >> 8, np.zeros_like(tag)], axis=1).astype(np.uint8)
+    pos = bench.sample_output(idx_img.reshape(37, 53, 3), budget=budget)
+    pos = (pos[:, 0] + 256 * pos[:, 1]).astype(np.int64)
+    assert len(set(pos.tolist())) == 100 and (np.diff(pos) > 0).all()
+    np.testing.assert_array_equal(a, img.reshape(-1, 3)[pos])
+    # the headline image: 4096^2 x 3 float32 is above the budget, the sample is within 64 MB
+    n = bench.OUTPUT_BUDGET // 12
+    assert 4096 * 4096 > n and n * 12 <= 64 * 10**6
+
+
+def test_dump_outputs_writes_image_npy(tmp_path):
+    import numpy as np
+    img = np.full((4, 6, 3), 7, dtype=np.uint8)
+    d = tmp_path / "dump" / "nested"
+    bench.dump_outputs(str(d), img)
+    got = np.load(d / "image.npy")
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got, img)
+
+
+def test_full_and_dump_options_parse():
+    """--full and --dump-outputs DIR are options of the command line."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run prints the headline line without --full's legs, times exactly --steps
+    steps, and --dump-outputs writes the image of its last timed step: byte-identical to the
+    CPU oracle's render of the same configuration (a small image is dumped whole)."""
+    import json
+    import numpy as np
+    from helpers import oracle_render, rc, scene_path
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps",
+                        "3", "--warmup", "1", "--size", "200", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "rays/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32+f64"
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 / (200 * 200) - 1) < 1e-3
+    assert d["verified"]["hand_offs"] == "3/3"
+    for leg in ("single_frame", "end_to_end", "rates", "cpu_baseline", "resolver_diag"):
+        assert leg not in d, leg
+    got = np.load(tmp_path / "image.npy")
+    ref, _ = oracle_render(rc.Scene.from_file(scene_path("quadric")), 200, 200, 6, "parity")
+    assert got.dtype == np.float32 and got.shape == (200, 200, 3)
+    np.testing.assert_array_equal(got, ref)
 
 
 # ---- bench.py --gpus N without a launcher (VERDICT r5 item 1) ----
