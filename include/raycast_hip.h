@@ -122,6 +122,8 @@ _Static_assert(sizeof(light_t) == 72, "light_t must match C/objects.h layout");
  *   RAYCAST_DEPTH  = bounce depth d, MAX_RECURSION = d+1 (default 6 == C/raycast.c:14)
  *   RAYCAST_GPUS   = number of GPUs for row-cyclic sharding over RCCL (default 1; both modes)
  *   RAYCAST_DEVICE = first HIP device ordinal (default 0)
+ *   RAYCAST_SSAA   = supersampling factor 1 (default) | 2 | 4 | 8 (rc_options.ssaa; any other
+ *                    value: a warning, then 1)
  *   RAYCAST_STATS  = 1: one JSON metrics line on stderr
  * Any HIP failure prints a message to stderr and exit(1)s (reference error convention). */
 void raycast(json_data_t *json_struct, PPMFormat photo_data);
@@ -139,7 +141,26 @@ typedef struct rc_options {
   int mode;            /* RC_MODE_* */
   int num_gpus;        /* >= 1 */
   int device;          /* first device ordinal */
+  int ssaa;            /* supersampling factor s: 1 (off; 0 means the same, so zero-initialised
+                          options keep one ray per pixel), 2, 4 or 8; anything else is refused */
 } rc_options;
+_Static_assert(sizeof(rc_options) == 20, "rc_options layout (ctypes binding)");
+
+/* Supersampled anti-aliasing (ssaa = s > 1).  Let B be the s*W x s*H image the same scene,
+ * mode and depth produce with ssaa = 1: the camera of that size (pw = cam_w / (float)(s*W),
+ * ph = cam_h / (float)(s*H), C/raycast.c:109-110), quantised uint8 samples.  The W x H output
+ * is B's box filter in integers, rounded to nearest:
+ *     out[y][x][c] = (sum over j < s, i < s of B[s*y + j][s*x + i][c]  +  s*s/2) / (s*s)
+ * so an anti-aliased image is an exact function of the reference's own s*W x s*H image.
+ * In parity mode B is the reference's parity image of that size (scan-order carry and
+ * phantom included); in fast / cuda mode it is that mode's image.  rc_timing.zero_normalize
+ * and dep_pixels are those of B.  Fast mode shoots the s*s subsamples of a pixel on adjacent
+ * lanes and reduces them in registers (B is never stored); parity and cuda modes render B
+ * into a buffer of the device context and box-filter it on the device.
+ * rc_render, rc_render_device and raycast() honour ssaa in every mode (rc_render_device's
+ * row0 / row_step / nrows stay in output rows; parity and cuda need row_step == 1 with s > 1);
+ * rc_frame_submit honours it in fast and cuda mode and refuses parity frames with s > 1;
+ * num_gpus > 1 and rc_render_sharded refuse s > 1. */
 
 typedef struct rc_timing {
   double total_ms;       /* whole call, host wall clock                                 */
@@ -154,7 +175,8 @@ typedef struct rc_timing {
   int64_t frames_failed; /* of them, frames whose carry hand-off failed (image invalid)  */
 } rc_timing;
 
-/* Fill *opt with the defaults (then the RAYCAST_* environment overrides if use_env). */
+/* Fill *opt with the defaults (ssaa = 1), then the RAYCAST_* environment overrides if use_env
+ * (a RAYCAST_SSAA other than 1, 2, 4 or 8 prints a warning and leaves 1). */
 void rc_default_options(rc_options *opt, int use_env);
 
 /* Opaque packed scene: flattened shape/light arrays + the out-of-bounds "phantom" record
@@ -354,6 +376,10 @@ typedef struct rc_tuning {
                              per-wave queue, whose front holds the runs that can be dense    */
   int pipe_last_whole;    /* rc_frames_wait runs the window's last frame's phase C on every CU
                              instead of the pixel partition (1, default; 0 = the partition)   */
+  int ssaa_fused;         /* fast mode with rc_options.ssaa > 1: 1 the fused kernel (default:
+                             subsamples on adjacent lanes, reduced in registers); 0 the two-pass
+                             path of the other modes (the s*W x s*H image, then the box filter)
+                             — the same bytes, kept for the measurement (scripts/ssaa_ab.py)   */
 } rc_tuning;
 void rc_default_tuning(rc_tuning *t);
 int rc_set_tuning(const rc_tuning *t);

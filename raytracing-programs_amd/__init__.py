@@ -65,7 +65,7 @@ class PPMFormat(ctypes.Structure):
 
 class RcOptions(ctypes.Structure):
     _fields_ = [("max_recursion", ctypes.c_int), ("mode", ctypes.c_int),
-                ("num_gpus", ctypes.c_int), ("device", ctypes.c_int)]
+                ("num_gpus", ctypes.c_int), ("device", ctypes.c_int), ("ssaa", ctypes.c_int)]
 
 
 class RcTiming(ctypes.Structure):
@@ -118,7 +118,7 @@ TUNING_FIELDS = ["side", "split_shade", "resolve_shared", "resolve_lds_kb", "res
                  "staged_d2h", "prefault", "copy_threads", "side_blocks", "comp_stream",
                  "block_min", "pipe_inres", "x0", "resolve_clean",
                  "shard_lone", "team_cscan", "pipe_order", "pipe_helpers", "patch_host",
-                 "share_device", "headb_first", "pipe_last_whole"]
+                 "share_device", "headb_first", "pipe_last_whole", "ssaa_fused"]
 
 
 class RcTuning(ctypes.Structure):
@@ -377,24 +377,48 @@ class tuned:
         return False
 
 
-def options(depth=6, mode="parity", gpus=1, device=0):
+def options(depth=6, mode="parity", gpus=1, device=0, ssaa=1):
     opt = RcOptions()
     opt.max_recursion = depth + 1
     opt.mode = MODES[mode] if isinstance(mode, str) else int(mode)
     opt.num_gpus = gpus
     opt.device = device
+    opt.ssaa = ssaa
     return opt
 
 
-def render(scene, width, height, depth=6, mode="parity", gpus=1, device=0, timing=None, out=None):
+def default_options(use_env=False):
+    """rc_default_options as a dict (with use_env: the RAYCAST_* environment applied)."""
+    opt = RcOptions()
+    hip_lib().rc_default_options(ctypes.byref(opt), 1 if use_env else 0)
+    return {k: getattr(opt, k) for k, _ in RcOptions._fields_}
+
+
+def box_downsample(img, s):
+    """The supersampling contract (include/raycast_hip.h, rc_options.ssaa) in numpy: the
+    [H, W, 3] uint8 box filter of an [s*H, s*W, 3] uint8 image, per channel
+    (sum of the s x s block + s*s/2) // (s*s)."""
+    img = np.asarray(img)
+    s = int(s)
+    if s < 1 or img.dtype != np.uint8 or img.ndim != 3 or img.shape[0] % s or img.shape[1] % s:
+        raise ValueError(f"box_downsample: a uint8 [s*H, s*W, C] image and s >= 1, got "
+                         f"{img.dtype} {img.shape} and s = {s}")
+    h, w, c = img.shape[0] // s, img.shape[1] // s, img.shape[2]
+    total = img.reshape(h, s, w, s, c).sum(axis=(1, 3), dtype=np.uint32)
+    return ((total + (s * s) // 2) // (s * s)).astype(np.uint8)
+
+
+def render(scene, width, height, depth=6, mode="parity", gpus=1, device=0, timing=None, out=None,
+           ssaa=1):
     """Render to a host array [H, W, 3] uint8 through rc_render (the raycast() path); `out`
-    (optional) is the caller's C-contiguous pixmap, like the reference's malloc'd one."""
+    (optional) is the caller's C-contiguous pixmap, like the reference's malloc'd one.  ssaa =
+    2, 4 or 8: the box filter of the ssaa*W x ssaa*H image (box_downsample), made on the device."""
     lib = hip_lib()
     if out is None:
         out = np.empty((height, width, 3), dtype=np.uint8)
     assert out.shape == (height, width, 3) and out.dtype == np.uint8 and out.flags.c_contiguous
     t = RcTiming()
-    opt = options(depth, mode, gpus, device)
+    opt = options(depth, mode, gpus, device, ssaa)
     rc = lib.rc_render(scene.packed(), width, height, ctypes.byref(opt),
                        out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
     if rc != 0:
@@ -405,11 +429,12 @@ def render(scene, width, height, depth=6, mode="parity", gpus=1, device=0, timin
 
 
 def render_device(scene, width, height, d_out_ptr, stream_ptr=None, depth=6, mode="parity",
-                  row0=0, row_step=1, nrows=None, timing=None):
-    """Render rows row0, row0+row_step, ... into device memory at d_out_ptr (nrows*W*3 B)."""
+                  row0=0, row_step=1, nrows=None, timing=None, ssaa=1):
+    """Render rows row0, row0+row_step, ... into device memory at d_out_ptr (nrows*W*3 B); with
+    ssaa > 1 the rows are those of the box-filtered W x H image."""
     lib = hip_lib()
     nrows = height if nrows is None else nrows
-    opt = options(depth, mode)
+    opt = options(depth, mode, ssaa=ssaa)
     t = RcTiming()
     rc = lib.rc_render_device(scene.packed(), width, height, row0, row_step, nrows,
                               ctypes.byref(opt), ctypes.c_void_p(d_out_ptr),
@@ -421,10 +446,11 @@ def render_device(scene, width, height, d_out_ptr, stream_ptr=None, depth=6, mod
         timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
 
 
-def frame_submit(scene, width, height, d_out_ptr, depth=6, mode="parity"):
+def frame_submit(scene, width, height, d_out_ptr, depth=6, mode="parity", ssaa=1):
     """Enqueue one whole image into device memory at d_out_ptr (W*H*3 B) with frames in
-    flight (rc_frame_submit); returns at once.  Pair with frames_wait()."""
-    opt = options(depth, mode)
+    flight (rc_frame_submit); returns at once.  Pair with frames_wait().  ssaa > 1: fast and
+    cuda mode only (parity frames in flight do not supersample)."""
+    opt = options(depth, mode, ssaa=ssaa)
     if hip_lib().rc_frame_submit(scene.packed(), width, height, ctypes.byref(opt),
                                  ctypes.c_void_p(d_out_ptr)) != 0:
         raise RuntimeError("rc_frame_submit failed (see stderr)")

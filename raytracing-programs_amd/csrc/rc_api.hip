@@ -30,7 +30,7 @@
 #include "rc_runtime.h"
 #include "rc_scene.h"
 
-#define RC_VERSION "raycast-mi355x 0.1 (gfx950)"
+#define RC_VERSION "raycast-mi355x 0.2 (gfx950)"
 
 namespace rcrt {
 
@@ -87,6 +87,7 @@ rc_tuning default_tuning() {
   // resolver (lone quadric 4096^2 4.66 -> 4.55-4.56 ms; profiles/r05e_lone_headb.txt)
   t.headb_first = 24;
   t.pipe_last_whole = 1;
+  t.ssaa_fused = 1;
   return t;
 }
 rc_tuning g_tune = default_tuning();
@@ -682,6 +683,7 @@ int rc_set_tuning(const rc_tuning* t) {
       in(t->resolve_clean, 1, 64) && in(t->shard_lone, 0, 1) && in(t->team_cscan, 0, 1) &&
       in(t->pipe_order, 0, 4) && in(t->pipe_helpers, 0, rc::kDenseSlots) &&
       in(t->patch_host, 0, 2) && in(t->share_device, 0, 1) && in(t->headb_first, 0, 1 << 16) && in(t->pipe_last_whole, 0, 1) &&
+      in(t->ssaa_fused, 0, 1) &&
       !(t->split_shade && !t->side);
   if (!ok) {
     std::fprintf(stderr, "Error: rc_set_tuning: a field is out of range\n");
@@ -715,6 +717,7 @@ void rc_default_options(rc_options* opt, int use_env) {
   opt->mode = RC_MODE_PARITY;
   opt->num_gpus = 1;
   opt->device = 0;
+  opt->ssaa = 1;
   if (!use_env) return;
   if (const char* m = std::getenv("RAYCAST_MODE")) {
     if (!std::strcmp(m, "fast")) opt->mode = RC_MODE_FAST;
@@ -727,6 +730,12 @@ void rc_default_options(rc_options* opt, int use_env) {
   if (const char* g = std::getenv("RAYCAST_GPUS")) opt->num_gpus = std::atoi(g);
   if (const char* v = std::getenv("RAYCAST_DEVICE")) opt->device = std::atoi(v);
   if (opt->num_gpus < 1) opt->num_gpus = 1;
+  if (const char* a = std::getenv("RAYCAST_SSAA")) {
+    if (!std::strcmp(a, "1") || !std::strcmp(a, "2") || !std::strcmp(a, "4") || !std::strcmp(a, "8"))
+      opt->ssaa = a[0] - '0';
+    else
+      std::fprintf(stderr, "Warning: RAYCAST_SSAA '%s' is not 1, 2, 4 or 8, using 1\n", a);
+  }
 }
 
 rc_scene* rc_scene_create(const json_data_t* js) {
@@ -1021,9 +1030,55 @@ int enqueue_render(DevCtx& c, const rc_scene* s, int W, int H, int row0, int row
   return rc;
 }
 
+int ssaa_factor(const rc_options* opt, const char* who) {
+  const int a = opt->ssaa;
+  if (a == 0 || a == 1) return 1;
+  if (a == 2 || a == 4 || a == 8) return a;
+  std::fprintf(stderr, "Error: %s: ssaa %d is not 0, 1, 2, 4 or 8\n", who, a);
+  return -1;
+}
+
+// Supersampling, two passes (parity and cuda modes; fast mode with rc_tuning.ssaa_fused = 0):
+// the s*W x s*H image of the same mode through the one-frame path below, unchanged, into the
+// context's buffer, then its box filter into d_out.  The frame's events, counts and hand-off
+// log are those of the large image; its last event is moved behind the box filter.
+int enqueue_render_two_pass(DevCtx& c, const rc_scene* s, int W, int H, int ss, int row0,
+                            int row_step, int nrows, const rc_options* opt, uint8_t* d_out,
+                            hipStream_t stream, bool timed, hipEvent_t** evset) {
+  if (row_step != 1) {
+    std::fprintf(stderr, "Error: ssaa %d in this mode renders contiguous rows only (row_step "
+                 "%d)\n", ss, row_step);
+    return -1;
+  }
+  if (W > (1 << 28) / ss || H > (1 << 28) / ss) return -1;
+  const int sw = W * ss, sh = H * ss;
+  if (c.ssaa.ensure((size_t)sw * 3 * (size_t)nrows * ss)) {
+    std::fprintf(stderr, "Error: out of device memory for the supersampled image (%dx%d)\n", sw,
+                 nrows * ss);
+    return -1;
+  }
+  rc_options one = *opt;
+  one.ssaa = 1;
+  hipEvent_t* ev = nullptr;
+  if (enqueue_render_ws(c, s, sw, sh, row0 * ss, 1, nrows * ss, &one, (uint8_t*)c.ssaa.p, stream,
+                        timed, nullptr, &ev))
+    return -1;
+  if (evset) *evset = ev;
+  HIP_TRY(rc::launch_box_down((const uint8_t*)c.ssaa.p, W, nrows, ss, d_out, stream));
+  const bool parity = opt->mode == RC_MODE_PARITY && opt->max_recursion > 1;
+  if (timed) HIP_TRY(hipEventRecord(ev[parity ? 4 : 1], stream));
+  return 0;
+}
+
 int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int row_step,
                       int nrows, const rc_options* opt, uint8_t* d_out, hipStream_t stream,
                       bool timed, uint32_t* patch, hipEvent_t** evset) {
+  const int ss = ssaa_factor(opt, "render");
+  if (ss < 0) return -1;
+  const bool fused = ss > 1 && opt->mode == RC_MODE_FAST && tune().ssaa_fused;
+  if (ss > 1 && !fused)
+    return enqueue_render_two_pass(c, s, W, H, ss, row0, row_step, nrows, opt, d_out, stream,
+                                   timed, evset);
   rc::LaunchScene ls;
   if (upload_scene(c.fb, stream, s, ls)) return -1;
   unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
@@ -1039,8 +1094,12 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
   if (evset) *evset = ev;
   if (timed) HIP_TRY(hipEventRecord(ev[0], stream));
   if (!parity) {
-    HIP_TRY(rc::launch_render(ls, W, H, row0, row_step, nrows, maxrec, d_out, zc, stream,
-                              opt->mode == RC_MODE_CUDA));
+    if (fused)   // the subsamples on adjacent lanes, box-filtered in registers
+      HIP_TRY(rc::launch_render_ssaa(ls, W, H, ss, row0, row_step, nrows, maxrec, d_out, zc,
+                                     stream));
+    else
+      HIP_TRY(rc::launch_render(ls, W, H, row0, row_step, nrows, maxrec, d_out, zc, stream,
+                                opt->mode == RC_MODE_CUDA));
     if (timed) HIP_TRY(hipEventRecord(ev[1], stream));
     return 0;
   }
@@ -1324,6 +1383,7 @@ int rc_render_device(const rc_scene* s, int W, int H, int row0, int row_step, in
                      const rc_options* opt, uint8_t* d_out, void* stream, rc_timing* timing) {
   if (!s || !opt || !d_out || W <= 0 || H <= 0 || nrows < 0 || row_step < 1) return -1;
   if (row0 < 0 || (nrows > 0 && row0 + (long long)(nrows - 1) * row_step >= H)) return -1;
+  if (ssaa_factor(opt, "rc_render_device") < 0) return -1;
   if (nrows == 0) return 0;
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
@@ -1546,6 +1606,13 @@ extern "C" {
 
 int rc_frame_submit(const rc_scene* s, int W, int H, const rc_options* opt, uint8_t* d_out) {
   if (!s || !opt || !d_out || W <= 0 || H <= 0) return -1;
+  const int ss = ssaa_factor(opt, "rc_frame_submit");
+  if (ss < 0) return -1;
+  if (ss > 1 && opt->mode == RC_MODE_PARITY) {   // the frame pipeline stays as it is
+    std::fprintf(stderr, "Error: rc_frame_submit: parity frames in flight do not supersample "
+                 "(ssaa %d); use rc_render_device\n", ss);
+    return -1;
+  }
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   DevCtx* c;
@@ -1868,6 +1935,13 @@ int rc_render(const rc_scene* s, int W, int H, const rc_options* opt, uint8_t* p
   if (timing) std::memset(timing, 0, sizeof *timing);
   // one snapshot of the tuning for the whole call (rc_set_tuning may run concurrently)
   const rc_tuning tu = tune();
+  const int ss = ssaa_factor(opt, "rc_render");
+  if (ss < 0) return -1;
+  if (ss > 1 && opt->num_gpus > 1) {
+    std::fprintf(stderr, "Error: rc_render: ssaa %d with num_gpus %d: the row shards do not "
+                 "supersample\n", ss, opt->num_gpus);
+    return -1;
+  }
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   int G = opt->num_gpus;
@@ -1934,7 +2008,9 @@ int rc_render(const rc_scene* s, int W, int H, const rc_options* opt, uint8_t* p
   uint8_t* d_out = (uint8_t*)c->out.p;
   // parity: the copy overlaps the resolver (copy_overlapped); split shading leaves the non-DEP
   // colours to phase C, so its framebuffer is not final after phase A
-  const bool overlap = parity && !tu.split_shade && tu.overlap_d2h;
+  // supersampled (ss > 1): the overlapped copy and the colour patch would act on the large
+  // image's pixels, so the frame stays device-resident, is box-filtered, then copied
+  const bool overlap = parity && !tu.split_shade && tu.overlap_d2h && ss == 1;
   uint32_t* patch = nullptr;
   const bool hpatch = overlap && tu.patch_host;
   size_t prev_dirty = 0;

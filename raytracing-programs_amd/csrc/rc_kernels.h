@@ -91,6 +91,16 @@ hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_s
                          int maxrec, uint8_t* out, unsigned long long* zcount,
                          hipStream_t stream, bool cuda_sem = false);
 
+// Supersampled fast mode (rc_options.ssaa = 2, 4 or 8), fused: rows row0 + k*row_step of the
+// W x H box-filtered image into `out`; the ssaa*W x ssaa*H subsample image is never stored.
+// zcount counts the zero-normalize events of every subsample.
+hipError_t launch_render_ssaa(const LaunchScene& s, int W, int H, int ssaa, int row0, int row_step,
+                              int nrows, int maxrec, uint8_t* out, unsigned long long* zcount,
+                              hipStream_t stream);
+// The two-pass path's box filter: dst (W x H) <- src (ssaa*W x ssaa*H), both compact RGB.
+hipError_t launch_box_down(const uint8_t* src, int W, int H, int ssaa, uint8_t* dst,
+                           hipStream_t stream);
+
 hipError_t launch_parity(const LaunchScene& s, int W, int H, int maxrec, uint8_t* out,
                          const ParityWork& w, unsigned long long* zcount, hipStream_t stream,
                          const hipEvent_t* ev);

@@ -19,6 +19,9 @@
 //   k_finish      after the resolver: whatever k_side has not claimed.
 //   k_render_cuda RC_MODE_CUDA: k_render's layout with the CUDA port's arithmetic
 //                 (rc_cudasem.hpp).
+//   k_render_ssaa fast mode with s x s supersampling: one lane per subsample, the box filter
+//                 across the lanes of a wave, one store per output pixel.
+//   k_box_down    the box filter of an s*W x s*H image in memory (parity and cuda modes).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -264,6 +267,92 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
   tile_write_rows<kTileW * 3 / 4>(tb.rgb, [&](int q) -> uint8_t* {
     return r0 + q < nrows ? out + ((size_t)(r0 + q) * W + x0) * 3 : nullptr;
   }, nx * 3);
+}
+
+// ------------------------------------------------- fast mode, supersampled (ssaa) --
+// k_render over the subsample grid of an s x s supersampled image (s = 1 << ls; 2, 4 or 8):
+// one lane shoots one subsample with the camera of the s*W x s*H image, the same tiles as
+// k_render in subsample coordinates.  lane = 8 * row + col inside a wave tile and s divides 8,
+// so the s x s subsamples of an output pixel are lanes of one wave: their quantised channels
+// are summed with xor butterflies over the column bits (1 .. s/2) and the row bits (8 .. 4s),
+// and the group's first lane stores the rounded mean, (sum + s*s/2) / (s*s).  The subsample
+// image is never written.  W, nrows, row0 and row_step are in output pixels: output row r
+// covers subsample rows s * (row0 + r * row_step) + j, j < s.
+// Tile origins are multiples of 8 subsamples, so a group is wholly inside the image or wholly
+// outside it: outside lanes skip shoot, add zeros in the butterflies (which every lane of the
+// wave executes) and store nothing.
+template <bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_render_ssaa(
+    Scene sc, Cam cam, int W, int ls, int row0, int row_step, int nrows, int maxrec,
+    uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount) {
+  if (!RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // no cross-term-free form here (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  stage_scene<kStage>(sc, stage);
+  int lx, ly;
+  tile_pixel(lx, ly);
+  int bx, by;
+  xcd_tile<0>(bx, by);
+  const int s = 1 << ls;
+  const int xs = bx * kTileW + lx;   // subsample column
+  const int rs = by * kTileH + ly;   // subsample row of the local (shard) rows
+  // only xs and rs stay live across shoot (k_render's x and r): the output pixel, the bounds
+  // test and the group's first lane all follow from them
+  const bool inside = (xs >> ls) < W && (rs >> ls) < nrows;
+  unsigned rg = 0u, b = 0u;          // R | G << 16 and B: a channel's sum is <= 64 * 255
+  if (inside) {
+    const int y = ((row0 + (rs >> ls) * row_step) << ls) + (rs & (s - 1));
+    int zero = 0;
+    const V3 d = primary_dir(cam, xs, y, zero);
+    PixelOut po;
+    shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
+    rg = (unsigned)quant(po.rgb.x) | ((unsigned)quant(po.rgb.y) << 16);
+    b = quant(po.rgb.z);
+    flush_events(zero, zcount);
+  }
+  for (int m = 1; m < s; m <<= 1) {       // columns of the group
+    rg += __shfl_xor(rg, m, 64);
+    b += __shfl_xor(b, m, 64);
+  }
+  for (int m = 8; m < 8 * s; m <<= 1) {   // rows of the group
+    rg += __shfl_xor(rg, m, 64);
+    b += __shfl_xor(b, m, 64);
+  }
+  // the group's first lane (tile origins are multiples of 8, so of s)
+  if (inside && ((xs | rs) & (s - 1)) == 0) {
+    const unsigned half = 1u << (2 * ls - 1);
+    const int x = xs >> ls, r = rs >> ls;   // r: local (shard) output row
+    uint8_t* p = out + ((size_t)r * W + x) * 3;
+    p[0] = (uint8_t)(((rg & 0xffffu) + half) >> (2 * ls));
+    p[1] = (uint8_t)(((rg >> 16) + half) >> (2 * ls));
+    p[2] = (uint8_t)((b + half) >> (2 * ls));
+  }
+}
+
+// Box filter of the two-pass path (parity and cuda modes, whose s*W x s*H image exists in
+// memory): dst pixel (x, y) = the rounded mean of src's s x s block at (s*x, s*y), per channel,
+// (sum + s*s/2) / (s*s).  One thread per output pixel; src is (s*W) x (s*H), dst W x H.
+__global__ void __launch_bounds__(256) k_box_down(const uint8_t* __restrict__ src, int W, int H,
+                                                  int ls, uint8_t* __restrict__ dst) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)W * H) return;
+  const int s = 1 << ls;
+  const size_t y = i / (size_t)W, x = i % (size_t)W;
+  const size_t srow = (size_t)W * s * 3;
+  const uint8_t* p = src + y * s * srow + x * s * 3;
+  unsigned r = 0u, g = 0u, b = 0u;
+  for (int j = 0; j < s; ++j) {
+    const uint8_t* q = p + (size_t)j * srow;
+    for (int k = 0; k < s; ++k) {
+      r += q[3 * k];
+      g += q[3 * k + 1];
+      b += q[3 * k + 2];
+    }
+  }
+  const unsigned half = 1u << (2 * ls - 1);
+  uint8_t* d = dst + i * 3;
+  d[0] = (uint8_t)((r + half) >> (2 * ls));
+  d[1] = (uint8_t)((g + half) >> (2 * ls));
+  d[2] = (uint8_t)((b + half) >> (2 * ls));
 }
 
 // ------------------------------------------------------- CUDA-port semantics (f4) --
@@ -3024,6 +3113,32 @@ hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_s
   }
   hipLaunchKernelGGL(stage_fits(s) ? k_render<true> : k_render<false>, grid, dim3(kBlock), 0, stream, make_scene(s), make_cam(s, W, H),
                      W, H, row0, row_step, nrows, maxrec, out, zcount);
+  return hipGetLastError();
+}
+
+static int ssaa_log2(int ssaa) { return ssaa == 2 ? 1 : ssaa == 4 ? 2 : ssaa == 8 ? 3 : -1; }
+
+hipError_t launch_render_ssaa(const LaunchScene& s, int W, int H, int ssaa, int row0, int row_step,
+                              int nrows, int maxrec, uint8_t* out, unsigned long long* zcount,
+                              hipStream_t stream) {
+  const int ls = ssaa_log2(ssaa);
+  if (ls < 0 || W > 0x7fffffff / ssaa || H > 0x7fffffff / ssaa || nrows > 0x7fffffff / ssaa)
+    return hipErrorInvalidValue;
+  const int sw = W * ssaa, sr = nrows * ssaa;
+  dim3 grid((sw + kTileW - 1) / kTileW, (sr + kTileH - 1) / kTileH);
+  if (grid.y > 65535u) return hipErrorInvalidValue;   // grid.y of k_render's tile layout
+  hipLaunchKernelGGL(stage_fits(s) ? k_render_ssaa<true> : k_render_ssaa<false>, grid,
+                     dim3(kBlock), 0, stream, make_scene(s), make_cam(s, sw, H * ssaa), W, ls, row0,
+                     row_step, nrows, maxrec, out, zcount);
+  return hipGetLastError();
+}
+
+hipError_t launch_box_down(const uint8_t* src, int W, int H, int ssaa, uint8_t* dst,
+                           hipStream_t stream) {
+  const int ls = ssaa_log2(ssaa);
+  const size_t blocks = ((size_t)W * H + 255) / 256;
+  if (ls < 0 || W <= 0 || H <= 0 || blocks > 0x7fffffffu) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_box_down, dim3((unsigned)blocks), dim3(256), 0, stream, src, W, H, ls, dst);
   return hipGetLastError();
 }
 

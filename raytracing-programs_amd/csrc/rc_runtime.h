@@ -176,6 +176,7 @@ struct DevCtx {
   hipEvent_t ev[kEvSets][5] = {};
   int prof_active = 0, prof_calls = 0, prof_parity = 0;
   DevBuf out;          // rc_render output pixmap
+  DevBuf ssaa;         // two-pass supersampling: the s*W x s*H image before the box filter
   uint8_t* stage[2] = {nullptr, nullptr};   // pinned bounce buffers of copy_to_host
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   FrameBufs fb;        // scene, counter and parity workspace of the plain path
@@ -241,6 +242,9 @@ double event_ms(hipEvent_t a, hipEvent_t b);
 int enqueue_render(DevCtx& c, const rc_scene* s, int W, int H, int row0, int row_step, int nrows,
                    const rc_options* opt, uint8_t* d_out, hipStream_t stream, bool timed,
                    uint32_t* patch = nullptr, hipEvent_t** evset = nullptr);
+// rc_options.ssaa as a factor: 1 (0 and 1 are both off), 2, 4 or 8; -1 and a message naming
+// `who` for any other value
+int ssaa_factor(const rc_options* opt, const char* who);
 int check_spin_error(FrameBufs& b, const rc_options* opt);
 void fill_device_timing(DevCtx& c, const rc_options* opt, rc_timing* t,
                         const uint8_t* tail = nullptr);

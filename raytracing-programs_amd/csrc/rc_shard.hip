@@ -741,6 +741,13 @@ int rc_render_sharded(rc_group* g, const rc_scene* s, int W, int H, const rc_opt
                       uint8_t* d_image, rc_timing* timing) {
   if (!g || !s || !opt || W <= 0 || H <= 0) return -1;
   if ((long long)W * H >= (1ll << 31)) return -1;   // DEP indices and wire pixels are 32-bit
+  const int ss = ssaa_factor(opt, "rc_render_sharded");
+  if (ss != 1) {
+    if (ss > 1)
+      std::fprintf(stderr, "Error: rc_render_sharded: ssaa %d: the row shards do not "
+                   "supersample\n", ss);
+    return -1;
+  }
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   int rc;
