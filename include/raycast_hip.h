@@ -124,6 +124,9 @@ _Static_assert(sizeof(light_t) == 72, "light_t must match C/objects.h layout");
  *   RAYCAST_DEVICE = first HIP device ordinal (default 0)
  *   RAYCAST_SSAA   = supersampling factor 1 (default) | 2 | 4 | 8 (rc_options.ssaa; any other
  *                    value: a warning, then 1)
+ *   RAYCAST_SSAA_ADAPTIVE = contrast threshold t, 1..255: supersample only the edge pixels
+ *                    (RC_SSAA_ADAPTIVE below; fast mode, RAYCAST_SSAA 2, 4 or 8).  Any other
+ *                    value: a warning, then off; set while the factor is 1: a warning, ignored
  *   RAYCAST_STATS  = 1: one JSON metrics line on stderr
  * Any HIP failure prints a message to stderr and exit(1)s (reference error convention). */
 void raycast(json_data_t *json_struct, PPMFormat photo_data);
@@ -142,9 +145,18 @@ typedef struct rc_options {
   int num_gpus;        /* >= 1 */
   int device;          /* first device ordinal */
   int ssaa;            /* supersampling factor s: 1 (off; 0 means the same, so zero-initialised
-                          options keep one ray per pixel), 2, 4 or 8; anything else is refused */
+                          options keep one ray per pixel), 2, 4 or 8, alone or with an adaptive
+                          threshold t in bits 8..15 (RC_SSAA_ADAPTIVE(s, t), below); anything
+                          else is refused */
 } rc_options;
 _Static_assert(sizeof(rc_options) == 20, "rc_options layout (ctypes binding)");
+
+/* rc_options.ssaa = s | (t << 8): the factor s and the adaptive contrast threshold t (0: every
+ * pixel is supersampled, the plain ssaa below).  A value decodes when s is 0, 1, 2, 4 or 8, t is
+ * 0..255 and no higher bit is set; t > 0 needs s >= 2.  Everything else is refused. */
+#define RC_SSAA_ADAPTIVE(s, t) ((int)(s) | ((int)(t) << 8))
+#define RC_SSAA_FACTOR(v)      ((int)(v) & 0xff)
+#define RC_SSAA_THRESHOLD(v)   (((int)(v) >> 8) & 0xff)
 
 /* Supersampled anti-aliasing (ssaa = s > 1).  Let B be the s*W x s*H image the same scene,
  * mode and depth produce with ssaa = 1: the camera of that size (pw = cam_w / (float)(s*W),
@@ -162,6 +174,39 @@ _Static_assert(sizeof(rc_options) == 20, "rc_options layout (ctypes binding)");
  * rc_frame_submit honours it in fast and cuda mode and refuses parity frames with s > 1;
  * num_gpus > 1 and rc_render_sharded refuse s > 1. */
 
+/* Adaptive supersampling (ssaa = RC_SSAA_ADAPTIVE(s, t), s in {2, 4, 8}, t in 1..255; fast and
+ * cuda mode).  Fix the scene, mode, depth, W and H, and let
+ *   A  be the W x H image of that mode with ssaa = 1,
+ *   F  be the W x H image of that mode with ssaa = s (the box filter above, t = 0),
+ *   contrast(x, y) = the maximum over the three channels of max - min of A's bytes over the 3 x 3
+ *                    window centred on (x, y), clipped to the image (a 1 x 1 image: 0).
+ * Then  out[y][x] = F[y][x] if contrast(x, y) >= t, else A[y][x].
+ * The contrast is computed on A's quantised bytes, in integers, so the output is an exact
+ * function of two images the reference's arithmetic defines and does not depend on any
+ * execution order.  On the device: A is rendered into the output, one kernel lists the pixels
+ * with contrast >= t (in no particular order), and a third shoots the s*s subsamples of the
+ * listed pixels only, on adjacent lanes, and stores their box filter over A's pixel.  The three
+ * are separate launches on one stream: the list is complete before any pixel its neighbours'
+ * contrast was read from is overwritten.  rc_timing.zero_normalize counts the rays actually
+ * shot (A's and the refined subsamples').
+ * rc_render, rc_render_device, raycast() and rc_frame_submit honour it in fast and cuda mode.
+ * Refused, each with a message: parity mode (every pixel of its s*W x s*H image depends on the
+ * scan-order carry of the whole image, so it cannot be shot sparsely; plain ssaa remains);
+ * rc_render_device with anything but the whole image (row0 = 0, row_step = 1, nrows = H: the
+ * contrast needs the neighbouring rows); t > 0 with s < 2; num_gpus > 1 and rc_render_sharded
+ * (by the factor, like plain ssaa); W * H >= 2^32. */
+typedef struct rc_adaptive_stats {
+  int64_t refined_pixels;   /* pixels with contrast >= t          */
+  int64_t rays;             /* W*H + s*s*refined_pixels           */
+} rc_adaptive_stats;
+/* The last adaptive frame enqueued on the current device: waits for that frame, then reads its
+ * count.  Returns -1 if there was none. */
+int rc_adaptive_stats_get(rc_adaptive_stats *out);
+/* The kernel spans (ms, HIP events) of the last adaptive frame rendered with timing (rc_render,
+ * rc_render_device with a timing record) on the current device: ms[0] the one-ray image, ms[1]
+ * the edge list, ms[2] the refinement.  Returns -1 if there was none. */
+int rc_adaptive_phase_ms(double ms[3]);
+
 typedef struct rc_timing {
   double total_ms;       /* whole call, host wall clock                                 */
   double kernel_ms;      /* sum of kernel spans (HIP events)                            */
@@ -176,7 +221,9 @@ typedef struct rc_timing {
 } rc_timing;
 
 /* Fill *opt with the defaults (ssaa = 1), then the RAYCAST_* environment overrides if use_env
- * (a RAYCAST_SSAA other than 1, 2, 4 or 8 prints a warning and leaves 1). */
+ * (a RAYCAST_SSAA other than 1, 2, 4 or 8 prints a warning and leaves 1; RAYCAST_SSAA_ADAPTIVE =
+ * 1..255 with a factor of 2, 4 or 8 gives RC_SSAA_ADAPTIVE(factor, t), any other value prints a
+ * warning and means off, and with a factor of 1 it prints a warning and is ignored). */
 void rc_default_options(rc_options *opt, int use_env);
 
 /* Opaque packed scene: flattened shape/light arrays + the out-of-bounds "phantom" record
@@ -380,6 +427,10 @@ typedef struct rc_tuning {
                              subsamples on adjacent lanes, reduced in registers); 0 the two-pass
                              path of the other modes (the s*W x s*H image, then the box filter)
                              — the same bytes, kept for the measurement (scripts/ssaa_ab.py)   */
+  int adaptive_blocks;    /* adaptive supersampling: workgroups of the refinement kernel, which
+                             stride over the edge list.  0 (default): sized from the CU count;
+                             1..4096: exactly that many (1 walks the whole list with one
+                             workgroup: tests, scripts/adaptive_ab.py)                         */
 } rc_tuning;
 void rc_default_tuning(rc_tuning *t);
 int rc_set_tuning(const rc_tuning *t);

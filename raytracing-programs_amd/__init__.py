@@ -75,6 +75,10 @@ class RcTiming(ctypes.Structure):
                 ("frames_checked", ctypes.c_int64), ("frames_failed", ctypes.c_int64)]
 
 
+class RcAdaptiveStats(ctypes.Structure):
+    _fields_ = [("refined_pixels", ctypes.c_int64), ("rays", ctypes.c_int64)]
+
+
 class RcPhaseStats(ctypes.Structure):
     _fields_ = [("calls", ctypes.c_int), ("parity", ctypes.c_int), ("phase_a_ms", ctypes.c_double),
                 ("compact_ms", ctypes.c_double), ("resolve_ms", ctypes.c_double),
@@ -118,7 +122,8 @@ TUNING_FIELDS = ["side", "split_shade", "resolve_shared", "resolve_lds_kb", "res
                  "staged_d2h", "prefault", "copy_threads", "side_blocks", "comp_stream",
                  "block_min", "pipe_inres", "x0", "resolve_clean",
                  "shard_lone", "team_cscan", "pipe_order", "pipe_helpers", "patch_host",
-                 "share_device", "headb_first", "pipe_last_whole", "ssaa_fused"]
+                 "share_device", "headb_first", "pipe_last_whole", "ssaa_fused",
+                 "adaptive_blocks"]
 
 
 class RcTuning(ctypes.Structure):
@@ -136,7 +141,8 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_group_transport", "rc_render_sharded", "rc_group_last_stats",
                "rc_default_tuning", "rc_set_tuning", "rc_get_tuning", "rc_lone_frames_check",
                "rc_debug_inject_error", "rc_group_debug_bound", "rc_resolver_stats_get",
-               "rc_group_rank_stats", "rc_debug_scatter_selftest"]
+               "rc_group_rank_stats", "rc_debug_scatter_selftest", "rc_adaptive_stats_get",
+               "rc_adaptive_phase_ms"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -250,6 +256,8 @@ def _hip_lib_locked():
     lib.rc_debug_inject_error.argtypes = [ctypes.c_int]
     lib.rc_resolver_stats_get.argtypes = [ctypes.c_int, ctypes.POINTER(RcResolverStats)]
     lib.rc_group_rank_stats.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RcRankStats)]
+    lib.rc_adaptive_stats_get.argtypes = [ctypes.POINTER(RcAdaptiveStats)]
+    lib.rc_adaptive_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
     _hip = lib
     return lib
 
@@ -377,21 +385,40 @@ class tuned:
         return False
 
 
-def options(depth=6, mode="parity", gpus=1, device=0, ssaa=1):
+def ssaa_adaptive(s, t):
+    """RC_SSAA_ADAPTIVE(s, t): rc_options.ssaa with the factor s and the contrast threshold t."""
+    return int(s) | (int(t) << 8)
+
+
+def ssaa_factor(v):
+    """RC_SSAA_FACTOR(v)."""
+    return int(v) & 0xff
+
+
+def ssaa_threshold(v):
+    """RC_SSAA_THRESHOLD(v)."""
+    return (int(v) >> 8) & 0xff
+
+
+def options(depth=6, mode="parity", gpus=1, device=0, ssaa=1, adaptive=0):
+    """rc_options; adaptive = t > 0 encodes RC_SSAA_ADAPTIVE(ssaa, t) (the library validates)."""
     opt = RcOptions()
     opt.max_recursion = depth + 1
     opt.mode = MODES[mode] if isinstance(mode, str) else int(mode)
     opt.num_gpus = gpus
     opt.device = device
-    opt.ssaa = ssaa
+    opt.ssaa = ssaa_adaptive(ssaa, adaptive) if adaptive else ssaa
     return opt
 
 
 def default_options(use_env=False):
-    """rc_default_options as a dict (with use_env: the RAYCAST_* environment applied)."""
+    """rc_default_options as a dict (with use_env: the RAYCAST_* environment applied); "ssaa" is
+    the factor and "adaptive" the threshold (0: off) of the encoded field."""
     opt = RcOptions()
     hip_lib().rc_default_options(ctypes.byref(opt), 1 if use_env else 0)
-    return {k: getattr(opt, k) for k, _ in RcOptions._fields_}
+    d = {k: getattr(opt, k) for k, _ in RcOptions._fields_}
+    d["ssaa"], d["adaptive"] = ssaa_factor(opt.ssaa), ssaa_threshold(opt.ssaa)
+    return d
 
 
 def box_downsample(img, s):
@@ -408,17 +435,51 @@ def box_downsample(img, s):
     return ((total + (s * s) // 2) // (s * s)).astype(np.uint8)
 
 
+def _window_range(a):
+    """max - min over the 3 x 3 window, clipped to the image, per channel: [H, W, C] int."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 3:
+        raise ValueError(f"a uint8 [H, W, C] image, got {a.dtype} {a.shape}")
+    h, w = a.shape[:2]
+    lo = np.pad(a, ((1, 1), (1, 1), (0, 0)), constant_values=255)
+    hi = np.pad(a, ((1, 1), (1, 1), (0, 0)), constant_values=0)
+    mn, mx = a.copy(), a.copy()
+    for dy in range(3):
+        for dx in range(3):
+            mn = np.minimum(mn, lo[dy:dy + h, dx:dx + w])
+            mx = np.maximum(mx, hi[dy:dy + h, dx:dx + w])
+    return mx.astype(np.int32) - mn.astype(np.int32)
+
+
+def edge_mask(a, t):
+    """The adaptive contract's edge test (include/raycast_hip.h, RC_SSAA_ADAPTIVE) in numpy:
+    [H, W] bool, true where the largest per-channel max - min of the uint8 image `a` over the
+    3 x 3 window centred on the pixel, clipped to the image, is >= t."""
+    return _window_range(a).max(axis=2) >= int(t)
+
+
+def adaptive_compose(a, f, t):
+    """The adaptive contract: `f` (the ssaa = s image) where edge_mask(a, t), `a` (the one-ray
+    image) elsewhere."""
+    a, f = np.asarray(a), np.asarray(f)
+    if a.shape != f.shape or f.dtype != np.uint8:
+        raise ValueError(f"two uint8 images of one shape, got {a.shape} and {f.dtype} {f.shape}")
+    return np.where(edge_mask(a, t)[:, :, None], f, a)
+
+
 def render(scene, width, height, depth=6, mode="parity", gpus=1, device=0, timing=None, out=None,
-           ssaa=1):
+           ssaa=1, adaptive=0):
     """Render to a host array [H, W, 3] uint8 through rc_render (the raycast() path); `out`
     (optional) is the caller's C-contiguous pixmap, like the reference's malloc'd one.  ssaa =
-    2, 4 or 8: the box filter of the ssaa*W x ssaa*H image (box_downsample), made on the device."""
+    2, 4 or 8: the box filter of the ssaa*W x ssaa*H image (box_downsample), made on the device.
+    adaptive = t in 1..255 (fast and cuda mode, with ssaa): only the pixels of the one-ray image
+    whose 3 x 3 contrast reaches t are supersampled (adaptive_compose)."""
     lib = hip_lib()
     if out is None:
         out = np.empty((height, width, 3), dtype=np.uint8)
     assert out.shape == (height, width, 3) and out.dtype == np.uint8 and out.flags.c_contiguous
     t = RcTiming()
-    opt = options(depth, mode, gpus, device, ssaa)
+    opt = options(depth, mode, gpus, device, ssaa, adaptive)
     rc = lib.rc_render(scene.packed(), width, height, ctypes.byref(opt),
                        out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
     if rc != 0:
@@ -429,12 +490,13 @@ def render(scene, width, height, depth=6, mode="parity", gpus=1, device=0, timin
 
 
 def render_device(scene, width, height, d_out_ptr, stream_ptr=None, depth=6, mode="parity",
-                  row0=0, row_step=1, nrows=None, timing=None, ssaa=1):
+                  row0=0, row_step=1, nrows=None, timing=None, ssaa=1, adaptive=0):
     """Render rows row0, row0+row_step, ... into device memory at d_out_ptr (nrows*W*3 B); with
-    ssaa > 1 the rows are those of the box-filtered W x H image."""
+    ssaa > 1 the rows are those of the box-filtered W x H image.  adaptive > 0: whole images
+    only."""
     lib = hip_lib()
     nrows = height if nrows is None else nrows
-    opt = options(depth, mode, ssaa=ssaa)
+    opt = options(depth, mode, ssaa=ssaa, adaptive=adaptive)
     t = RcTiming()
     rc = lib.rc_render_device(scene.packed(), width, height, row0, row_step, nrows,
                               ctypes.byref(opt), ctypes.c_void_p(d_out_ptr),
@@ -446,11 +508,11 @@ def render_device(scene, width, height, d_out_ptr, stream_ptr=None, depth=6, mod
         timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
 
 
-def frame_submit(scene, width, height, d_out_ptr, depth=6, mode="parity", ssaa=1):
+def frame_submit(scene, width, height, d_out_ptr, depth=6, mode="parity", ssaa=1, adaptive=0):
     """Enqueue one whole image into device memory at d_out_ptr (W*H*3 B) with frames in
-    flight (rc_frame_submit); returns at once.  Pair with frames_wait().  ssaa > 1: fast and
-    cuda mode only (parity frames in flight do not supersample)."""
-    opt = options(depth, mode, ssaa=ssaa)
+    flight (rc_frame_submit); returns at once.  Pair with frames_wait().  ssaa > 1 (and
+    adaptive): fast and cuda mode only (parity frames in flight do not supersample)."""
+    opt = options(depth, mode, ssaa=ssaa, adaptive=adaptive)
     if hip_lib().rc_frame_submit(scene.packed(), width, height, ctypes.byref(opt),
                                  ctypes.c_void_p(d_out_ptr)) != 0:
         raise RuntimeError("rc_frame_submit failed (see stderr)")
@@ -464,6 +526,24 @@ def frames_wait(timing=None):
                            "frames' carry hand-offs failed (see stderr)")
     if timing is not None:
         timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+
+
+def adaptive_stats():
+    """The last adaptive frame enqueued on the current device (rc_adaptive_stats_get, which
+    waits for it): {"refined_pixels": pixels with contrast >= t, "rays": W*H + s*s*that}."""
+    st = RcAdaptiveStats()
+    if hip_lib().rc_adaptive_stats_get(ctypes.byref(st)) != 0:
+        raise RuntimeError("rc_adaptive_stats_get: no adaptive frame on this device")
+    return {k: getattr(st, k) for k, _ in RcAdaptiveStats._fields_}
+
+
+def adaptive_phase_ms():
+    """Kernel spans of the last timed adaptive frame (rc_adaptive_phase_ms), in ms:
+    {"render", "mark", "refine"}."""
+    ms = (ctypes.c_double * 3)()
+    if hip_lib().rc_adaptive_phase_ms(ms) != 0:
+        raise RuntimeError("rc_adaptive_phase_ms: no timed adaptive frame on this device")
+    return {"render": ms[0], "mark": ms[1], "refine": ms[2]}
 
 
 SPIN_SITES = ("team_handoff", "phase_c_carry_in", "ready_queue", "helper_queue")

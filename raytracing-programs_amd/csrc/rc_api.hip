@@ -30,7 +30,7 @@
 #include "rc_runtime.h"
 #include "rc_scene.h"
 
-#define RC_VERSION "raycast-mi355x 0.2 (gfx950)"
+#define RC_VERSION "raycast-mi355x 0.3 (gfx950)"
 
 namespace rcrt {
 
@@ -88,6 +88,7 @@ rc_tuning default_tuning() {
   t.headb_first = 24;
   t.pipe_last_whole = 1;
   t.ssaa_fused = 1;
+  t.adaptive_blocks = 0;
   return t;
 }
 rc_tuning g_tune = default_tuning();
@@ -683,7 +684,7 @@ int rc_set_tuning(const rc_tuning* t) {
       in(t->resolve_clean, 1, 64) && in(t->shard_lone, 0, 1) && in(t->team_cscan, 0, 1) &&
       in(t->pipe_order, 0, 4) && in(t->pipe_helpers, 0, rc::kDenseSlots) &&
       in(t->patch_host, 0, 2) && in(t->share_device, 0, 1) && in(t->headb_first, 0, 1 << 16) && in(t->pipe_last_whole, 0, 1) &&
-      in(t->ssaa_fused, 0, 1) &&
+      in(t->ssaa_fused, 0, 1) && in(t->adaptive_blocks, 0, 4096) &&
       !(t->split_shade && !t->side);
   if (!ok) {
     std::fprintf(stderr, "Error: rc_set_tuning: a field is out of range\n");
@@ -712,6 +713,38 @@ int rc_set_tuning(const rc_tuning* t) {
 
 double rc_last_kernel_ms(void) { return g_last_kernel_ms; }
 
+int rc_adaptive_stats_get(rc_adaptive_stats* out) {
+  if (!out) return -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->aa_valid) return -1;
+  HIP_TRY(hipEventSynchronize(c->aa_done));   // the frame's stream, up to its refinement
+  unsigned n = 0;
+  HIP_TRY(hipMemcpy(&n, c->aa_count.p, sizeof n, hipMemcpyDeviceToHost));
+  out->refined_pixels = (int64_t)n;
+  out->rays = (int64_t)c->aa_pixels + (int64_t)c->aa_ss * c->aa_ss * (int64_t)n;
+  return 0;
+}
+
+int rc_adaptive_phase_ms(double ms[3]) {
+  if (!ms) return -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->aa_ev) return -1;
+  hipEvent_t* ev = c->aa_ev;
+  HIP_TRY(hipEventSynchronize(ev[1]));
+  ms[0] = event_ms(ev[0], ev[2]);
+  ms[1] = event_ms(ev[2], ev[3]);
+  ms[2] = event_ms(ev[3], ev[1]);
+  return 0;
+}
+
 void rc_default_options(rc_options* opt, int use_env) {
   opt->max_recursion = 7;   // C/raycast.c:14
   opt->mode = RC_MODE_PARITY;
@@ -735,6 +768,18 @@ void rc_default_options(rc_options* opt, int use_env) {
       opt->ssaa = a[0] - '0';
     else
       std::fprintf(stderr, "Warning: RAYCAST_SSAA '%s' is not 1, 2, 4 or 8, using 1\n", a);
+  }
+  if (const char* a = std::getenv("RAYCAST_SSAA_ADAPTIVE")) {
+    char* end = nullptr;
+    const long t = std::strtol(a, &end, 10);
+    if (a[0] < '0' || a[0] > '9' || *end != '\0' || t < 1 || t > 255)
+      std::fprintf(stderr, "Warning: RAYCAST_SSAA_ADAPTIVE '%s' is not a threshold 1..255, "
+                   "adaptive supersampling is off\n", a);
+    else if (opt->ssaa < 2)
+      std::fprintf(stderr, "Warning: RAYCAST_SSAA_ADAPTIVE '%s' needs RAYCAST_SSAA 2, 4 or 8, "
+                   "ignored\n", a);
+    else
+      opt->ssaa = RC_SSAA_ADAPTIVE(opt->ssaa, (int)t);
   }
 }
 
@@ -1030,11 +1075,38 @@ int enqueue_render(DevCtx& c, const rc_scene* s, int W, int H, int row0, int row
   return rc;
 }
 
-int ssaa_factor(const rc_options* opt, const char* who) {
-  const int a = opt->ssaa;
-  if (a == 0 || a == 1) return 1;
-  if (a == 2 || a == 4 || a == 8) return a;
-  std::fprintf(stderr, "Error: %s: ssaa %d is not 0, 1, 2, 4 or 8\n", who, a);
+// The one decoding point of rc_options.ssaa = s | (t << 8) (RC_SSAA_ADAPTIVE): s in
+// {0, 1, 2, 4, 8}, t in 0..255, no higher bit, and t > 0 only with s >= 2.
+static int ssaa_decode(const rc_options* opt, const char* who, int* threshold) {
+  const int v = opt->ssaa;
+  const int a = RC_SSAA_FACTOR(v), t = RC_SSAA_THRESHOLD(v);
+  if (v < 0 || v != RC_SSAA_ADAPTIVE(a, t) || !(a == 0 || a == 1 || a == 2 || a == 4 || a == 8)) {
+    std::fprintf(stderr, "Error: %s: ssaa %d is not 0, 1, 2, 4 or 8 (alone or with an adaptive "
+                 "threshold 1..255 in bits 8..15)\n", who, v);
+    return -1;
+  }
+  if (t > 0 && a < 2) {
+    std::fprintf(stderr, "Error: %s: adaptive threshold %d needs an ssaa factor of 2, 4 or 8 "
+                 "(got %d)\n", who, t, a);
+    return -1;
+  }
+  if (threshold) *threshold = t;
+  return a == 0 ? 1 : a;
+}
+
+int ssaa_factor(const rc_options* opt, const char* who) { return ssaa_decode(opt, who, nullptr); }
+
+int ssaa_threshold(const rc_options* opt, const char* who) {
+  int t = 0;
+  return ssaa_decode(opt, who, &t) < 0 ? -1 : t;
+}
+
+// Adaptive supersampling's refusals that do not depend on the entry point.
+static int adaptive_refused(const rc_options* opt, const char* who, int ss, int at) {
+  if (opt->mode != RC_MODE_PARITY) return 0;
+  std::fprintf(stderr, "Error: %s: adaptive supersampling (ssaa %d, threshold %d) is for fast "
+               "and cuda mode: every pixel of the parity image of %d times the size depends on "
+               "the scan-order carry of the whole image; use plain ssaa\n", who, ss, at, ss);
   return -1;
 }
 
@@ -1075,14 +1147,39 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
                       bool timed, uint32_t* patch, hipEvent_t** evset) {
   const int ss = ssaa_factor(opt, "render");
   if (ss < 0) return -1;
-  const bool fused = ss > 1 && opt->mode == RC_MODE_FAST && tune().ssaa_fused;
-  if (ss > 1 && !fused)
+  // adaptive (at > 0): the one-ray image through the plain kernel, then the edge list and the
+  // refinement of the listed pixels below
+  const int at = ssaa_threshold(opt, "render");
+  if (at > 0) {
+    if (adaptive_refused(opt, "render", ss, at)) return -1;
+    if (row0 != 0 || row_step != 1 || nrows != H) {
+      std::fprintf(stderr, "Error: adaptive supersampling renders whole images only (row0 %d, "
+                   "row_step %d, nrows %d of %d): the contrast needs the neighbouring rows\n",
+                   row0, row_step, nrows, H);
+      return -1;
+    }
+    if ((unsigned long long)W * (unsigned long long)H >= (1ull << 32) ||
+        W > 0x7fffffff / ss || H > 0x7fffffff / ss) {
+      std::fprintf(stderr, "Error: adaptive supersampling: %d x %d is too large (32-bit pixel "
+                   "indices)\n", W, H);
+      return -1;
+    }
+    if (c.aa_list.ensure((size_t)W * H * sizeof(uint32_t)) || c.aa_count.ensure(8)) {
+      std::fprintf(stderr, "Error: out of device memory for the edge list (%d x %d)\n", W, H);
+      return -1;
+    }
+    if (!c.aa_done) HIP_TRY(hipEventCreateWithFlags(&c.aa_done, hipEventDisableTiming));
+  }
+  const bool fused = ss > 1 && at == 0 && opt->mode == RC_MODE_FAST && tune().ssaa_fused;
+  if (ss > 1 && at == 0 && !fused)
     return enqueue_render_two_pass(c, s, W, H, ss, row0, row_step, nrows, opt, d_out, stream,
                                    timed, evset);
   rc::LaunchScene ls;
   if (upload_scene(c.fb, stream, s, ls)) return -1;
   unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
   HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
+  // the edge list's counter block, here rather than between the render and the list kernel
+  if (at > 0) HIP_TRY(hipMemsetAsync(c.aa_count.p, 0, 8, stream));
   const int maxrec = opt->max_recursion;
   const bool parity = opt->mode == RC_MODE_PARITY && maxrec > 1;
   hipEvent_t* ev = c.ev[0];
@@ -1092,6 +1189,7 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
     c.prof_parity = parity;
   }
   if (evset) *evset = ev;
+  if (timed && c.aa_ev == ev) c.aa_ev = nullptr;   // the set is recorded anew (rc_adaptive_phase_ms)
   if (timed) HIP_TRY(hipEventRecord(ev[0], stream));
   if (!parity) {
     if (fused)   // the subsamples on adjacent lanes, box-filtered in registers
@@ -1100,6 +1198,21 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
     else
       HIP_TRY(rc::launch_render(ls, W, H, row0, row_step, nrows, maxrec, d_out, zc, stream,
                                 opt->mode == RC_MODE_CUDA));
+    if (at > 0) {
+      unsigned* cnt = (unsigned*)c.aa_count.p;
+      uint32_t* list = (uint32_t*)c.aa_list.p;
+      if (timed) HIP_TRY(hipEventRecord(ev[2], stream));
+      HIP_TRY(rc::launch_aa_mark(d_out, W, H, at, list, cnt, stream));
+      if (timed) HIP_TRY(hipEventRecord(ev[3], stream));
+      HIP_TRY(rc::launch_aa_refine(ls, W, H, ss, maxrec, list, cnt, d_out, zc,
+                                   rc::aa_refine_blocks(W, H, ss, c.cus, tune().adaptive_blocks),
+                                   stream, opt->mode == RC_MODE_CUDA));
+      HIP_TRY(hipEventRecord(c.aa_done, stream));
+      c.aa_valid = true;
+      c.aa_ss = ss;
+      c.aa_pixels = (long long)W * H;
+      if (timed) c.aa_ev = ev;
+    }
     if (timed) HIP_TRY(hipEventRecord(ev[1], stream));
     return 0;
   }
@@ -1608,6 +1721,8 @@ int rc_frame_submit(const rc_scene* s, int W, int H, const rc_options* opt, uint
   if (!s || !opt || !d_out || W <= 0 || H <= 0) return -1;
   const int ss = ssaa_factor(opt, "rc_frame_submit");
   if (ss < 0) return -1;
+  const int at = ssaa_threshold(opt, "rc_frame_submit");
+  if (at > 0 && adaptive_refused(opt, "rc_frame_submit", ss, at)) return -1;
   if (ss > 1 && opt->mode == RC_MODE_PARITY) {   // the frame pipeline stays as it is
     std::fprintf(stderr, "Error: rc_frame_submit: parity frames in flight do not supersample "
                  "(ssaa %d); use rc_render_device\n", ss);
@@ -1942,6 +2057,8 @@ int rc_render(const rc_scene* s, int W, int H, const rc_options* opt, uint8_t* p
                  "supersample\n", ss, opt->num_gpus);
     return -1;
   }
+  const int at = ssaa_threshold(opt, "rc_render");
+  if (at > 0 && adaptive_refused(opt, "rc_render", ss, at)) return -1;
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   int G = opt->num_gpus;

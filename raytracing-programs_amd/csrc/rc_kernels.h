@@ -101,6 +101,25 @@ hipError_t launch_render_ssaa(const LaunchScene& s, int W, int H, int ssaa, int 
 hipError_t launch_box_down(const uint8_t* src, int W, int H, int ssaa, uint8_t* dst,
                            hipStream_t stream);
 
+// Adaptive supersampling (rc_options.ssaa = RC_SSAA_ADAPTIVE(s, t); fast and cuda modes), after
+// launch_render has put the one-ray W x H image into `img`, all on one stream:
+//   launch_aa_mark    appends the index y*W + x of every pixel whose 3x3 contrast is >= threshold
+//                     to `list` (W*H entries of room) and counts them in *count (zeroed by the
+//                     caller, on the stream); W*H >= 2^32 is refused;
+//   launch_aa_refine  shoots the ssaa x ssaa subsamples of the listed pixels with the camera of
+//                     the ssaa*W x ssaa*H image and stores their box filter over `out`'s pixels;
+//                     `blocks` workgroups (aa_refine_blocks) stride over the list, whose length
+//                     is read on the device.  zcount: the subsamples' zero-normalize events (fast).
+// Mark reads pixels that refine overwrites: they must stay two launches.
+hipError_t launch_aa_mark(const uint8_t* img, int W, int H, int threshold, uint32_t* list,
+                          unsigned* count, hipStream_t stream);
+hipError_t launch_aa_refine(const LaunchScene& s, int W, int H, int ssaa, int maxrec,
+                            const uint32_t* list, const unsigned* count, uint8_t* out,
+                            unsigned long long* zcount, int blocks, hipStream_t stream,
+                            bool cuda_sem);
+// want > 0: that many; else from the CU count, at most the wave steps a W x H list can need
+int aa_refine_blocks(int W, int H, int ssaa, int cus, int want);
+
 hipError_t launch_parity(const LaunchScene& s, int W, int H, int maxrec, uint8_t* out,
                          const ParityWork& w, unsigned long long* zcount, hipStream_t stream,
                          const hipEvent_t* ev);

@@ -22,6 +22,9 @@
 //   k_render_ssaa fast mode with s x s supersampling: one lane per subsample, the box filter
 //                 across the lanes of a wave, one store per output pixel.
 //   k_box_down    the box filter of an s*W x s*H image in memory (parity and cuda modes).
+//   k_aa_mark / k_aa_refine
+//                 adaptive supersampling (fast and cuda modes): the list of the one-ray image's
+//                 edge pixels (3x3 contrast >= t), then the s x s subsamples of those pixels only.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -370,6 +373,173 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
   if (x >= W || r >= nrows) return;
   const V3 c = cusem::render_pixel(sc, cam, x, row0 + r * row_step, maxrec - 1);
   store_rgb(out + ((size_t)r * W + x) * 3, c);
+}
+
+// ------------------------------------------- adaptive supersampling (fast, cuda) --
+// rc_options.ssaa = RC_SSAA_ADAPTIVE(s, t): the one-ray image A is rendered into `out` by
+// k_render / k_render_cuda, k_aa_mark lists the pixels of A whose 3x3 contrast reaches t, and
+// k_aa_refine shoots the s x s subsamples of the listed pixels only and stores their box filter
+// over A's pixel.  Mark reads neighbours that refine overwrites, so the two are separate
+// launches on one stream: the list is complete before the first refined store.
+//
+// k_aa_mark: one lane per pixel.  A workgroup is four waves side by side, each taking 64 adjacent
+// columns of kMarkRows rows of tile (tx, ty) (the tile index is divided once per workgroup, in
+// scalars).  A wave walks down its rows with a rolling window of three: of every row it loads
+// each lane's own pixel once (packed R | G << 8 | B << 16), takes the left and right neighbours
+// from the adjacent lanes, and only lanes 0 and 63 load the pixel beyond the wave, so a pixel
+// costs 3 * (kMarkRows + 2) / kMarkRows byte loads instead of 27.  Coordinates are clamped to
+// the image: a clamped neighbour is a pixel of the window taken twice, which changes neither max
+// nor min.  List slots are reserved per wave: a ballot of the flagged lanes of every row, one
+// atomicAdd of their popcounts' sum by lane 0, and each flagged lane writes at base + the flagged
+// pixels of the rows above + the popcount of the flagged lanes below it in its row.  Every lane
+// of a wave reaches the shuffles and the ballots (lanes past the image load and flag nothing;
+// skipping a row past the image is uniform).  The list's order follows
+// the atomics' arrival and is not deterministic; no output byte depends on it.
+constexpr int kMarkBlock = 256, kMarkRows = 8;
+struct MarkRow {
+  int lo[3], hi[3];   // per channel, over the pixel and its two neighbours in the row
+};
+__device__ __forceinline__ unsigned mark_load(const uint8_t* __restrict__ q) {
+  return (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
+}
+// in: x < W.  y < H.  Called by every lane of the wave.
+__device__ __forceinline__ MarkRow mark_row(const uint8_t* __restrict__ img, unsigned W, unsigned x,
+                                            unsigned y, int lane, bool in) {
+  const uint8_t* q = img + (size_t)y * W * 3;
+  const unsigned v = in ? mark_load(q + (size_t)x * 3) : 0u;
+  unsigned l = __shfl_up(v, 1, 64), r = __shfl_down(v, 1, 64);
+  if (in) {
+    if (x == 0u) l = v;
+    else if (lane == 0) l = mark_load(q + (size_t)(x - 1u) * 3);
+    if (x + 1u >= W) r = v;
+    else if (lane == 63) r = mark_load(q + (size_t)(x + 1u) * 3);
+  }
+  MarkRow m;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int a = (int)((v >> (8 * c)) & 255u), b = (int)((l >> (8 * c)) & 255u),
+              d = (int)((r >> (8 * c)) & 255u);
+    const int lo = a < b ? a : b, hi = a > b ? a : b;
+    m.lo[c] = lo < d ? lo : d;
+    m.hi[c] = hi > d ? hi : d;
+  }
+  return m;
+}
+__global__ void __launch_bounds__(kMarkBlock) k_aa_mark(const uint8_t* __restrict__ img, int W,
+                                                        int H, unsigned tiles_x, int thr,
+                                                        uint32_t* __restrict__ list,
+                                                        unsigned* __restrict__ count) {
+  const unsigned ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+  const int lane = threadIdx.x & 63;
+  const unsigned x = tx * kMarkBlock + threadIdx.x;   // tx * 256 < W + 256 <= 2^31 + 255
+  const unsigned y0 = ty * kMarkRows, w = (unsigned)W, h = (unsigned)H;   // y0 < H
+  const bool in = x < w;
+  MarkRow p = mark_row(img, w, x, y0 > 0u ? y0 - 1u : 0u, lane, in);
+  MarkRow c = mark_row(img, w, x, y0, lane, in);
+  unsigned long long flagged[kMarkRows];   // per row, the ballot of its flagged lanes (uniform)
+  unsigned total = 0u;
+#pragma unroll
+  for (int k = 0; k < kMarkRows; ++k) {
+    const unsigned y = y0 + (unsigned)k;
+    flagged[k] = 0ull;
+    if (y >= h) continue;   // uniform
+    const MarkRow n = mark_row(img, w, x, y + 1u < h ? y + 1u : y, lane, in);
+    int con = 0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      int lo = p.lo[ch] < c.lo[ch] ? p.lo[ch] : c.lo[ch];
+      int hi = p.hi[ch] > c.hi[ch] ? p.hi[ch] : c.hi[ch];
+      lo = n.lo[ch] < lo ? n.lo[ch] : lo;
+      hi = n.hi[ch] > hi ? n.hi[ch] : hi;
+      con = hi - lo > con ? hi - lo : con;
+    }
+    flagged[k] = __ballot(in && con >= thr);
+    total += (unsigned)__popcll(flagged[k]);
+    p = c;
+    c = n;
+  }
+  // one reservation per wave for all its rows: the atomics all hit one address
+  unsigned base = 0u;
+  if (lane == 0 && total) base = atomicAdd(count, total);
+  base = __shfl(base, 0, 64);
+#pragma unroll
+  for (int k = 0; k < kMarkRows; ++k) {
+    const unsigned long long m = flagged[k];
+    if ((m >> lane) & 1ull)   // y*W + x < W*H < 2^32 (launch_aa_mark)
+      list[base + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] =
+          (uint32_t)((size_t)(y0 + (unsigned)k) * w + x);
+    base += (unsigned)__popcll(m);
+  }
+}
+
+// k_aa_refine: over the list, not the image.  A wave serves 64 / (s*s) listed pixels per step
+// (s = 1 << ls: 16, 4 or 1): lane l belongs to group l / (s*s) and shoots subsample
+// (i, j) = ((l % (s*s)) % s, (l % (s*s)) / s) of its group's pixel (x, y), that is the pixel
+// (s*x + i, s*y + j) of the s*W x s*H image with that image's camera (`cam`), exactly as
+// k_render_ssaa / the two-pass path do, so every subsample byte is that image's byte.  The
+// quantised channels are summed over the group with xor butterflies over the lane bits
+// 1 .. s*s/2 and the group's first lane stores (sum + s*s/2) / (s*s) over A's pixel.
+// The list's length is read from device memory (k_aa_mark's counter) and the grid is a fixed
+// number of workgroups whose waves stride over the list, so the host never waits between mark
+// and refine.  A wave's trip count depends on the wave alone, so all its lanes execute every
+// butterfly; lanes past the list's end shoot nothing, add zeros and store nothing.
+// kCuda: the CUDA port's arithmetic (k_render_cuda's pixel routine) instead of fast mode.
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_aa_refine(
+    Scene sc, Cam cam, int W, int ls, int maxrec, const uint32_t* __restrict__ list,
+    const unsigned* __restrict__ count, uint8_t* __restrict__ out,
+    unsigned long long* __restrict__ zcount) {
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  stage_scene<kStage>(sc, stage);   // its barrier comes before the loop: every thread is here
+  const unsigned n = *count;
+  const int lane = threadIdx.x & 63;
+  const unsigned per = 64u >> (2 * ls);                    // listed pixels per wave step
+  const unsigned sub = (unsigned)lane & ((1u << (2 * ls)) - 1u);   // subsample within the group
+  // wave-uniform by construction: told to the compiler, so the loop's counters stay scalar
+  const unsigned wave =
+      __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
+  const unsigned step = gridDim.x * (kBlock / 64) * per;   // <= 4096 * 4 * 16
+  // 64-bit index: n + step may pass 2^32
+  for (unsigned long long first = (unsigned long long)wave * per; first < n; first += step) {
+    const unsigned long long k = first + ((unsigned)lane >> (2 * ls));
+    const bool live = k < n;
+    unsigned p = 0u, rg = 0u, b = 0u;   // R | G << 16 and B: a channel's sum is <= 64 * 255
+    if (live) {
+      p = list[k];
+      const int xs = (int)((p % (unsigned)W) << ls) + (int)(sub & ((1u << ls) - 1u));
+      const int ys = (int)((p / (unsigned)W) << ls) + (int)(sub >> ls);
+      V3 c;
+      if constexpr (kCuda) {
+        c = cusem::render_pixel(sc, cam, xs, ys, maxrec - 1);
+      } else {
+        int zero = 0;
+        const V3 d = primary_dir(cam, xs, ys, zero);
+        PixelOut po;
+        shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
+        c = po.rgb;
+        flush_events(zero, zcount);
+      }
+      rg = (unsigned)quant(c.x) | ((unsigned)quant(c.y) << 16);
+      b = quant(c.z);
+    }
+    for (int m = 1; m < (1 << (2 * ls)); m <<= 1) {
+      rg += __shfl_xor(rg, m, 64);
+      b += __shfl_xor(b, m, 64);
+    }
+    if (live && sub == 0u) {
+      // the entry is read again (opaque index) rather than kept in a register across shoot,
+      // where the kernel sits at the 128-register edge
+      unsigned g = (unsigned)lane >> (2 * ls);
+      asm volatile("" : "+v"(g));
+      p = list[first + g];
+      const unsigned half = 1u << (2 * ls - 1);
+      uint8_t* q = out + (size_t)p * 3;
+      q[0] = (uint8_t)(((rg & 0xffffu) + half) >> (2 * ls));
+      q[1] = (uint8_t)(((rg >> 16) + half) >> (2 * ls));
+      q[2] = (uint8_t)((b + half) >> (2 * ls));
+    }
+  }
 }
 
 // ------------------------------------------------------------------ parity phase A --
@@ -3139,6 +3309,51 @@ hipError_t launch_box_down(const uint8_t* src, int W, int H, int ssaa, uint8_t* 
   const size_t blocks = ((size_t)W * H + 255) / 256;
   if (ls < 0 || W <= 0 || H <= 0 || blocks > 0x7fffffffu) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_box_down, dim3((unsigned)blocks), dim3(256), 0, stream, src, W, H, ls, dst);
+  return hipGetLastError();
+}
+
+hipError_t launch_aa_mark(const uint8_t* img, int W, int H, int threshold, uint32_t* list,
+                          unsigned* count, hipStream_t stream) {
+  if (W <= 0 || H <= 0 || threshold < 1 || threshold > 255) return hipErrorInvalidValue;
+  if ((unsigned long long)W * (unsigned long long)H >= (1ull << 32))
+    return hipErrorInvalidValue;   // pixel indices are uint32
+  const unsigned long long tiles_x = ((unsigned long long)W + kMarkBlock - 1) / kMarkBlock;
+  const unsigned long long tiles = tiles_x * (((unsigned long long)H + kMarkRows - 1) / kMarkRows);
+  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_aa_mark, dim3((unsigned)tiles), dim3(kMarkBlock), 0, stream, img, W, H,
+                     (unsigned)tiles_x, threshold, list, count);
+  return hipGetLastError();
+}
+
+int aa_refine_blocks(int W, int H, int ssaa, int cus, int want) {
+  if (want > 0) return want;
+  // the kernels are compiled for RC_PHASE_A_WAVES waves per SIMD: that many 4-wave workgroups
+  // per CU are resident at once; never more workgroups than the image has wave steps
+  const unsigned long long per = 64u / (unsigned)(ssaa * ssaa) * (kBlock / 64);
+  const unsigned long long need = ((unsigned long long)W * H + per - 1) / per;
+  const unsigned long long cap = (unsigned long long)(cus > 0 ? cus : 256) * RC_PHASE_A_WAVES;
+  return (int)(need < cap ? need : cap);
+}
+
+hipError_t launch_aa_refine(const LaunchScene& s, int W, int H, int ssaa, int maxrec,
+                            const uint32_t* list, const unsigned* count, uint8_t* out,
+                            unsigned long long* zcount, int blocks, hipStream_t stream,
+                            bool cuda_sem) {
+  const int ls = ssaa_log2(ssaa);
+  if (ls < 0 || W <= 0 || H <= 0 || W > 0x7fffffff / ssaa || H > 0x7fffffff / ssaa ||
+      blocks < 1 || blocks > 4096)
+    return hipErrorInvalidValue;
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, W * ssaa, H * ssaa);   // the camera of the s*W x s*H image
+  const bool st = stage_fits(s);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, sc, cam, W, ls,
+                       maxrec, list, count, out, zcount);
+  };
+  if (cuda_sem)
+    st ? go(k_aa_refine<true, true>) : go(k_aa_refine<true, false>);
+  else
+    st ? go(k_aa_refine<false, true>) : go(k_aa_refine<false, false>);
   return hipGetLastError();
 }
 

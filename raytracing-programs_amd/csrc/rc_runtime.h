@@ -170,13 +170,23 @@ struct DevCtx {
   int cus = 256;
   hipStream_t stream = nullptr;
   // event sets: [0] start, then per phase ends (fast: [1] = render; parity: [1] phase A,
-  // [2] compaction, [3] resolver, [4] phase C).  Set 0 serves plain calls; inside an
+  // [2] compaction, [3] resolver, [4] phase C; adaptive supersampling: [2] the one-ray image,
+  // [3] the edge list, [1] the refinement).  Set 0 serves plain calls; inside an
   // rc_profile_begin/end window every call takes the next set of the pool.
   static constexpr int kEvSets = 64;
   hipEvent_t ev[kEvSets][5] = {};
   int prof_active = 0, prof_calls = 0, prof_parity = 0;
   DevBuf out;          // rc_render output pixmap
   DevBuf ssaa;         // two-pass supersampling: the s*W x s*H image before the box filter
+  // adaptive supersampling: the edge list (uint32 pixel index, W*H entries of room) and its
+  // 8-byte counter block (word 0: entries), zeroed on the frame's stream before the list is made
+  DevBuf aa_list, aa_count;
+  hipEvent_t aa_done = nullptr;      // behind the last adaptive frame's refinement
+  bool aa_valid = false;             // an adaptive frame has been enqueued on this device
+  int aa_ss = 0;                     // its factor and pixels (rc_adaptive_stats_get)
+  long long aa_pixels = 0;
+  hipEvent_t* aa_ev = nullptr;       // the event set of the last timed adaptive frame:
+                                     // [0] start, [2] one-ray image, [3] list, [1] refinement
   uint8_t* stage[2] = {nullptr, nullptr};   // pinned bounce buffers of copy_to_host
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   FrameBufs fb;        // scene, counter and parity workspace of the plain path
@@ -245,6 +255,9 @@ int enqueue_render(DevCtx& c, const rc_scene* s, int W, int H, int row0, int row
 // rc_options.ssaa as a factor: 1 (0 and 1 are both off), 2, 4 or 8; -1 and a message naming
 // `who` for any other value
 int ssaa_factor(const rc_options* opt, const char* who);
+// rc_options.ssaa's adaptive threshold t: 0 (off) or 1..255 with a factor of 2, 4 or 8; -1 and
+// a message naming `who` otherwise (ssaa_factor's refusals included)
+int ssaa_threshold(const rc_options* opt, const char* who);
 int check_spin_error(FrameBufs& b, const rc_options* opt);
 void fill_device_timing(DevCtx& c, const rc_options* opt, rc_timing* t,
                         const uint8_t* tail = nullptr);
