@@ -207,6 +207,47 @@ int rc_adaptive_stats_get(rc_adaptive_stats *out);
  * the edge list, ms[2] the refinement.  Returns -1 if there was none. */
 int rc_adaptive_phase_ms(double ms[3]);
 
+/* Variable-rate supersampling from the caller's per-pixel rate map (rc_render_rates,
+ * rc_render_rates_device; fast and cuda mode).  Fix the scene, mode, depth, W and H, and let
+ *   F_1  be the W x H image of that mode with ssaa = 1,
+ *   F_s  for s in {2, 4, 8} be its image with ssaa = s (the box filter above),
+ *   R    be the rate map: W*H bytes, row-major, top row first.
+ * Then
+ *   R[y][x] in {1, 2, 4, 8}:  out[y][x] = F_{R[y][x]}[y][x]
+ *   R[y][x] == 0           :  the three bytes of out[y][x] are not stored to (they keep what
+ *                             the caller's buffer held)
+ *   any other value        :  invalid: rc_render_rates checks the map on the host before it
+ *                             enqueues anything, prints a message and returns -1 with the
+ *                             pixmap unchanged; rc_render_rates_device cannot see the bytes, so
+ *                             such a pixel is treated as rate 0 and counted in
+ *                             rc_rate_stats.invalid.
+ * Every output byte is an exact function of images the reference's arithmetic defines and does
+ * not depend on any execution order.  On the device: one kernel shoots the rate-1 pixels and
+ * bins the others into one list per factor (in no particular order), then each list's pixels
+ * get their s*s subsamples, on adjacent lanes, and the box filter of those is stored; all
+ * launches go to one stream with no host wait in between, so a map written on that stream just
+ * before the call is honoured.  The lists take 8 * W * H bytes of device memory.
+ * rc_options: mode fast or cuda; ssaa 0 or 1 (the map carries the factor); max_recursion as
+ * everywhere.  rc_timing.zero_normalize counts the rays actually shot, kernel_ms covers both
+ * stages.  The refinement's grids follow rc_tuning.adaptive_blocks.
+ * Refused, each with a message and -1: parity mode (every pixel of its s*W x s*H image depends
+ * on the scan-order carry of the whole image, so it cannot be shot sparsely); an ssaa factor
+ * above 1 or a threshold in the options; num_gpus > 1; null pointers; W * H >= 2^32, 8 * W or
+ * 8 * H past INT_MAX, or more than 65535 rows of 16-pixel tiles.
+ * raycast(), rc_render, rc_render_device and rc_frame_submit take no rate map. */
+typedef struct rc_rate_stats {
+  int64_t pixels[4];   /* pixels with rate 1, 2, 4, 8                          */
+  int64_t invalid;     /* map bytes outside {0,1,2,4,8} (treated as 0)         */
+  int64_t rays;        /* pixels[0] + 4*pixels[1] + 16*pixels[2] + 64*pixels[3] */
+} rc_rate_stats;
+_Static_assert(sizeof(rc_rate_stats) == 48, "rc_rate_stats layout (ctypes binding)");
+/* The last rate-map frame enqueued on the current device: waits for that frame, then reads its
+ * counters.  Returns -1 if there was none. */
+int rc_rate_stats_get(rc_rate_stats *out);
+/* The kernel spans (ms, HIP events) of the last rate-map frame on the current device: ms[0] the
+ * rate-1 pass with the binning, ms[1] the refinement.  Returns -1 if there was none. */
+int rc_rate_phase_ms(double ms[2]);
+
 typedef struct rc_timing {
   double total_ms;       /* whole call, host wall clock                                 */
   double kernel_ms;      /* sum of kernel spans (HIP events)                            */
@@ -246,6 +287,18 @@ int rc_render(const rc_scene *scene, int width, int height, const rc_options *op
 int rc_render_device(const rc_scene *scene, int width, int height, int row0, int row_step,
                      int nrows, const rc_options *opt, uint8_t *d_out, void *stream,
                      rc_timing *timing);
+
+/* Variable-rate supersampling (the rate-map contract above, at rc_rate_stats).
+ * rc_render_rates: host map (W*H bytes), host pixmap (W*H*3 bytes, in/out: the bytes of rate-0
+ * pixels are unchanged on return); synchronous, on opt->device.
+ * rc_render_rates_device: device map, device image, on the current device and the given HIP
+ * stream (NULL = default stream); asynchronous unless timing is requested.
+ * Both return 0 on success. */
+int rc_render_rates(const rc_scene *scene, int width, int height, const rc_options *opt,
+                    const uint8_t *rates, uint8_t *pixmap, rc_timing *timing);
+int rc_render_rates_device(const rc_scene *scene, int width, int height, const rc_options *opt,
+                           const uint8_t *d_rates, uint8_t *d_out, void *stream,
+                           rc_timing *timing);
 
 /* Frames in flight (an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out

@@ -79,6 +79,16 @@ class RcAdaptiveStats(ctypes.Structure):
     _fields_ = [("refined_pixels", ctypes.c_int64), ("rays", ctypes.c_int64)]
 
 
+class RcRateStats(ctypes.Structure):
+    """rc_rate_stats (48 bytes): pixels with rate 1, 2, 4, 8; invalid map bytes; rays shot."""
+    _fields_ = [("pixels", ctypes.c_int64 * 4), ("invalid", ctypes.c_int64),
+                ("rays", ctypes.c_int64)]
+
+
+# the values a rate map's bytes may take (rc_render_rates): 0 leaves the pixel alone
+RATE_VALUES = (0, 1, 2, 4, 8)
+
+
 class RcPhaseStats(ctypes.Structure):
     _fields_ = [("calls", ctypes.c_int), ("parity", ctypes.c_int), ("phase_a_ms", ctypes.c_double),
                 ("compact_ms", ctypes.c_double), ("resolve_ms", ctypes.c_double),
@@ -142,7 +152,8 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_default_tuning", "rc_set_tuning", "rc_get_tuning", "rc_lone_frames_check",
                "rc_debug_inject_error", "rc_group_debug_bound", "rc_resolver_stats_get",
                "rc_group_rank_stats", "rc_debug_scatter_selftest", "rc_adaptive_stats_get",
-               "rc_adaptive_phase_ms"]
+               "rc_adaptive_phase_ms", "rc_render_rates", "rc_render_rates_device",
+               "rc_rate_stats_get", "rc_rate_phase_ms"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -258,6 +269,15 @@ def _hip_lib_locked():
     lib.rc_group_rank_stats.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(RcRankStats)]
     lib.rc_adaptive_stats_get.argtypes = [ctypes.POINTER(RcAdaptiveStats)]
     lib.rc_adaptive_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    lib.rc_render_rates.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                    ctypes.POINTER(RcOptions), ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.POINTER(RcTiming)]
+    lib.rc_render_rates_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(RcOptions), ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.POINTER(RcTiming)]
+    lib.rc_rate_stats_get.argtypes = [ctypes.POINTER(RcRateStats)]
+    lib.rc_rate_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
     _hip = lib
     return lib
 
@@ -544,6 +564,94 @@ def adaptive_phase_ms():
     if hip_lib().rc_adaptive_phase_ms(ms) != 0:
         raise RuntimeError("rc_adaptive_phase_ms: no timed adaptive frame on this device")
     return {"render": ms[0], "mark": ms[1], "refine": ms[2]}
+
+
+def rates_compose(base, images, rates):
+    """The rate-map contract (include/raycast_hip.h, rc_render_rates) in numpy: `base` where the
+    rate is 0 and images[s] where it is s.  base and every image are [H, W, 3] uint8, rates is
+    [H, W] uint8 with values in RATE_VALUES; images needs an entry for every non-zero rate that
+    occurs."""
+    base, rates = np.asarray(base), np.asarray(rates)
+    if base.dtype != np.uint8 or base.ndim != 3 or base.shape[2] != 3:
+        raise ValueError(f"base: a uint8 [H, W, 3] image, got {base.dtype} {base.shape}")
+    if rates.dtype != np.uint8 or rates.shape != base.shape[:2]:
+        raise ValueError(f"rates: uint8 {base.shape[:2]}, got {rates.dtype} {rates.shape}")
+    out = base.copy()
+    for r in np.unique(rates).tolist():
+        if r not in RATE_VALUES:
+            raise ValueError(f"rate {r} is not one of {RATE_VALUES}")
+        if r == 0:
+            continue
+        if r not in images:
+            raise ValueError(f"rate {r} occurs in the map and images has no entry for it")
+        img = np.asarray(images[r])
+        if img.dtype != np.uint8 or img.shape != base.shape:
+            raise ValueError(f"images[{r}]: uint8 {base.shape}, got {img.dtype} {img.shape}")
+        sel = rates == r
+        out[sel] = img[sel]
+    return out
+
+
+def render_rates(scene, width, height, rates, depth=6, mode="fast", out=None, timing=None):
+    """Variable-rate supersampling through rc_render_rates: `rates` is the [H, W] uint8 map with
+    values in RATE_VALUES, `out` the caller's C-contiguous [H, W, 3] uint8 pixmap, in and out (the
+    default is zeros): a pixel of rate 0 keeps its bytes, one of rate s gets the ssaa = s image's
+    pixel (rates_compose).  Fast and cuda mode."""
+    lib = hip_lib()
+    rates = np.asarray(rates)
+    if rates.dtype != np.uint8 or rates.shape != (height, width):
+        raise ValueError(f"rates: uint8 {(height, width)}, got {rates.dtype} {rates.shape}")
+    rates = np.ascontiguousarray(rates)
+    if out is None:
+        out = np.zeros((height, width, 3), dtype=np.uint8)
+    assert out.shape == (height, width, 3) and out.dtype == np.uint8 and out.flags.c_contiguous
+    t = RcTiming()
+    opt = options(depth, mode)
+    rc = lib.rc_render_rates(scene.packed(), width, height, ctypes.byref(opt),
+                             rates.ctypes.data_as(ctypes.c_void_p),
+                             out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
+    if rc != 0:
+        raise RuntimeError("rc_render_rates failed (see stderr)")
+    if timing is not None:
+        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    return out
+
+
+def render_rates_device(scene, width, height, d_rates_ptr, d_out_ptr, stream_ptr=None, depth=6,
+                        mode="fast", timing=None):
+    """rc_render_rates_device: the map (W*H bytes) and the image (W*H*3 bytes) are device memory;
+    enqueued on the stream and asynchronous unless `timing` is given.  A map byte outside
+    RATE_VALUES leaves its pixel alone and is counted in rate_stats()["invalid"]."""
+    lib = hip_lib()
+    opt = options(depth, mode)
+    t = RcTiming()
+    rc = lib.rc_render_rates_device(scene.packed(), width, height, ctypes.byref(opt),
+                                    ctypes.c_void_p(d_rates_ptr), ctypes.c_void_p(d_out_ptr),
+                                    ctypes.c_void_p(stream_ptr),
+                                    ctypes.byref(t) if timing is not None else None)
+    if rc != 0:
+        raise RuntimeError("rc_render_rates_device failed (see stderr)")
+    if timing is not None:
+        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+
+
+def rate_stats():
+    """The last rate-map frame enqueued on the current device (rc_rate_stats_get, which waits for
+    it): {"pixels": {1: n, 2: n, 4: n, 8: n}, "invalid": map bytes outside RATE_VALUES, "rays"}."""
+    st = RcRateStats()
+    if hip_lib().rc_rate_stats_get(ctypes.byref(st)) != 0:
+        raise RuntimeError("rc_rate_stats_get: no rate-map frame on this device")
+    return {"pixels": {s: int(st.pixels[i]) for i, s in enumerate(RATE_VALUES[1:])},
+            "invalid": int(st.invalid), "rays": int(st.rays)}
+
+
+def rate_phase_ms():
+    """Kernel spans of the last rate-map frame (rc_rate_phase_ms), in ms: {"render": the rate-1
+    pass with the binning, "refine": the three lists}."""
+    ms = (ctypes.c_double * 2)()
+    if hip_lib().rc_rate_phase_ms(ms) != 0:
+        raise RuntimeError("rc_rate_phase_ms: no rate-map frame on this device")
+    return {"render": ms[0], "refine": ms[1]}
 
 
 SPIN_SITES = ("team_handoff", "phase_c_carry_in", "ready_queue", "helper_queue")

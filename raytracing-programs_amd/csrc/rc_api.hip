@@ -745,6 +745,41 @@ int rc_adaptive_phase_ms(double ms[3]) {
   return 0;
 }
 
+int rc_rate_stats_get(rc_rate_stats* out) {
+  if (!out) return -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->rate_valid) return -1;
+  HIP_TRY(hipEventSynchronize(c->rate_done));   // the frame's stream, up to its refinement
+  unsigned n[5] = {0, 0, 0, 0, 0};   // launch_rates_render's counter block
+  HIP_TRY(hipMemcpy(n, c->rate_count.p, sizeof n, hipMemcpyDeviceToHost));
+  out->pixels[0] = (int64_t)n[3];
+  out->pixels[1] = (int64_t)n[0];
+  out->pixels[2] = (int64_t)n[1];
+  out->pixels[3] = (int64_t)n[2];
+  out->invalid = (int64_t)n[4];
+  out->rays = out->pixels[0] + 4 * out->pixels[1] + 16 * out->pixels[2] + 64 * out->pixels[3];
+  return 0;
+}
+
+int rc_rate_phase_ms(double ms[2]) {
+  if (!ms) return -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->rate_ev) return -1;
+  hipEvent_t* ev = c->rate_ev;
+  HIP_TRY(hipEventSynchronize(ev[1]));
+  ms[0] = event_ms(ev[0], ev[2]);
+  ms[1] = event_ms(ev[2], ev[1]);
+  return 0;
+}
+
 void rc_default_options(rc_options* opt, int use_env) {
   opt->max_recursion = 7;   // C/raycast.c:14
   opt->mode = RC_MODE_PARITY;
@@ -1190,6 +1225,7 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
   }
   if (evset) *evset = ev;
   if (timed && c.aa_ev == ev) c.aa_ev = nullptr;   // the set is recorded anew (rc_adaptive_phase_ms)
+  if (timed && c.rate_ev == ev) c.rate_ev = nullptr;   // likewise (rc_rate_phase_ms)
   if (timed) HIP_TRY(hipEventRecord(ev[0], stream));
   if (!parity) {
     if (fused)   // the subsamples on adjacent lanes, box-filtered in registers
@@ -1238,6 +1274,102 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
   w.inject = take_inject();
   HIP_TRY(rc::launch_parity(ls, W, H, maxrec, d_out, w, zc, stream, timed ? ev + 1 : nullptr));
   return c.lone_log.enqueue(w.team, stream);
+}
+
+// Rate-map supersampling's refusals that do not depend on the entry point (rc_render_rates*).
+static int rates_refused(const rc_options* opt, const char* who, int W, int H) {
+  const int ss = ssaa_factor(opt, who);
+  if (ss < 0) return -1;   // ssaa_decode has said why (a threshold without a factor included)
+  if (ss > 1) {
+    std::fprintf(stderr, "Error: %s: ssaa %d in the options: the rate map carries the factor "
+                 "per pixel, leave ssaa at 0 or 1\n", who, opt->ssaa);
+    return -1;
+  }
+  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
+    std::fprintf(stderr, "Error: %s: a rate map is for fast and cuda mode: every pixel of a "
+                 "parity image depends on the scan-order carry of the whole image, so it cannot "
+                 "be shot sparsely\n", who);
+    return -1;
+  }
+  if (opt->num_gpus > 1) {
+    std::fprintf(stderr, "Error: %s: num_gpus %d: the row shards take no rate map\n", who,
+                 opt->num_gpus);
+    return -1;
+  }
+  if (!rc::rates_supported(W, H)) {
+    std::fprintf(stderr, "Error: %s: %d x %d is too large for a rate map (32-bit pixel indices "
+                 "at 8 subsamples a side, at most 65535 rows of tiles)\n", who, W, H);
+    return -1;
+  }
+  return 0;
+}
+
+// One rate-map frame on `stream` through the device's one-frame workspace (the caller holds
+// c.mu and has passed rates_refused): the rate-1 pixels with the binning, then the three lists'
+// refinements, with no host wait in between.  The host does not know which lists are empty, so
+// all three are launched.
+static int enqueue_rates(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
+                         const uint8_t* d_rates, uint8_t* d_out, hipStream_t stream) {
+  if (flush_phase_c(c, false)) return -1;
+  const size_t entries = (size_t)W * H;
+  if (c.aa_list.ensure(entries * sizeof(uint32_t)) ||
+      c.rate_list.ensure(entries * sizeof(uint32_t)) || c.rate_count.ensure(32)) {
+    std::fprintf(stderr, "Error: out of device memory for the rate lists (%d x %d)\n", W, H);
+    return -1;
+  }
+  if (!c.rate_done) HIP_TRY(hipEventCreateWithFlags(&c.rate_done, hipEventDisableTiming));
+  if (c.ws_valid && c.ws_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, c.ws_ev, 0));
+  auto body = [&]() -> int {
+    rc::LaunchScene ls;
+    if (upload_scene(c.fb, stream, s, ls)) return -1;
+    unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
+    unsigned* cnt = (unsigned*)c.rate_count.p;
+    uint32_t* list4 = (uint32_t*)c.aa_list.p;
+    uint32_t* list28 = (uint32_t*)c.rate_list.p;
+    HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(cnt, 0, 32, stream));
+    const int maxrec = opt->max_recursion;
+    const bool cuda = opt->mode == RC_MODE_CUDA;
+    hipEvent_t* ev = c.ev[0];
+    if (c.prof_active) {
+      ev = c.ev[c.prof_calls % DevCtx::kEvSets];
+      c.prof_calls++;
+      c.prof_parity = false;
+    }
+    if (c.aa_ev == ev) c.aa_ev = nullptr;   // the set is recorded anew (rc_adaptive_phase_ms)
+    c.rate_ev = nullptr;
+    // The lists follow the map's row-major order, so over a uniform region entry k is pixel
+    // k + const and a wave's static stride (workgroups * 4 waves * pixels per step) that is a
+    // multiple of W keeps the wave in one column of the image: the waves whose column crosses
+    // the expensive shapes finish last.  An odd number of workgroups makes the stride drift
+    // through the columns (measured: DESIGN.md section 12).  An explicit adaptive_blocks holds.
+    const int want = tune().adaptive_blocks;
+    auto blocks = [&](int ss) {
+      const int b = rc::aa_refine_blocks(W, H, ss, c.cus, want);
+      return want <= 0 && b > 2 && (b & 1) == 0 ? b - 1 : b;
+    };
+    HIP_TRY(hipEventRecord(ev[0], stream));
+    HIP_TRY(rc::launch_rates_render(ls, W, H, maxrec, d_rates, d_out, list4, list28, cnt, zc,
+                                    stream, cuda));
+    HIP_TRY(hipEventRecord(ev[2], stream));
+    HIP_TRY(rc::launch_aa_refine(ls, W, H, 2, maxrec, list28, cnt, d_out, zc,
+                                 blocks(2), stream, cuda));
+    HIP_TRY(rc::launch_aa_refine(ls, W, H, 4, maxrec, list4, cnt + 1, d_out, zc,
+                                 blocks(4), stream, cuda));
+    HIP_TRY(rc::launch_rates_refine8(ls, W, H, maxrec, list28, cnt + 2, d_out, zc,
+                                     blocks(8), stream, cuda));
+    HIP_TRY(hipEventRecord(c.rate_done, stream));
+    HIP_TRY(hipEventRecord(ev[1], stream));
+    c.rate_valid = true;
+    c.rate_ev = ev;
+    return 0;
+  };
+  const int rc = body();
+  // recorded even after a failed enqueue: whatever was enqueued stays ordered
+  HIP_TRY(hipEventRecord(c.ws_ev, stream));
+  c.ws_stream = stream;
+  c.ws_valid = true;
+  return rc;
 }
 
 // After a synchronised parity render: the resolver's and phase C's bounded spins set
@@ -1535,6 +1667,93 @@ int rc_render_device(const rc_scene* s, int W, int H, int row0, int row_step, in
     timing->frames_checked = c->lone_log.checked - before;
     fill_device_timing(*c, opt, timing);
     timing->total_ms = timing->kernel_ms;
+  }
+  return 0;
+}
+
+int rc_render_rates_device(const rc_scene* s, int W, int H, const rc_options* opt,
+                           const uint8_t* d_rates, uint8_t* d_out, void* stream,
+                           rc_timing* timing) {
+  if (!s || !opt || !d_rates || !d_out) {
+    std::fprintf(stderr, "Error: rc_render_rates_device: a null pointer\n");
+    return -1;
+  }
+  if (W <= 0 || H <= 0) return -1;
+  if (rates_refused(opt, "rc_render_rates_device", W, H)) return -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  // an earlier frame of this workspace whose hand-off failed is reported by the next call
+  if (c->lone_log.earlier_failed()) {
+    c->lone_log.take(nullptr, nullptr);
+    return -1;
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if (enqueue_rates(*c, s, W, H, opt, d_rates, d_out, st)) return -1;
+  if (timing) {
+    std::memset(timing, 0, sizeof *timing);
+    HIP_TRY(hipStreamSynchronize(st));
+    fill_device_timing(*c, opt, timing);
+    timing->total_ms = timing->kernel_ms;
+  }
+  return 0;
+}
+
+int rc_render_rates(const rc_scene* s, int W, int H, const rc_options* opt, const uint8_t* rates,
+                    uint8_t* pixmap, rc_timing* timing) {
+  if (!s || !opt || !rates || !pixmap) {
+    std::fprintf(stderr, "Error: rc_render_rates: a null pointer\n");
+    return -1;
+  }
+  if (W <= 0 || H <= 0) return -1;
+  auto t0 = std::chrono::steady_clock::now();
+  if (rates_refused(opt, "rc_render_rates", W, H)) return -1;
+  const size_t pixels = (size_t)W * H;
+  for (size_t i = 0; i < pixels; ++i) {
+    const unsigned r = rates[i];
+    if (r > 8u || !((0x117u >> r) & 1u)) {   // bits 0, 1, 2, 4, 8
+      std::fprintf(stderr, "Error: rc_render_rates: rate %u at pixel (%zu, %zu) is not 0, 1, 2, "
+                   "4 or 8\n", r, i % (size_t)W, i / (size_t)W);
+      return -1;
+    }
+  }
+  if (timing) std::memset(timing, 0, sizeof *timing);
+  const rc_tuning tu = tune();
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (opt->device < 0 || opt->device >= ndev) {
+    std::fprintf(stderr, "Error: device %d not available (%d devices)\n", opt->device, ndev);
+    return -1;
+  }
+  DevCtx* c;
+  if (hipSetDevice(opt->device) != hipSuccess || ctx_get(opt->device, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (c->lone_log.earlier_failed()) {
+    c->lone_log.take(nullptr, nullptr);
+    return -1;
+  }
+  if (c->out.ensure(pixels * 3) || c->rate_map.ensure(pixels)) {
+    std::fprintf(stderr, "Error: out of device memory for the image and its rate map (%d x %d)\n",
+                 W, H);
+    return -1;
+  }
+  uint8_t* d_out = (uint8_t*)c->out.p;
+  uint8_t* d_rates = (uint8_t*)c->rate_map.p;
+  // the pixmap goes in as well as out: the bytes of rate-0 pixels come back as they were
+  HIP_TRY(hipMemcpyAsync(d_rates, rates, pixels, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_out, pixmap, pixels * 3, hipMemcpyHostToDevice, c->stream));
+  if (enqueue_rates(*c, s, W, H, opt, d_rates, d_out, c->stream)) return -1;
+  auto td = std::chrono::steady_clock::now();
+  if (copy_to_host(*c, pixmap, d_out, pixels * 3, c->stream, tu)) return -1;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  fill_device_timing(*c, opt, timing);
+  if (timing) {
+    timing->d2h_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
+    timing->total_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return 0;
 }

@@ -120,6 +120,26 @@ hipError_t launch_aa_refine(const LaunchScene& s, int W, int H, int ssaa, int ma
 // want > 0: that many; else from the CU count, at most the wave steps a W x H list can need
 int aa_refine_blocks(int W, int H, int ssaa, int cus, int want);
 
+// Supersampling by a per-pixel rate map (rc_render_rates*; fast and cuda modes), all on one
+// stream.  cnt is five words zeroed by the caller on the stream: [0] [1] [2] the lengths of the
+// rate-2, rate-4 and rate-8 lists, [3] the rate-1 pixels, [4] the map bytes that are no rate.
+//   launch_rates_render   shoots the rate-1 pixels of `rates` (W*H bytes) into `out` and lists
+//                         the others: rate 4 in list4, rate 2 upwards from list28[0], rate 8
+//                         downwards from list28[W*H - 1] (W*H entries each);
+//   launch_aa_refine      (above) then serves the rate-2 list (list28, cnt) and the rate-4 list
+//                         (list4, cnt + 1);
+//   launch_rates_refine8  serves the rate-8 list (list28, cnt + 2) with `blocks` workgroups.
+// rates_supported: W*H < 2^32, 8*W and 8*H within int, a grid the tile layout can address.
+int rates_supported(int W, int H);
+hipError_t launch_rates_render(const LaunchScene& s, int W, int H, int maxrec,
+                               const uint8_t* rates, uint8_t* out, uint32_t* list4,
+                               uint32_t* list28, unsigned* cnt, unsigned long long* zcount,
+                               hipStream_t stream, bool cuda_sem);
+hipError_t launch_rates_refine8(const LaunchScene& s, int W, int H, int maxrec,
+                                const uint32_t* list28, const unsigned* count, uint8_t* out,
+                                unsigned long long* zcount, int blocks, hipStream_t stream,
+                                bool cuda_sem);
+
 hipError_t launch_parity(const LaunchScene& s, int W, int H, int maxrec, uint8_t* out,
                          const ParityWork& w, unsigned long long* zcount, hipStream_t stream,
                          const hipEvent_t* ev);

@@ -25,6 +25,10 @@
 //   k_aa_mark / k_aa_refine
 //                 adaptive supersampling (fast and cuda modes): the list of the one-ray image's
 //                 edge pixels (3x3 contrast >= t), then the s x s subsamples of those pixels only.
+//   k_rates_render / k_rates_refine8
+//                 supersampling by the caller's per-pixel rate map (fast and cuda modes): the
+//                 rate-1 pixels and one list per factor, refined by k_aa_refine (2, 4) and by
+//                 k_rates_refine8 (8, whose list grows downwards).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -538,6 +542,179 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
       q[0] = (uint8_t)(((rg & 0xffffu) + half) >> (2 * ls));
       q[1] = (uint8_t)(((rg >> 16) + half) >> (2 * ls));
       q[2] = (uint8_t)((b + half) >> (2 * ls));
+    }
+  }
+}
+
+// ---------------------------------------- rate-map supersampling (fast, cuda) --
+// rc_render_rates*: the caller's map gives every pixel a rate in {0, 1, 2, 4, 8} (one byte per
+// pixel, row-major): 0 leaves the pixel's bytes alone, 1 is the one-ray pixel, s > 1 the ssaa = s
+// pixel.  k_rates_render shoots the rate-1 pixels and bins the others into one list per factor;
+// k_aa_refine (rates 2 and 4) and k_rates_refine8 then shoot the listed pixels' subsamples.  No
+// pixel is in two classes and nobody reads a pixel, so the stream order of the launches is all
+// the ordering there is.
+//
+// k_rates_render: k_render's grid and tiles (one lane per pixel) for the rate-1 pixels.  The
+// binning comes first, so nothing of it is live across shoot, and it does not follow the tiles:
+// the map is cut into chunks of kRateChunk * 256 consecutive pixels (row-major, so the byte loads
+// are contiguous) and one workgroup in every kRateChunk takes a chunk, so a class's counter gets
+// one atomicAdd per chunk and not one per wave (same-address atomics were what the first form's
+// time followed).  The chunk's workgroup counts first: per wave and step
+// a ballot per class, the waves' sums through LDS, one atomicAdd per class by one thread; then it
+// reads the chunk again and every flagged lane writes its pixel index y*W + x at the class's base
+// + the flagged pixels of the waves and steps before it + the popcount of the flagged lanes below
+// it (k_aa_mark's reservation, one level up).  Every lane of a wave reaches the ballots; lanes
+// past the map flag nothing.  The duty rotates over the eight residues of the workgroup index, so
+// it does not fall on one XCD.  cnt: [0] [1] [2] the lengths of the rate-2, rate-4 and rate-8
+// lists, [3] the rate-1 pixels, [4] the map bytes that are no rate (those pixels are left alone,
+// like rate 0).  The rate-2 list grows upwards from list2up, the rate-8 list downwards from
+// list8down (the two ends of one W*H-entry buffer: together they never hold more than W*H
+// entries), the rate-4 list upwards from list4.
+// A workgroup without a rate-1 pixel ends before stage_scene; the decision is one
+// __syncthreads_or, so stage_scene's barrier stays uniform.  A rate-1 lane stores its own three
+// bytes: a wider store would write into a neighbour that may have rate 0.
+constexpr int kRateChunk = 8;   // tiles' worth of pixels per binning workgroup (a power of two)
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_rates_render(
+    Scene sc, Cam cam, int W, int H, int maxrec, const uint8_t* __restrict__ rates,
+    uint8_t* __restrict__ out, uint32_t* __restrict__ list2up, uint32_t* __restrict__ list4,
+    uint32_t* __restrict__ list8down, unsigned* __restrict__ cnt,
+    unsigned long long* __restrict__ zcount) {
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  __shared__ unsigned wsum[kBlock / 64][5];   // per wave: the chunk's pixels per counter of cnt
+  __shared__ unsigned wbase[3];               // the chunk's first slot in each list
+  {
+    const int lin = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
+    const int nwg = (int)gridDim.x * (int)gridDim.y;
+    const int chunk = lin / kRateChunk;
+    int duty = chunk % kRateChunk;   // which workgroup of the chunk's kRateChunk bins it
+    if (chunk * kRateChunk + duty >= nwg) duty = 0;
+    if (lin % kRateChunk == duty) {   // uniform over the workgroup: the barriers below are too
+      const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+      const unsigned long long below = (1ull << lane) - 1ull;
+      const size_t n = (size_t)W * H;   // < 2^32; the grid's workgroups * 256 >= n
+      const size_t first = (size_t)chunk * (kRateChunk * kBlock) + threadIdx.x;
+      unsigned tot[5] = {0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int it = 0; it < kRateChunk; ++it) {
+        const size_t i = first + (size_t)it * kBlock;
+        const unsigned rate = i < n ? (unsigned)rates[i] : 0u;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tot[k] += (unsigned)__popcll(__ballot(rate == (2u << k)));
+        tot[3] += (unsigned)__popcll(__ballot(rate == 1u));
+        tot[4] += (unsigned)__popcll(__ballot(!(rate <= 2u || rate == 4u || rate == 8u)));
+      }
+      if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) wsum[wave][k] = tot[k];
+      }
+      __syncthreads();
+      if (threadIdx.x < 5) {
+        unsigned sum = 0u;
+        for (int w = 0; w < kBlock / 64; ++w) sum += wsum[w][threadIdx.x];
+        unsigned base = 0u;
+        if (sum) base = atomicAdd(cnt + threadIdx.x, sum);
+        if (threadIdx.x < 3) wbase[threadIdx.x] = base;
+      }
+      __syncthreads();
+      unsigned base[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        base[k] = wbase[k];
+        for (int w = 0; w < wave; ++w) base[k] += wsum[w][k];
+      }
+      if (tot[0] | tot[1] | tot[2]) {   // uniform over the wave
+#pragma unroll
+        for (int it = 0; it < kRateChunk; ++it) {
+          const size_t i = first + (size_t)it * kBlock;
+          const unsigned rate = i < n ? (unsigned)rates[i] : 0u;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            const unsigned long long m = __ballot(rate == (2u << k));
+            if ((m >> lane) & 1ull) {   // i < n: a pixel index below 2^32
+              const size_t at = (size_t)base[k] + (unsigned)__popcll(m & below);
+              if (k == 0) list2up[at] = (uint32_t)i;
+              else if (k == 1) list4[at] = (uint32_t)i;
+              else *(list8down - at) = (uint32_t)i;
+            }
+            base[k] += (unsigned)__popcll(m);
+          }
+        }
+      }
+    }
+  }
+  int lx, ly;
+  tile_pixel(lx, ly);
+  int bx, by;
+  xcd_tile<0>(bx, by);
+  const int x = bx * kTileW + lx;
+  const int y = by * kTileH + ly;
+  const bool one = x < W && y < H && rates[(size_t)y * W + x] == 1;
+  if (!__syncthreads_or(one ? 1 : 0)) return;   // uniform: no rate-1 pixel in this tile
+  stage_scene<kStage>(sc, stage);
+  if (!one) return;
+  V3 c;
+  if constexpr (kCuda) {
+    c = cusem::render_pixel(sc, cam, x, y, maxrec - 1);
+  } else {
+    int zero = 0;
+    const V3 d = primary_dir(cam, x, y, zero);
+    PixelOut po;
+    shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
+    c = po.rgb;
+    flush_events(zero, zcount);
+  }
+  store_rgb(out + ((size_t)y * W + x) * 3, c);
+}
+
+// k_rates_refine8: k_aa_refine at s = 8 over a list that grows downwards (entry k is
+// last[-k]): a wave serves one listed pixel per step, lane l shoots subsample (l % 8, l / 8) of
+// it with the camera of the 8*W x 8*H image, the quantised channels are summed over the wave
+// with xor butterflies and lane 0 stores (sum + 32) / 64.  The entry is wave-uniform and stays
+// in a scalar register across shoot.  The list's length is read on the device; the grid is a
+// fixed number of workgroups whose waves stride over the list.
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_rates_refine8(
+    Scene sc, Cam cam, int W, int maxrec, const uint32_t* __restrict__ last,
+    const unsigned* __restrict__ count, uint8_t* __restrict__ out,
+    unsigned long long* __restrict__ zcount) {
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  const unsigned n = *count;
+  if (n == 0u) return;   // uniform over the grid: an empty list costs its launch
+  stage_scene<kStage>(sc, stage);
+  const int lane = threadIdx.x & 63;
+  const unsigned wave =
+      __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
+  const unsigned step = gridDim.x * (kBlock / 64);
+  // 64-bit index: n + step may pass 2^32
+  for (unsigned long long k = wave; k < n; k += step) {
+    const unsigned p = __builtin_amdgcn_readfirstlane(*(last - (size_t)k));
+    const int xs = (int)((p % (unsigned)W) << 3) + (lane & 7);
+    const int ys = (int)((p / (unsigned)W) << 3) + (lane >> 3);
+    V3 c;
+    if constexpr (kCuda) {
+      c = cusem::render_pixel(sc, cam, xs, ys, maxrec - 1);
+    } else {
+      int zero = 0;
+      const V3 d = primary_dir(cam, xs, ys, zero);
+      PixelOut po;
+      shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
+      c = po.rgb;
+      flush_events(zero, zcount);
+    }
+    unsigned rg = (unsigned)quant(c.x) | ((unsigned)quant(c.y) << 16);   // sums <= 64 * 255
+    unsigned b = quant(c.z);
+    for (int m = 1; m < 64; m <<= 1) {
+      rg += __shfl_xor(rg, m, 64);
+      b += __shfl_xor(b, m, 64);
+    }
+    if (lane == 0) {
+      uint8_t* q = out + (size_t)p * 3;
+      q[0] = (uint8_t)(((rg & 0xffffu) + 32u) >> 6);
+      q[1] = (uint8_t)(((rg >> 16) + 32u) >> 6);
+      q[2] = (uint8_t)((b + 32u) >> 6);
     }
   }
 }
@@ -3354,6 +3531,53 @@ hipError_t launch_aa_refine(const LaunchScene& s, int W, int H, int ssaa, int ma
     st ? go(k_aa_refine<true, true>) : go(k_aa_refine<true, false>);
   else
     st ? go(k_aa_refine<false, true>) : go(k_aa_refine<false, false>);
+  return hipGetLastError();
+}
+
+int rates_supported(int W, int H) {
+  if (W <= 0 || H <= 0) return 0;
+  if ((unsigned long long)W * (unsigned long long)H >= (1ull << 32)) return 0;   // uint32 entries
+  if (W > 0x7fffffff / 8 || H > 0x7fffffff / 8) return 0;   // subsample coordinates at rate 8
+  return ((unsigned)H + kTileH - 1) / kTileH <= 65535u;     // grid.y of k_render's tile layout
+}
+
+hipError_t launch_rates_render(const LaunchScene& s, int W, int H, int maxrec,
+                               const uint8_t* rates, uint8_t* out, uint32_t* list4,
+                               uint32_t* list28, unsigned* cnt, unsigned long long* zcount,
+                               hipStream_t stream, bool cuda_sem) {
+  if (!rates_supported(W, H)) return hipErrorInvalidValue;
+  dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, W, H);
+  const bool st = stage_fits(s);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, stream, sc, cam, W, H, maxrec, rates, out,
+                       list28, list4, list28 + ((size_t)W * H - 1), cnt, zcount);
+  };
+  if (cuda_sem)
+    st ? go(k_rates_render<true, true>) : go(k_rates_render<true, false>);
+  else
+    st ? go(k_rates_render<false, true>) : go(k_rates_render<false, false>);
+  return hipGetLastError();
+}
+
+hipError_t launch_rates_refine8(const LaunchScene& s, int W, int H, int maxrec,
+                                const uint32_t* list28, const unsigned* count, uint8_t* out,
+                                unsigned long long* zcount, int blocks, hipStream_t stream,
+                                bool cuda_sem) {
+  if (!rates_supported(W, H) || blocks < 1 || blocks > 4096) return hipErrorInvalidValue;
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, W * 8, H * 8);   // the camera of the 8*W x 8*H image
+  const bool st = stage_fits(s);
+  const uint32_t* last = list28 + ((size_t)W * H - 1);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, sc, cam, W,
+                       maxrec, last, count, out, zcount);
+  };
+  if (cuda_sem)
+    st ? go(k_rates_refine8<true, true>) : go(k_rates_refine8<true, false>);
+  else
+    st ? go(k_rates_refine8<false, true>) : go(k_rates_refine8<false, false>);
   return hipGetLastError();
 }
 

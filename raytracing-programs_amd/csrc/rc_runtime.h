@@ -171,7 +171,8 @@ struct DevCtx {
   hipStream_t stream = nullptr;
   // event sets: [0] start, then per phase ends (fast: [1] = render; parity: [1] phase A,
   // [2] compaction, [3] resolver, [4] phase C; adaptive supersampling: [2] the one-ray image,
-  // [3] the edge list, [1] the refinement).  Set 0 serves plain calls; inside an
+  // [3] the edge list, [1] the refinement; rate maps: [2] the rate-1 pass, [1] the
+  // refinement).  Set 0 serves plain calls; inside an
   // rc_profile_begin/end window every call takes the next set of the pool.
   static constexpr int kEvSets = 64;
   hipEvent_t ev[kEvSets][5] = {};
@@ -187,6 +188,15 @@ struct DevCtx {
   long long aa_pixels = 0;
   hipEvent_t* aa_ev = nullptr;       // the event set of the last timed adaptive frame:
                                      // [0] start, [2] one-ray image, [3] list, [1] refinement
+  // rate-map supersampling (rc_render_rates*): the rate-4 list lives in aa_list; rate_list holds
+  // the rate-2 list (upwards from its start) and the rate-8 list (downwards from its end), W*H
+  // entries; rate_count is the counter block (five words, launch_rates_render), zeroed on the
+  // frame's stream; rate_map is rc_render_rates' device copy of the host map
+  DevBuf rate_list, rate_count, rate_map;
+  hipEvent_t rate_done = nullptr;    // behind the last rate-map frame's refinement
+  bool rate_valid = false;           // a rate-map frame has been enqueued on this device
+  hipEvent_t* rate_ev = nullptr;     // the event set of the last timed rate-map frame:
+                                     // [0] start, [2] the rate-1 pass, [1] the refinement
   uint8_t* stage[2] = {nullptr, nullptr};   // pinned bounce buffers of copy_to_host
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   FrameBufs fb;        // scene, counter and parity workspace of the plain path
