@@ -127,7 +127,10 @@ _Static_assert(sizeof(light_t) == 72, "light_t must match C/objects.h layout");
  *   RAYCAST_SSAA_ADAPTIVE = contrast threshold t, 1..255: supersample only the edge pixels
  *                    (RC_SSAA_ADAPTIVE below; fast mode, RAYCAST_SSAA 2, 4 or 8).  Any other
  *                    value: a warning, then off; set while the factor is 1: a warning, ignored
- *   RAYCAST_STATS  = 1: one JSON metrics line on stderr
+ *   RAYCAST_FILTER = box (default) | tent: the reconstruction filter of RAYCAST_SSAA 2, 4 or 8
+ *                    (rc_filter below).  With RAYCAST_SSAA 1 or RAYCAST_SSAA_ADAPTIVE: a
+ *                    warning, ignored; any other value: a warning, then box
+ *   RAYCAST_STATS = 1: one JSON metrics line on stderr
  * Any HIP failure prints a message to stderr and exit(1)s (reference error convention). */
 void raycast(json_data_t *json_struct, PPMFormat photo_data);
 
@@ -299,6 +302,78 @@ int rc_render_rates(const rc_scene *scene, int width, int height, const rc_optio
 int rc_render_rates_device(const rc_scene *scene, int width, int height, const rc_options *opt,
                            const uint8_t *d_rates, uint8_t *d_out, void *stream,
                            rc_timing *timing);
+
+/* Separable reconstruction filters for supersampling (rc_render_filtered,
+ * rc_render_filtered_device, rc_filter_image_device; every mode).  Plain ssaa ends in the box
+ * filter over a pixel's own s x s subsamples; a wider filter lets a subsample contribute to the
+ * neighbouring pixels as well, at no extra ray.  Fix the scene, mode, depth, W, H and s in
+ * {2, 4, 8}, and let B be the s*W x s*H image of that mode with ssaa = 1 (the B of the ssaa
+ * contract above: in parity mode the carry and the phantom included).  A filter is a 1-D integer
+ * tap vector k[0..L):
+ *     L = s + 2h with a halo 0 <= h <= s   (so s <= L <= 3s <= 24, and L - s is even)
+ *     int16 taps, negative ones allowed;  S = sum k > 0;  sum |k| <= 2048
+ * applied along x and along y, with B's coordinates clamped to the image (edge replicate):
+ *     acc[y][x][c] = sum over j < L, i < L of
+ *                    k[j] * k[i] * B[clamp(s*y - h + j, 0, s*H - 1)][clamp(s*x - h + i, 0, s*W - 1)][c]
+ *     out[y][x][c] = clamp(floor((acc + S*S/2) / (S*S)), 0, 255)     (integers; S*S/2 rounds down)
+ * so a filtered image is still an exact integer function of the reference's own s*W x s*H image.
+ * The bound on sum |k| keeps it in int32: a horizontal sum is at most 2048 * 255 < 2^19 in
+ * magnitude, acc + S*S/2 at most 2048^2 * 255 + 2^21 < 2^31, so the separable evaluation (rows,
+ * then columns) is exact.  A negative acc + S*S/2 clamps to 0 whatever the division's rounding.
+ * Built-in vectors: box, h = 0, k = [1]*s (the output equals rc_options.ssaa = s byte for byte);
+ * tent, h = s/2, k = [1, 3, .., 2s-1, 2s-1, .., 3, 1], S = 2*s*s (the tent of radius one output
+ * pixel sampled at the subsample centres, times 2).  Anything else is the caller's.
+ * On the device: B is rendered into a buffer of the device context in every mode (two passes;
+ * fast mode's fused kernel has no counterpart here), then one kernel stages each output tile's
+ * subsamples and halo in LDS once, filters the rows into int32 partial sums and then the
+ * columns.  rc_timing.zero_normalize and dep_pixels are those of B.
+ * rc_options: ssaa = s, a plain factor of 2, 4 or 8; mode and max_recursion as everywhere.
+ * Whole images only (the halo needs the neighbouring rows).
+ * Refused, each with a message and -1, from the arguments alone (before any device work): a
+ * filter that fails rc_filter_check; a factor other than 2, 4 or 8; an adaptive threshold in
+ * opt->ssaa; num_gpus > 1; null pointers; W or H above 2^28 / s; rc_filter_image_device with
+ * overlapping source and destination (d_src == d_dst included).
+ * rc_render, rc_render_device, rc_frame_submit, rc_render_sharded, adaptive supersampling and
+ * rate maps take no filter and stay as they are: a refined pixel's filter footprint would
+ * reach its unrefined neighbours' subsamples, which those paths never shoot.  raycast() takes
+ * the tent through RAYCAST_FILTER:
+ *   RAYCAST_FILTER = box (default) | tent: the reconstruction filter of RAYCAST_SSAA 2, 4 or 8.
+ *                    With RAYCAST_SSAA 1 or with RAYCAST_SSAA_ADAPTIVE: a warning, ignored.  Any
+ *                    other value: a warning, then box. */
+#define RC_FILTER_MAX_TAPS 24
+typedef struct rc_filter {
+  int32_t ntaps;                       /* L                             */
+  int16_t taps[RC_FILTER_MAX_TAPS];    /* k[0..L); the rest is ignored   */
+} rc_filter;
+_Static_assert(sizeof(rc_filter) == 52, "rc_filter layout (ctypes binding)");
+/* The built-in tap vectors for s = 2, 4 or 8 (-1 for any other s, or a null out). */
+int rc_filter_box(int s, rc_filter *out);
+int rc_filter_tent(int s, rc_filter *out);
+/* 0 when *f is a valid filter at factor s, else -1 with a message naming the rule broken. */
+int rc_filter_check(const rc_filter *f, int s);
+/* raycast()'s reading of RAYCAST_FILTER against the options rc_default_options(.., 1) gave: 1
+ * and the tent of the options' factor in *out when the frame goes through rc_render_filtered, 0
+ * when it goes through rc_render (unset, box, or ignored with one of the warnings above). */
+int rc_filter_env(const rc_options *opt, rc_filter *out);
+/* rc_render_filtered: host pixmap (W*H*3 bytes), synchronous, on opt->device.
+ * rc_render_filtered_device: device image on the current device and the given HIP stream (NULL:
+ * the library's stream of that device, as rc_render_device); asynchronous unless timing is
+ * requested.  Both return 0 on success. */
+int rc_render_filtered(const rc_scene *scene, int width, int height, const rc_options *opt,
+                       const rc_filter *filter, uint8_t *pixmap, rc_timing *timing);
+int rc_render_filtered_device(const rc_scene *scene, int width, int height,
+                              const rc_options *opt, const rc_filter *filter, uint8_t *d_out,
+                              void *stream, rc_timing *timing);
+/* The filter pass alone, on any device image whatever rendered it: d_dst (W x H x 3 bytes) <-
+ * d_src (s*W x s*H x 3 bytes), both compact RGB in device memory, on the given stream (NULL as
+ * above); asynchronous.  A caller that keeps B can filter it again with other taps. */
+int rc_filter_image_device(const uint8_t *d_src, int width, int height, int s,
+                           const rc_filter *filter, uint8_t *d_dst, void *stream);
+/* The kernel spans (ms, HIP events) of the last timed two-pass supersampled frame on the current
+ * device — a filtered frame, or a plain ssaa frame of the two-pass path (parity and cuda mode,
+ * fast mode with rc_tuning.ssaa_fused = 0), whose second pass is the box filter: ms[0] B's
+ * render, ms[1] the filter.  Returns -1 if there was none. */
+int rc_filter_phase_ms(double ms[2]);
 
 /* Frames in flight (an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out

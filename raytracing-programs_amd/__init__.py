@@ -85,6 +85,19 @@ class RcRateStats(ctypes.Structure):
                 ("rays", ctypes.c_int64)]
 
 
+FILTER_MAX_TAPS = 24
+
+
+class RcFilter(ctypes.Structure):
+    """rc_filter (52 bytes): the tap count L and the int16 taps k[0..L)."""
+    _fields_ = [("ntaps", ctypes.c_int32), ("taps", ctypes.c_int16 * FILTER_MAX_TAPS)]
+
+
+# the output tile (width, height) one workgroup of the filter kernel owns, per factor
+# (csrc/rc_kernels.h filter_tile_w / filter_tile_h)
+FILTER_TILES = {2: (32, 16), 4: (32, 8), 8: (16, 8)}
+
+
 # the values a rate map's bytes may take (rc_render_rates): 0 leaves the pixel alone
 RATE_VALUES = (0, 1, 2, 4, 8)
 
@@ -153,7 +166,9 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_debug_inject_error", "rc_group_debug_bound", "rc_resolver_stats_get",
                "rc_group_rank_stats", "rc_debug_scatter_selftest", "rc_adaptive_stats_get",
                "rc_adaptive_phase_ms", "rc_render_rates", "rc_render_rates_device",
-               "rc_rate_stats_get", "rc_rate_phase_ms"]
+               "rc_rate_stats_get", "rc_rate_phase_ms", "rc_filter_box", "rc_filter_tent",
+               "rc_filter_check", "rc_filter_env", "rc_render_filtered",
+               "rc_render_filtered_device", "rc_filter_image_device", "rc_filter_phase_ms"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -278,6 +293,21 @@ def _hip_lib_locked():
                                            ctypes.POINTER(RcTiming)]
     lib.rc_rate_stats_get.argtypes = [ctypes.POINTER(RcRateStats)]
     lib.rc_rate_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    lib.rc_filter_box.argtypes = [ctypes.c_int, ctypes.POINTER(RcFilter)]
+    lib.rc_filter_tent.argtypes = [ctypes.c_int, ctypes.POINTER(RcFilter)]
+    lib.rc_filter_check.argtypes = [ctypes.POINTER(RcFilter), ctypes.c_int]
+    lib.rc_filter_env.argtypes = [ctypes.POINTER(RcOptions), ctypes.POINTER(RcFilter)]
+    lib.rc_render_filtered.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(RcOptions), ctypes.POINTER(RcFilter),
+                                       ctypes.c_void_p, ctypes.POINTER(RcTiming)]
+    lib.rc_render_filtered_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(RcOptions), ctypes.POINTER(RcFilter),
+                                              ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.POINTER(RcTiming)]
+    lib.rc_filter_image_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.POINTER(RcFilter),
+                                           ctypes.c_void_p, ctypes.c_void_p]
+    lib.rc_filter_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
     _hip = lib
     return lib
 
@@ -652,6 +682,153 @@ def rate_phase_ms():
     if hip_lib().rc_rate_phase_ms(ms) != 0:
         raise RuntimeError("rc_rate_phase_ms: no rate-map frame on this device")
     return {"render": ms[0], "refine": ms[1]}
+
+
+def filter_box(s):
+    """The box filter's taps at factor s (2, 4 or 8): [1]*s, the plain ssaa = s image."""
+    s = int(s)
+    if s not in (2, 4, 8):
+        raise ValueError(f"filter_box: s = {s} is not 2, 4 or 8")
+    return [1] * s
+
+
+def filter_tent(s):
+    """The tent's taps at factor s (2, 4 or 8): [1, 3, .., 2s-1, 2s-1, .., 3, 1], halo s/2, sum
+    2*s*s: the tent of radius one output pixel at the subsample centres, times 2."""
+    s = int(s)
+    if s not in (2, 4, 8):
+        raise ValueError(f"filter_tent: s = {s} is not 2, 4 or 8")
+    up = list(range(1, 2 * s, 2))
+    return up + up[::-1]
+
+
+def filter_check(taps, s):
+    """The rules of a tap vector at factor s (include/raycast_hip.h, rc_filter), stated here so
+    that they hold without the library; returns the halo h, raises ValueError naming the rule."""
+    s = int(s)
+    if s not in (2, 4, 8):
+        raise ValueError(f"filter: s = {s} is not 2, 4 or 8")
+    taps = [int(k) for k in taps]
+    n = len(taps)
+    if n > FILTER_MAX_TAPS:
+        raise ValueError(f"filter: {n} taps, at most {FILTER_MAX_TAPS}")
+    if n < s or (n - s) % 2:
+        raise ValueError(f"filter: {n} taps at s = {s}: the count is s + 2h with a halo h >= 0")
+    h = (n - s) // 2
+    if h > s:
+        raise ValueError(f"filter: {n} taps at s = {s}: halo {h} > s (at most {3 * s} taps)")
+    if any(k < -32768 or k > 32767 for k in taps):
+        raise ValueError("filter: the taps are int16")
+    if sum(taps) <= 0:
+        raise ValueError(f"filter: the taps sum to {sum(taps)}, the sum must be positive")
+    if sum(abs(k) for k in taps) > 2048:
+        raise ValueError(f"filter: the taps' absolute values sum to "
+                         f"{sum(abs(k) for k in taps)}, at most 2048 (the int32 bound)")
+    return h
+
+
+def filter_accumulate(img, s, taps):
+    """The filter contract's accumulators acc[y][x][c] (before rounding and clamping): int64
+    [H, W, C] of a uint8 [s*H, s*W, C] image."""
+    img = np.asarray(img)
+    s = int(s)
+    h = filter_check(taps, s)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[0] % s or img.shape[1] % s \
+            or img.shape[0] == 0 or img.shape[1] == 0:
+        raise ValueError(f"filter_downsample: a uint8 [s*H, s*W, C] image, got {img.dtype} "
+                         f"{img.shape} and s = {s}")
+    oh, ow = img.shape[0] // s, img.shape[1] // s
+    k = np.asarray(taps, dtype=np.int64)
+    b = np.pad(img.astype(np.int64), ((h, h), (h, h), (0, 0)), mode="edge")
+    rows = sum(k[i] * b[:, i:i + s * ow:s] for i in range(len(k)))       # [s*H + 2h, W, C]
+    return sum(k[j] * rows[j:j + s * oh:s] for j in range(len(k)))       # [H, W, C]
+
+
+def filter_downsample(img, s, taps):
+    """The filter contract (include/raycast_hip.h, rc_filter) in numpy: the [H, W, C] uint8 image
+    of an [s*H, s*W, C] uint8 image through the integer taps k, applied along x and along y over
+    the edge-replicated image: clamp((acc + S*S/2) // (S*S), 0, 255) with S = sum k."""
+    acc = filter_accumulate(img, s, taps)
+    s2 = int(sum(int(k) for k in taps)) ** 2
+    return np.clip((acc + s2 // 2) // s2, 0, 255).astype(np.uint8)
+
+
+def _rc_filter(taps, s):
+    filter_check(taps, s)
+    f = RcFilter()
+    f.ntaps = len(taps)
+    for i, k in enumerate(taps):
+        f.taps[i] = int(k)
+    return f
+
+
+def render_filtered(scene, width, height, taps, ssaa, depth=6, mode="parity", device=0,
+                    timing=None, out=None):
+    """rc_render_filtered: the ssaa*W x ssaa*H image of the mode through the tap vector `taps`
+    (filter_downsample), into a host array [H, W, 3] uint8.  ssaa is 2, 4 or 8."""
+    lib = hip_lib()
+    f = _rc_filter(taps, ssaa)
+    if out is None:
+        out = np.empty((height, width, 3), dtype=np.uint8)
+    assert out.shape == (height, width, 3) and out.dtype == np.uint8 and out.flags.c_contiguous
+    t = RcTiming()
+    opt = options(depth, mode, 1, device, ssaa)
+    rc = lib.rc_render_filtered(scene.packed(), width, height, ctypes.byref(opt), ctypes.byref(f),
+                                out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
+    if rc != 0:
+        raise RuntimeError("rc_render_filtered failed (see stderr)")
+    if timing is not None:
+        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    return out
+
+
+def render_filtered_device(scene, width, height, taps, ssaa, d_out_ptr, stream_ptr=None, depth=6,
+                           mode="parity", timing=None):
+    """rc_render_filtered_device: the image (W*H*3 bytes) is device memory; enqueued on the
+    stream and asynchronous unless `timing` is given."""
+    lib = hip_lib()
+    f = _rc_filter(taps, ssaa)
+    opt = options(depth, mode, ssaa=ssaa)
+    t = RcTiming()
+    rc = lib.rc_render_filtered_device(scene.packed(), width, height, ctypes.byref(opt),
+                                       ctypes.byref(f), ctypes.c_void_p(d_out_ptr),
+                                       ctypes.c_void_p(stream_ptr or 0),
+                                       ctypes.byref(t) if timing is not None else None)
+    if rc != 0:
+        raise RuntimeError("rc_render_filtered_device failed (see stderr)")
+    if timing is not None:
+        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+
+
+def filter_image_device(d_src_ptr, width, height, s, taps, d_dst_ptr, stream_ptr=None):
+    """rc_filter_image_device: the filter pass alone, d_dst (W x H x 3 bytes) <- d_src (s*W x s*H
+    x 3 bytes), device memory, on the stream; asynchronous."""
+    f = _rc_filter(taps, s)
+    rc = hip_lib().rc_filter_image_device(ctypes.c_void_p(d_src_ptr), width, height, int(s),
+                                          ctypes.byref(f), ctypes.c_void_p(d_dst_ptr),
+                                          ctypes.c_void_p(stream_ptr or 0))
+    if rc != 0:
+        raise RuntimeError("rc_filter_image_device failed (see stderr)")
+
+
+def filter_phase_ms():
+    """Kernel spans of the last timed two-pass supersampled frame (rc_filter_phase_ms), in ms:
+    {"render": the s*W x s*H image, "filter": the filter pass}."""
+    ms = (ctypes.c_double * 2)()
+    if hip_lib().rc_filter_phase_ms(ms) != 0:
+        raise RuntimeError("rc_filter_phase_ms: no timed two-pass frame on this device")
+    return {"render": ms[0], "filter": ms[1]}
+
+
+def filter_from_env(ssaa=1, adaptive=0):
+    """raycast()'s reading of RAYCAST_FILTER (rc_filter_env) for a frame with the factor `ssaa`
+    and the adaptive threshold `adaptive`: the tent's taps when the frame goes through the
+    filtered path, None when it goes through rc_render (the warnings go to stderr)."""
+    f = RcFilter()
+    opt = options(ssaa=ssaa, adaptive=adaptive)
+    if hip_lib().rc_filter_env(ctypes.byref(opt), ctypes.byref(f)) != 1:
+        return None
+    return [int(f.taps[i]) for i in range(f.ntaps)]
 
 
 SPIN_SITES = ("team_handoff", "phase_c_carry_in", "ready_queue", "helper_queue")

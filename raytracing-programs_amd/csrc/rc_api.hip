@@ -780,6 +780,137 @@ int rc_rate_phase_ms(double ms[2]) {
   return 0;
 }
 
+int rc_filter_phase_ms(double ms[2]) {
+  if (!ms) return -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->filt_ev) return -1;
+  hipEvent_t* ev = c->filt_ev;
+  HIP_TRY(hipEventSynchronize(ev[c->filt_end]));
+  ms[0] = event_ms(ev[0], c->filt_mid);
+  ms[1] = event_ms(c->filt_mid, ev[c->filt_end]);
+  return 0;
+}
+
+// ---------------------------------------------------------- reconstruction filters --
+static bool filter_factor(int s) { return s == 2 || s == 4 || s == 8; }
+
+int rc_filter_box(int s, rc_filter* out) {
+  if (!out || !filter_factor(s)) return -1;
+  std::memset(out, 0, sizeof *out);
+  out->ntaps = s;
+  for (int i = 0; i < s; ++i) out->taps[i] = 1;
+  return 0;
+}
+
+int rc_filter_tent(int s, rc_filter* out) {
+  if (!out || !filter_factor(s)) return -1;
+  std::memset(out, 0, sizeof *out);
+  out->ntaps = 2 * s;
+  for (int i = 0; i < s; ++i) out->taps[i] = out->taps[2 * s - 1 - i] = (int16_t)(2 * i + 1);
+  return 0;
+}
+
+// The rules of include/raycast_hip.h (rc_filter).  The bound on the absolute sum is what keeps
+// the kernel's arithmetic in int32: a horizontal sum is at most 2048 * 255 < 2^19 in magnitude,
+// the full sum at most 2048^2 * 255, and with the rounding term S*S/2 <= 2^21 that stays below
+// 2^31, so the separable evaluation is exact.
+int rc_filter_check(const rc_filter* f, int s) {
+  if (!f) {
+    std::fprintf(stderr, "Error: rc_filter_check: a null filter\n");
+    return -1;
+  }
+  if (!filter_factor(s)) {
+    std::fprintf(stderr, "Error: rc_filter_check: factor %d is not 2, 4 or 8\n", s);
+    return -1;
+  }
+  const int n = f->ntaps;
+  if (n > RC_FILTER_MAX_TAPS) {
+    std::fprintf(stderr, "Error: rc_filter_check: %d taps, at most %d\n", n, RC_FILTER_MAX_TAPS);
+    return -1;
+  }
+  if (n < s || ((n - s) & 1)) {
+    std::fprintf(stderr, "Error: rc_filter_check: %d taps at factor %d: the count is s + 2h with "
+                 "a halo h >= 0, so it is at least s and differs from s by an even number\n", n, s);
+    return -1;
+  }
+  if ((n - s) / 2 > s) {
+    std::fprintf(stderr, "Error: rc_filter_check: %d taps at factor %d: the halo %d is wider than "
+                 "one output pixel (h <= s, at most %d taps)\n", n, s, (n - s) / 2, 3 * s);
+    return -1;
+  }
+  long long sum = 0, mag = 0;
+  for (int i = 0; i < n; ++i) {
+    sum += f->taps[i];
+    mag += f->taps[i] < 0 ? -(long long)f->taps[i] : f->taps[i];
+  }
+  if (sum <= 0) {
+    std::fprintf(stderr, "Error: rc_filter_check: the taps sum to %lld, the sum must be "
+                 "positive\n", sum);
+    return -1;
+  }
+  if (mag > 2048) {
+    std::fprintf(stderr, "Error: rc_filter_check: the taps' absolute values sum to %lld, at most "
+                 "2048 (the int32 bound)\n", mag);
+    return -1;
+  }
+  return 0;
+}
+
+int rc_filter_env(const rc_options* opt, rc_filter* out) {
+  const char* v = std::getenv("RAYCAST_FILTER");
+  if (!v || !opt || !out) return 0;
+  bool tent = false;
+  if (!std::strcmp(v, "tent")) tent = true;
+  else if (std::strcmp(v, "box"))
+    std::fprintf(stderr, "Warning: RAYCAST_FILTER '%s' is not box or tent, using box\n", v);
+  const int s = RC_SSAA_FACTOR(opt->ssaa);
+  if (!filter_factor(s)) {
+    std::fprintf(stderr, "Warning: RAYCAST_FILTER '%s' needs RAYCAST_SSAA 2, 4 or 8, ignored\n", v);
+    return 0;
+  }
+  if (RC_SSAA_THRESHOLD(opt->ssaa) > 0) {
+    std::fprintf(stderr, "Warning: RAYCAST_FILTER '%s' does not combine with "
+                 "RAYCAST_SSAA_ADAPTIVE (a refined pixel's footprint would reach its unrefined "
+                 "neighbours), ignored\n", v);
+    return 0;
+  }
+  return tent && rc_filter_tent(s, out) == 0 ? 1 : 0;
+}
+
+// What the filtered entry points refuse from their arguments alone; the factor, or -1.
+static int filtered_refused(const char* who, const rc_options* opt, int W, int H,
+                            const rc_filter* f) {
+  const int ss = ssaa_factor(opt, who);
+  if (ss < 0) return -1;   // ssaa_decode has said why
+  if (RC_SSAA_THRESHOLD(opt->ssaa) > 0) {
+    std::fprintf(stderr, "Error: %s: an adaptive threshold (ssaa %d): a refined pixel's filter "
+                 "footprint would reach its unrefined neighbours' subsamples; use a plain factor\n",
+                 who, opt->ssaa);
+    return -1;
+  }
+  if (ss < 2) {
+    std::fprintf(stderr, "Error: %s: ssaa %d: a filtered frame needs a factor of 2, 4 or 8\n", who,
+                 opt->ssaa);
+    return -1;
+  }
+  if (opt->num_gpus > 1) {
+    std::fprintf(stderr, "Error: %s: num_gpus %d: the row shards do not supersample\n", who,
+                 opt->num_gpus);
+    return -1;
+  }
+  if (rc_filter_check(f, ss)) return -1;
+  if (W <= 0 || H <= 0 || W > (1 << 28) / ss || H > (1 << 28) / ss) {
+    std::fprintf(stderr, "Error: %s: %d x %d at factor %d: both sides must be 1 .. 2^28 / s\n",
+                 who, W, H, ss);
+    return -1;
+  }
+  return ss;
+}
+
 void rc_default_options(rc_options* opt, int use_env) {
   opt->max_recursion = 7;   // C/raycast.c:14
   opt->mode = RC_MODE_PARITY;
@@ -1090,19 +1221,20 @@ int flush_phase_c(DevCtx& c, bool whole) {
 
 int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int row_step,
                       int nrows, const rc_options* opt, uint8_t* d_out, hipStream_t stream,
-                      bool timed, uint32_t* patch, hipEvent_t** evset);
+                      bool timed, uint32_t* patch, hipEvent_t** evset,
+                      const rc_filter* filt = nullptr);
 
 // Enqueue one render of rows (row0 + k*row_step) into d_out on `stream`, using the device's
 // one-frame workspace c.fb: after the previous render that used it, whatever its stream.
 int enqueue_render(DevCtx& c, const rc_scene* s, int W, int H, int row0, int row_step, int nrows,
                    const rc_options* opt, uint8_t* d_out, hipStream_t stream, bool timed,
-                   uint32_t* patch, hipEvent_t** evset) {
+                   uint32_t* patch, hipEvent_t** evset, const rc_filter* filt) {
   // a frame in flight's held-back phase C goes out first, so that a device synchronisation
   // after this call completes it (rc_frames_wait stays the frames' completion point)
   if (flush_phase_c(c, false)) return -1;
   if (c.ws_valid && c.ws_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, c.ws_ev, 0));
   const int rc = enqueue_render_ws(c, s, W, H, row0, row_step, nrows, opt, d_out, stream, timed,
-                                   patch, evset);
+                                   patch, evset, filt);
   // recorded even after a failed enqueue: whatever was enqueued stays ordered
   HIP_TRY(hipEventRecord(c.ws_ev, stream));
   c.ws_stream = stream;
@@ -1148,16 +1280,26 @@ static int adaptive_refused(const rc_options* opt, const char* who, int ss, int 
 // Supersampling, two passes (parity and cuda modes; fast mode with rc_tuning.ssaa_fused = 0):
 // the s*W x s*H image of the same mode through the one-frame path below, unchanged, into the
 // context's buffer, then its box filter into d_out.  The frame's events, counts and hand-off
-// log are those of the large image; its last event is moved behind the box filter.
+// log are those of the large image; its last event is moved behind the box filter.  With filt
+// (whole images: the halo needs the neighbouring rows) the separable filter of rc_filter.hip
+// takes the box filter's place.  A timed frame also records filt_mid between the two passes
+// (rc_filter_phase_ms).
 int enqueue_render_two_pass(DevCtx& c, const rc_scene* s, int W, int H, int ss, int row0,
                             int row_step, int nrows, const rc_options* opt, uint8_t* d_out,
-                            hipStream_t stream, bool timed, hipEvent_t** evset) {
+                            hipStream_t stream, bool timed, hipEvent_t** evset,
+                            const rc_filter* filt) {
   if (row_step != 1) {
     std::fprintf(stderr, "Error: ssaa %d in this mode renders contiguous rows only (row_step "
                  "%d)\n", ss, row_step);
     return -1;
   }
   if (W > (1 << 28) / ss || H > (1 << 28) / ss) return -1;
+  if (filt && (row0 != 0 || nrows != H)) {
+    std::fprintf(stderr, "Error: a filtered frame renders whole images only (row0 %d, nrows %d of "
+                 "%d): the filter's halo needs the neighbouring rows\n", row0, nrows, H);
+    return -1;
+  }
+  if (timed && !c.filt_mid) HIP_TRY(hipEventCreate(&c.filt_mid));
   const int sw = W * ss, sh = H * ss;
   if (c.ssaa.ensure((size_t)sw * 3 * (size_t)nrows * ss)) {
     std::fprintf(stderr, "Error: out of device memory for the supersampled image (%dx%d)\n", sw,
@@ -1171,15 +1313,24 @@ int enqueue_render_two_pass(DevCtx& c, const rc_scene* s, int W, int H, int ss, 
                         timed, nullptr, &ev))
     return -1;
   if (evset) *evset = ev;
-  HIP_TRY(rc::launch_box_down((const uint8_t*)c.ssaa.p, W, nrows, ss, d_out, stream));
+  if (timed) HIP_TRY(hipEventRecord(c.filt_mid, stream));
+  if (filt)
+    HIP_TRY(rc::launch_filter_down((const uint8_t*)c.ssaa.p, W, H, ss, filt->taps, filt->ntaps,
+                                   d_out, stream));
+  else
+    HIP_TRY(rc::launch_box_down((const uint8_t*)c.ssaa.p, W, nrows, ss, d_out, stream));
   const bool parity = opt->mode == RC_MODE_PARITY && opt->max_recursion > 1;
-  if (timed) HIP_TRY(hipEventRecord(ev[parity ? 4 : 1], stream));
+  if (timed) {
+    HIP_TRY(hipEventRecord(ev[parity ? 4 : 1], stream));
+    c.filt_ev = ev;
+    c.filt_end = parity ? 4 : 1;
+  }
   return 0;
 }
 
 int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int row_step,
                       int nrows, const rc_options* opt, uint8_t* d_out, hipStream_t stream,
-                      bool timed, uint32_t* patch, hipEvent_t** evset) {
+                      bool timed, uint32_t* patch, hipEvent_t** evset, const rc_filter* filt) {
   const int ss = ssaa_factor(opt, "render");
   if (ss < 0) return -1;
   // adaptive (at > 0): the one-ray image through the plain kernel, then the edge list and the
@@ -1205,10 +1356,11 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
     }
     if (!c.aa_done) HIP_TRY(hipEventCreateWithFlags(&c.aa_done, hipEventDisableTiming));
   }
-  const bool fused = ss > 1 && at == 0 && opt->mode == RC_MODE_FAST && tune().ssaa_fused;
+  if (filt && (ss < 2 || at > 0)) return -1;   // the entry points have refused these
+  const bool fused = ss > 1 && at == 0 && opt->mode == RC_MODE_FAST && tune().ssaa_fused && !filt;
   if (ss > 1 && at == 0 && !fused)
     return enqueue_render_two_pass(c, s, W, H, ss, row0, row_step, nrows, opt, d_out, stream,
-                                   timed, evset);
+                                   timed, evset, filt);
   rc::LaunchScene ls;
   if (upload_scene(c.fb, stream, s, ls)) return -1;
   unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
@@ -1226,6 +1378,7 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
   if (evset) *evset = ev;
   if (timed && c.aa_ev == ev) c.aa_ev = nullptr;   // the set is recorded anew (rc_adaptive_phase_ms)
   if (timed && c.rate_ev == ev) c.rate_ev = nullptr;   // likewise (rc_rate_phase_ms)
+  if (timed && c.filt_ev == ev) c.filt_ev = nullptr;   // likewise (rc_filter_phase_ms)
   if (timed) HIP_TRY(hipEventRecord(ev[0], stream));
   if (!parity) {
     if (fused)   // the subsamples on adjacent lanes, box-filtered in registers
@@ -1337,6 +1490,7 @@ static int enqueue_rates(DevCtx& c, const rc_scene* s, int W, int H, const rc_op
       c.prof_parity = false;
     }
     if (c.aa_ev == ev) c.aa_ev = nullptr;   // the set is recorded anew (rc_adaptive_phase_ms)
+    if (c.filt_ev == ev) c.filt_ev = nullptr;   // likewise (rc_filter_phase_ms)
     c.rate_ev = nullptr;
     // The lists follow the map's row-major order, so over a uniform region entry k is pixel
     // k + const and a wave's static stride (workgroups * 4 waves * pixels per step) that is a
@@ -1755,6 +1909,133 @@ int rc_render_rates(const rc_scene* s, int W, int H, const rc_options* opt, cons
     timing->total_ms =
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
+  return 0;
+}
+
+int rc_render_filtered_device(const rc_scene* s, int W, int H, const rc_options* opt,
+                              const rc_filter* f, uint8_t* d_out, void* stream,
+                              rc_timing* timing) {
+  if (!s || !opt || !f || !d_out) {
+    std::fprintf(stderr, "Error: rc_render_filtered_device: a null pointer\n");
+    return -1;
+  }
+  if (filtered_refused("rc_render_filtered_device", opt, W, H, f) < 0) return -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (c->lone_log.earlier_failed()) {   // as rc_render_device
+    c->lone_log.take(nullptr, nullptr);
+    return -1;
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const long long own = c->lone_log.head;
+  hipStream_t saved = c->stream;   // the scene upload and events follow the caller's stream
+  c->stream = st;
+  const int rc = enqueue_render(*c, s, W, H, 0, 1, H, opt, d_out, st, true, nullptr, nullptr, f);
+  c->stream = saved;
+  if (rc) return -1;
+  if (timing) {
+    std::memset(timing, 0, sizeof *timing);
+    HIP_TRY(hipStreamSynchronize(st));
+    const long long before = c->lone_log.checked;
+    const bool failed = c->lone_log.entry_failed(own);
+    c->lone_log.poll();
+    if (failed) {
+      c->lone_log.take(nullptr, nullptr);
+      return -1;
+    }
+    if (check_spin_error(c->fb, opt)) return -1;
+    timing->frames_checked = c->lone_log.checked - before;
+    fill_device_timing(*c, opt, timing);
+    timing->total_ms = timing->kernel_ms;
+  }
+  return 0;
+}
+
+int rc_render_filtered(const rc_scene* s, int W, int H, const rc_options* opt, const rc_filter* f,
+                       uint8_t* pixmap, rc_timing* timing) {
+  if (!s || !opt || !f || !pixmap) {
+    std::fprintf(stderr, "Error: rc_render_filtered: a null pointer\n");
+    return -1;
+  }
+  auto t0 = std::chrono::steady_clock::now();
+  if (filtered_refused("rc_render_filtered", opt, W, H, f) < 0) return -1;
+  if (timing) std::memset(timing, 0, sizeof *timing);
+  const rc_tuning tu = tune();
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (opt->device < 0 || opt->device >= ndev) {
+    std::fprintf(stderr, "Error: device %d not available (%d devices)\n", opt->device, ndev);
+    return -1;
+  }
+  DevCtx* c;
+  if (hipSetDevice(opt->device) != hipSuccess || ctx_get(opt->device, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (c->lone_log.earlier_failed()) {   // as rc_render
+    c->lone_log.take(nullptr, nullptr);
+    return -1;
+  }
+  const size_t bytes = (size_t)W * H * 3;
+  if (c->out.ensure(bytes)) return -1;
+  uint8_t* d_out = (uint8_t*)c->out.p;
+  const bool parity = opt->mode == RC_MODE_PARITY && opt->max_recursion > 1;
+  const long long own = c->lone_log.head;
+  if (enqueue_render(*c, s, W, H, 0, 1, H, opt, d_out, c->stream, true, nullptr, nullptr, f))
+    return -1;
+  // the frame's counts (those of the s*W x s*H image), behind its last kernel
+  if (!c->pin_tail) HIP_TRY(hipHostMalloc((void**)&c->pin_tail, 64, hipHostMallocDefault));
+  HIP_TRY(hipMemcpyAsync(c->pin_tail, c->fb.zcount.p, 8, hipMemcpyDeviceToHost, c->stream));
+  if (parity)
+    HIP_TRY(hipMemcpyAsync(c->pin_tail + 16, c->fb.counters.p, 16, hipMemcpyDeviceToHost,
+                           c->stream));
+  prefault(*c, pixmap, bytes, tu);
+  auto td = std::chrono::steady_clock::now();
+  if (copy_to_host(*c, pixmap, d_out, bytes, c->stream, tu)) return -1;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->lone_log.entry_failed(own)) {
+    c->lone_log.poll();
+    (void)check_spin_error(c->fb, opt);
+    c->lone_log.take(nullptr, nullptr);
+    return -1;
+  }
+  c->lone_log.poll();
+  fill_device_timing(*c, opt, timing, c->pin_tail);
+  if (timing) {
+    timing->d2h_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
+    timing->total_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return 0;
+}
+
+int rc_filter_image_device(const uint8_t* d_src, int W, int H, int s, const rc_filter* f,
+                           uint8_t* d_dst, void* stream) {
+  if (!d_src || !d_dst || !f) {
+    std::fprintf(stderr, "Error: rc_filter_image_device: a null pointer\n");
+    return -1;
+  }
+  if (rc_filter_check(f, s)) return -1;
+  if (W <= 0 || H <= 0 || W > (1 << 28) / s || H > (1 << 28) / s) {
+    std::fprintf(stderr, "Error: rc_filter_image_device: %d x %d at factor %d: both sides must "
+                 "be 1 .. 2^28 / s\n", W, H, s);
+    return -1;
+  }
+  const uintptr_t a = (uintptr_t)d_src, b = (uintptr_t)d_dst;
+  const size_t nb = (size_t)W * H * 3, na = nb * (size_t)s * s;
+  if (a < b + nb && b < a + na) {
+    std::fprintf(stderr, "Error: rc_filter_image_device: the source and the destination "
+                 "overlap: every output pixel reads its neighbours' subsamples\n");
+    return -1;
+  }
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  HIP_TRY(rc::launch_filter_down(d_src, W, H, s, f->taps, f->ntaps, d_dst,
+                                 stream ? (hipStream_t)stream : c->stream));
   return 0;
 }
 
@@ -2467,7 +2748,11 @@ void raycast(json_data_t* json_struct, PPMFormat photo_data) {
     return;
   }
   rc_timing t;
-  if (rc_render(s, photo_data.width, photo_data.height, &opt, photo_data.pixmap, &t)) {
+  rc_filter filt;
+  const bool filtered = rc_filter_env(&opt, &filt) == 1;   // RAYCAST_FILTER
+  if (filtered ? rc_render_filtered(s, photo_data.width, photo_data.height, &opt, &filt,
+                                    photo_data.pixmap, &t)
+               : rc_render(s, photo_data.width, photo_data.height, &opt, photo_data.pixmap, &t)) {
     std::fprintf(stderr, "Error: GPU render failed\n");
     std::exit(1);
   }

@@ -100,6 +100,16 @@ hipError_t launch_render_ssaa(const LaunchScene& s, int W, int H, int ssaa, int 
 // The two-pass path's box filter: dst (W x H) <- src (ssaa*W x ssaa*H), both compact RGB.
 hipError_t launch_box_down(const uint8_t* src, int W, int H, int ssaa, uint8_t* dst,
                            hipStream_t stream);
+// The separable reconstruction filter (rc_filter.hip; rc_filter in include/raycast_hip.h):
+// dst (W x H) <- src (ssaa*W x ssaa*H) through the ntaps = ssaa + 2h integer taps, applied along
+// x and along y with src's coordinates clamped to the image.  hipErrorInvalidValue for anything
+// rc_filter_check or the size limits (W, H <= 2^28 / ssaa) refuse.  src and dst must not overlap.
+constexpr int kFilterMaxTaps = 24;
+// the output tile one workgroup owns, per factor
+constexpr int filter_tile_w(int ssaa) { return ssaa == 8 ? 16 : 32; }
+constexpr int filter_tile_h(int ssaa) { return ssaa == 2 ? 16 : 8; }
+hipError_t launch_filter_down(const uint8_t* src, int W, int H, int ssaa, const int16_t* taps,
+                              int ntaps, uint8_t* dst, hipStream_t stream);
 
 // Adaptive supersampling (rc_options.ssaa = RC_SSAA_ADAPTIVE(s, t); fast and cuda modes), after
 // launch_render has put the one-ray W x H image into `img`, all on one stream:

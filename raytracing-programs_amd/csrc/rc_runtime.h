@@ -197,6 +197,12 @@ struct DevCtx {
   bool rate_valid = false;           // a rate-map frame has been enqueued on this device
   hipEvent_t* rate_ev = nullptr;     // the event set of the last timed rate-map frame:
                                      // [0] start, [2] the rate-1 pass, [1] the refinement
+  // two-pass supersampling's own spans (rc_filter_phase_ms): filt_mid is recorded between the
+  // s*W x s*H image and its filter; filt_ev is the event set of the last timed two-pass frame
+  // ([0] start, [filt_end] behind the filter), null when that set has been recorded anew
+  hipEvent_t filt_mid = nullptr;
+  hipEvent_t* filt_ev = nullptr;
+  int filt_end = 1;
   uint8_t* stage[2] = {nullptr, nullptr};   // pinned bounce buffers of copy_to_host
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   FrameBufs fb;        // scene, counter and parity workspace of the plain path
@@ -261,7 +267,10 @@ double event_ms(hipEvent_t a, hipEvent_t b);
 // workspace (rc_render_device's path; the caller holds c.mu).  timed: phase events c.ev[0].
 int enqueue_render(DevCtx& c, const rc_scene* s, int W, int H, int row0, int row_step, int nrows,
                    const rc_options* opt, uint8_t* d_out, hipStream_t stream, bool timed,
-                   uint32_t* patch = nullptr, hipEvent_t** evset = nullptr);
+                   uint32_t* patch = nullptr, hipEvent_t** evset = nullptr,
+                   const rc_filter* filt = nullptr);
+// filt (with a plain factor of 2, 4 or 8 in opt->ssaa, every mode): the s*W x s*H image through
+// the two-pass path and filt's taps instead of the box (the caller has passed rc_filter_check)
 // rc_options.ssaa as a factor: 1 (0 and 1 are both off), 2, 4 or 8; -1 and a message naming
 // `who` for any other value
 int ssaa_factor(const rc_options* opt, const char* who);
