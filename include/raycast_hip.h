@@ -130,6 +130,11 @@ _Static_assert(sizeof(light_t) == 72, "light_t must match C/objects.h layout");
  *   RAYCAST_FILTER = box (default) | tent: the reconstruction filter of RAYCAST_SSAA 2, 4 or 8
  *                    (rc_filter below).  With RAYCAST_SSAA 1 or RAYCAST_SSAA_ADAPTIVE: a
  *                    warning, ignored; any other value: a warning, then box
+ *   RAYCAST_PATTERN = name | name:t: a sparse sample pattern (rc_pattern below; diag2, rgss4,
+ *                    checker8 or queens8) for every pixel, or with a contrast threshold t in
+ *                    1..255 for the edge pixels only; fast and cuda mode, RAYCAST_SSAA unset or
+ *                    1.  An unknown name, a bad t, parity mode or RAYCAST_SSAA 2, 4 or 8 set as
+ *                    well: a warning, ignored
  *   RAYCAST_STATS = 1: one JSON metrics line on stderr
  * Any HIP failure prints a message to stderr and exit(1)s (reference error convention). */
 void raycast(json_data_t *json_struct, PPMFormat photo_data);
@@ -374,6 +379,84 @@ int rc_filter_image_device(const uint8_t *d_src, int width, int height, int s,
  * fast mode with rc_tuning.ssaa_fused = 0), whose second pass is the box filter: ms[0] B's
  * render, ms[1] the filter.  Returns -1 if there was none. */
 int rc_filter_phase_ms(double ms[2]);
+
+/* Sparse sample patterns for supersampling (rc_render_pattern, rc_render_pattern_device; fast and
+ * cuda mode).  Plain ssaa, adaptive refinement and the rate map shoot the full s x s ordered grid
+ * of every pixel they refine.  A rotated-grid or N-rooks pattern takes n samples of a g x g
+ * subsample lattice with no two in one row or column: on a near-horizontal or near-vertical edge
+ * it resolves g coverage levels with n rays where the ordered grid needs g*g.
+ * Fix the scene, mode, depth, W and H.  A pattern is (g, n, px[0..n), py[0..n)) with
+ *     g in {2, 4, 8};  n in {2, 4, 8, 16} and n <= g*g;  every px[k] < g and py[k] < g;
+ *     the n pairs (px[k], py[k]) pairwise distinct
+ * (x to the right and y downwards, as image coordinates).  Let B_g be that mode's g*W x g*H image
+ * with ssaa = 1 (the B of the ssaa contract above, at s = g).  Then
+ *     P[y][x][c] = (sum over k < n of B_g[g*y + py[k]][g*x + px[k]][c]  +  n/2) / n    (integers)
+ * so a pattern image is still an exact integer function of the reference's own g*W x g*H image.
+ * A threshold t in 0..255 selects the pixels: t = 0: out = P.  t > 0: out = P where
+ * contrast(x, y) >= t, else A, with A the one-ray image and contrast exactly the adaptive
+ * contract's above (rc_adaptive_stats).  The full patterns (every lattice point once: g = 2 with
+ * n = 4, g = 4 with n = 16) give the bytes of rc_options.ssaa = g.
+ * Built-in patterns (rc_pattern_builtin), as (x, y) pairs:
+ *     diag2     g 2   (0,0) (1,1)
+ *     rgss4     g 4   (1,0) (3,1) (0,2) (2,3)                      rotated-grid supersampling
+ *     checker8  g 4   the eight (i, j) with i + j even, row by row
+ *     queens8   g 8   row r has column [3,6,2,7,1,4,0,5][r]       no shared row, column, diagonal
+ * On the device: n lanes a pixel, a lane's lattice position out of two 64-bit words of 4-bit
+ * entries held in scalar registers, the quantised channels summed over the n lanes in registers;
+ * B_g is never stored.  t = 0 is one kernel over tiles of 256 / n output pixels.  t > 0 is three
+ * launches on one stream with no host wait: A by the plain kernel, the adaptive path's edge list,
+ * then the pattern kernel striding over the list (its grid follows rc_tuning.adaptive_blocks).
+ * rc_options: mode fast or cuda; ssaa 0 or 1 (the pattern carries the grid, as the rate map
+ * does); max_recursion as everywhere.  rc_timing.zero_normalize counts the rays actually shot.
+ * Whole images only.
+ * Refused, each with a message and -1, from the arguments alone (before any device work): parity
+ * mode (every pixel of its g*W x g*H image depends on the scan-order carry of the whole image, so
+ * it cannot be shot sparsely; plain ssaa remains); a pattern that fails rc_pattern_check; a factor
+ * above 1 or a threshold in opt->ssaa; a threshold outside 0..255; num_gpus > 1; null pointers;
+ * W or H above 2^28 / g (or below 1); with t > 0, W * H >= 2^32; an image of more than 65535
+ * rows of tiles (t = 0: tiles of 8, 8, 4, 4 rows at n = 2, 4, 8, 16; t > 0: of 16 rows).
+ * rc_render, rc_render_device, rc_frame_submit, rc_render_sharded, the rate-map and the filtered
+ * entry points take no pattern and stay as they are.  raycast() takes a built-in one through
+ *   RAYCAST_PATTERN = name | name:t   (name: diag2, rgss4, checker8, queens8; t: 0..255, default 0)
+ *                    in fast and cuda mode with RAYCAST_SSAA unset or 1.  An unknown name, a bad
+ *                    t, parity mode, or RAYCAST_SSAA 2, 4 or 8 set as well: a warning, ignored. */
+#define RC_PATTERN_MAX_SAMPLES 16
+typedef struct rc_pattern {
+  int32_t grid, nsamples;                 /* g and n                                  */
+  uint8_t x[RC_PATTERN_MAX_SAMPLES];      /* px[0..n); the rest is ignored            */
+  uint8_t y[RC_PATTERN_MAX_SAMPLES];      /* py[0..n)                                 */
+} rc_pattern;
+_Static_assert(sizeof(rc_pattern) == 40, "rc_pattern layout (ctypes binding)");
+/* The built-in pattern of that name into *out: 0, or -1 for an unknown name or a null pointer. */
+int rc_pattern_builtin(const char *name, rc_pattern *out);
+/* 0 when *p is a valid pattern, else -1 with a message naming the rule broken. */
+int rc_pattern_check(const rc_pattern *p);
+/* raycast()'s reading of RAYCAST_PATTERN against the options rc_default_options(.., 1) gave: 1,
+ * the pattern in *out and the threshold in *threshold when the frame goes through
+ * rc_render_pattern; 0 when it goes through rc_render (unset, or ignored with one of the warnings
+ * above). */
+int rc_pattern_env(const rc_options *opt, rc_pattern *out, int *threshold);
+/* rc_render_pattern: host pixmap (W*H*3 bytes), synchronous, on opt->device.
+ * rc_render_pattern_device: device image on the current device and the given HIP stream (NULL:
+ * the library's stream of that device, as rc_render_device); asynchronous unless timing is
+ * requested.  Both return 0 on success. */
+int rc_render_pattern(const rc_scene *scene, int width, int height, const rc_options *opt,
+                      const rc_pattern *pattern, int threshold, uint8_t *pixmap,
+                      rc_timing *timing);
+int rc_render_pattern_device(const rc_scene *scene, int width, int height, const rc_options *opt,
+                             const rc_pattern *pattern, int threshold, uint8_t *d_out,
+                             void *stream, rc_timing *timing);
+typedef struct rc_pattern_stats {
+  int64_t refined_pixels;   /* t = 0: W*H; t > 0: pixels with contrast >= t              */
+  int64_t rays;             /* t = 0: n*W*H; t > 0: W*H + n*refined_pixels               */
+} rc_pattern_stats;
+/* The last pattern frame enqueued on the current device; with a threshold it waits for that
+ * frame, then reads its count.  Returns -1 if there was none. */
+int rc_pattern_stats_get(rc_pattern_stats *out);
+/* The kernel spans (ms, HIP events) of the last pattern frame on the current device.  t = 0:
+ * ms[0] the pattern kernel, ms[1] = ms[2] = 0.  t > 0: ms[0] the one-ray image, ms[1] the edge
+ * list, ms[2] the refinement.  Returns -1 if there was none. */
+int rc_pattern_phase_ms(double ms[3]);
 
 /* Frames in flight (an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out

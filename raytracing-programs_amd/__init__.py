@@ -98,6 +98,30 @@ class RcFilter(ctypes.Structure):
 FILTER_TILES = {2: (32, 16), 4: (32, 8), 8: (16, 8)}
 
 
+PATTERN_MAX_SAMPLES = 16
+
+
+class RcPattern(ctypes.Structure):
+    """rc_pattern (40 bytes): the lattice g, the sample count n and the positions px, py."""
+    _fields_ = [("grid", ctypes.c_int32), ("nsamples", ctypes.c_int32),
+                ("x", ctypes.c_uint8 * PATTERN_MAX_SAMPLES),
+                ("y", ctypes.c_uint8 * PATTERN_MAX_SAMPLES)]
+
+
+class RcPatternStats(ctypes.Structure):
+    _fields_ = [("refined_pixels", ctypes.c_int64), ("rays", ctypes.c_int64)]
+
+
+# the built-in sample patterns (rc_pattern_builtin): name -> (g, [(x, y), ...]), x to the right
+# and y downwards on the g x g subsample lattice of a pixel
+PATTERNS = {
+    "diag2": (2, [(0, 0), (1, 1)]),
+    "rgss4": (4, [(1, 0), (3, 1), (0, 2), (2, 3)]),
+    "checker8": (4, [(i, j) for j in range(4) for i in range(4) if (i + j) % 2 == 0]),
+    "queens8": (8, [(c, r) for r, c in enumerate([3, 6, 2, 7, 1, 4, 0, 5])]),
+}
+
+
 # the values a rate map's bytes may take (rc_render_rates): 0 leaves the pixel alone
 RATE_VALUES = (0, 1, 2, 4, 8)
 
@@ -168,7 +192,9 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_adaptive_phase_ms", "rc_render_rates", "rc_render_rates_device",
                "rc_rate_stats_get", "rc_rate_phase_ms", "rc_filter_box", "rc_filter_tent",
                "rc_filter_check", "rc_filter_env", "rc_render_filtered",
-               "rc_render_filtered_device", "rc_filter_image_device", "rc_filter_phase_ms"]
+               "rc_render_filtered_device", "rc_filter_image_device", "rc_filter_phase_ms",
+               "rc_pattern_builtin", "rc_pattern_check", "rc_pattern_env", "rc_render_pattern",
+               "rc_render_pattern_device", "rc_pattern_stats_get", "rc_pattern_phase_ms"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -308,6 +334,19 @@ def _hip_lib_locked():
                                            ctypes.c_int, ctypes.POINTER(RcFilter),
                                            ctypes.c_void_p, ctypes.c_void_p]
     lib.rc_filter_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    lib.rc_pattern_builtin.argtypes = [ctypes.c_char_p, ctypes.POINTER(RcPattern)]
+    lib.rc_pattern_check.argtypes = [ctypes.POINTER(RcPattern)]
+    lib.rc_pattern_env.argtypes = [ctypes.POINTER(RcOptions), ctypes.POINTER(RcPattern),
+                                   ctypes.POINTER(ctypes.c_int)]
+    lib.rc_render_pattern.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(RcOptions), ctypes.POINTER(RcPattern),
+                                      ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(RcTiming)]
+    lib.rc_render_pattern_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(RcOptions), ctypes.POINTER(RcPattern),
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.POINTER(RcTiming)]
+    lib.rc_pattern_stats_get.argtypes = [ctypes.POINTER(RcPatternStats)]
+    lib.rc_pattern_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
     _hip = lib
     return lib
 
@@ -829,6 +868,134 @@ def filter_from_env(ssaa=1, adaptive=0):
     if hip_lib().rc_filter_env(ctypes.byref(opt), ctypes.byref(f)) != 1:
         return None
     return [int(f.taps[i]) for i in range(f.ntaps)]
+
+
+def pattern_check(g, points):
+    """The rules of a sample pattern (include/raycast_hip.h, rc_pattern), stated here so that they
+    hold without the library; returns the sample count n, raises ValueError naming the rule."""
+    g = int(g)
+    if g not in (2, 4, 8):
+        raise ValueError(f"pattern: grid {g} is not 2, 4 or 8")
+    pts = [(int(x), int(y)) for x, y in points]
+    n = len(pts)
+    if n not in (2, 4, 8, 16):
+        raise ValueError(f"pattern: {n} samples, not 2, 4, 8 or 16")
+    if n > g * g:
+        raise ValueError(f"pattern: {n} samples on a {g} x {g} lattice of {g * g} points")
+    for k, (x, y) in enumerate(pts):
+        if not (0 <= x < g and 0 <= y < g):
+            raise ValueError(f"pattern: sample {k} at ({x}, {y}) is off the {g} x {g} lattice")
+        if (x, y) in pts[:k]:
+            raise ValueError(f"pattern: sample {k} repeats ({x}, {y})")
+    return n
+
+
+def pattern(p):
+    """A checked pattern (g, [(x, y), ...]) from a built-in name (PATTERNS) or a (g, points)
+    pair."""
+    if isinstance(p, str):
+        if p not in PATTERNS:
+            raise ValueError(f"pattern: '{p}' is not one of {sorted(PATTERNS)}")
+        p = PATTERNS[p]
+    g, points = p
+    pts = [(int(x), int(y)) for x, y in points]
+    pattern_check(g, pts)
+    return int(g), pts
+
+
+def pattern_downsample(big, g, points):
+    """The pattern contract (include/raycast_hip.h, rc_pattern) in numpy: the [H, W, C] uint8 image
+    of a [g*H, g*W, C] uint8 image, per channel (sum over the n points (x, y) of
+    big[g*Y + y, g*X + x] + n/2) // n."""
+    big = np.asarray(big)
+    g = int(g)
+    points = [(int(x), int(y)) for x, y in points]
+    n = pattern_check(g, points)
+    if big.dtype != np.uint8 or big.ndim != 3 or big.shape[0] % g or big.shape[1] % g:
+        raise ValueError(f"pattern_downsample: a uint8 [g*H, g*W, C] image, got {big.dtype} "
+                         f"{big.shape} and g = {g}")
+    total = sum(big[int(y)::g, int(x)::g].astype(np.uint32) for x, y in points)
+    return ((total + n // 2) // n).astype(np.uint8)
+
+
+def _rc_pattern(p):
+    g, pts = pattern(p)
+    pat = RcPattern()
+    pat.grid, pat.nsamples = g, len(pts)
+    for k, (x, y) in enumerate(pts):
+        pat.x[k], pat.y[k] = x, y
+    return pat
+
+
+def render_pattern(scene, width, height, pat, threshold=0, depth=6, mode="fast", device=0,
+                   timing=None, out=None):
+    """rc_render_pattern: every pixel (threshold 0) or the pixels of the one-ray image whose
+    3 x 3 contrast reaches `threshold` (adaptive_compose) get the rounded mean of the pattern's
+    samples of the g*W x g*H image (pattern_downsample).  `pat` is a built-in name or a
+    (g, [(x, y), ...]) pair.  Fast and cuda mode."""
+    lib = hip_lib()
+    p = _rc_pattern(pat)
+    if out is None:
+        out = np.empty((height, width, 3), dtype=np.uint8)
+    assert out.shape == (height, width, 3) and out.dtype == np.uint8 and out.flags.c_contiguous
+    t = RcTiming()
+    opt = options(depth, mode, 1, device)
+    rc = lib.rc_render_pattern(scene.packed(), width, height, ctypes.byref(opt), ctypes.byref(p),
+                               int(threshold), out.ctypes.data_as(ctypes.c_void_p),
+                               ctypes.byref(t))
+    if rc != 0:
+        raise RuntimeError("rc_render_pattern failed (see stderr)")
+    if timing is not None:
+        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    return out
+
+
+def render_pattern_device(scene, width, height, pat, d_out_ptr, threshold=0, stream_ptr=None,
+                          depth=6, mode="fast", timing=None):
+    """rc_render_pattern_device: the image (W*H*3 bytes) is device memory; enqueued on the stream
+    and asynchronous unless `timing` is given."""
+    lib = hip_lib()
+    p = _rc_pattern(pat)
+    opt = options(depth, mode)
+    t = RcTiming()
+    rc = lib.rc_render_pattern_device(scene.packed(), width, height, ctypes.byref(opt),
+                                      ctypes.byref(p), int(threshold), ctypes.c_void_p(d_out_ptr),
+                                      ctypes.c_void_p(stream_ptr or 0),
+                                      ctypes.byref(t) if timing is not None else None)
+    if rc != 0:
+        raise RuntimeError("rc_render_pattern_device failed (see stderr)")
+    if timing is not None:
+        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+
+
+def pattern_stats():
+    """The last pattern frame enqueued on the current device (rc_pattern_stats_get, which waits
+    for it): {"refined_pixels", "rays"}; threshold 0: W*H and n*W*H, else the listed pixels and
+    W*H + n*listed."""
+    st = RcPatternStats()
+    if hip_lib().rc_pattern_stats_get(ctypes.byref(st)) != 0:
+        raise RuntimeError("rc_pattern_stats_get: no pattern frame on this device")
+    return {k: getattr(st, k) for k, _ in RcPatternStats._fields_}
+
+
+def pattern_phase_ms():
+    """Kernel spans of the last pattern frame (rc_pattern_phase_ms), in ms: {"render", "mark",
+    "refine"}; threshold 0: "render" is the pattern kernel and the others are 0."""
+    ms = (ctypes.c_double * 3)()
+    if hip_lib().rc_pattern_phase_ms(ms) != 0:
+        raise RuntimeError("rc_pattern_phase_ms: no pattern frame on this device")
+    return {"render": ms[0], "mark": ms[1], "refine": ms[2]}
+
+
+def pattern_from_env(mode="fast", ssaa=1, adaptive=0):
+    """raycast()'s reading of RAYCAST_PATTERN (rc_pattern_env) for a frame of that mode, factor
+    and adaptive threshold: (g, [(x, y), ...], t) when the frame goes through the pattern path,
+    None when it goes through rc_render (the warnings go to stderr)."""
+    p, t = RcPattern(), ctypes.c_int(0)
+    opt = options(mode=mode, ssaa=ssaa, adaptive=adaptive)
+    if hip_lib().rc_pattern_env(ctypes.byref(opt), ctypes.byref(p), ctypes.byref(t)) != 1:
+        return None
+    return p.grid, [(int(p.x[k]), int(p.y[k])) for k in range(p.nsamples)], t.value
 
 
 SPIN_SITES = ("team_handoff", "phase_c_carry_in", "ready_queue", "helper_queue")

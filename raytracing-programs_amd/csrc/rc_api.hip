@@ -911,6 +911,192 @@ static int filtered_refused(const char* who, const rc_options* opt, int W, int H
   return ss;
 }
 
+// ------------------------------------------------------------ sparse sample patterns --
+int rc_pattern_stats_get(rc_pattern_stats* out) {
+  if (!out) return -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->pat_valid) return -1;
+  int64_t refined = (int64_t)c->pat_pixels;   // without a threshold: known without the device
+  if (c->pat_t > 0) {
+    HIP_TRY(hipEventSynchronize(c->pat_done));   // the frame's stream, up to its refinement
+    unsigned n = 0;
+    HIP_TRY(hipMemcpy(&n, c->pat_count.p, sizeof n, hipMemcpyDeviceToHost));
+    refined = (int64_t)n;
+  }
+  out->refined_pixels = refined;
+  out->rays = (c->pat_t > 0 ? (int64_t)c->pat_pixels : 0) + (int64_t)c->pat_n * refined;
+  return 0;
+}
+
+int rc_pattern_phase_ms(double ms[3]) {
+  if (!ms) return -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (!c->pat_ev) return -1;
+  hipEvent_t* ev = c->pat_ev;
+  HIP_TRY(hipEventSynchronize(ev[1]));
+  if (c->pat_ev_listed) {
+    ms[0] = event_ms(ev[0], ev[2]);
+    ms[1] = event_ms(ev[2], ev[3]);
+    ms[2] = event_ms(ev[3], ev[1]);
+  } else {
+    ms[0] = event_ms(ev[0], ev[1]);
+    ms[1] = ms[2] = 0.0;
+  }
+  return 0;
+}
+
+// (x, y) pairs, x to the right and y downwards (include/raycast_hip.h, rc_pattern)
+static const struct {
+  const char* name;
+  int grid, nsamples;
+  uint8_t xy[RC_PATTERN_MAX_SAMPLES][2];
+} kPatterns[] = {
+    {"diag2", 2, 2, {{0, 0}, {1, 1}}},
+    {"rgss4", 4, 4, {{1, 0}, {3, 1}, {0, 2}, {2, 3}}},
+    {"checker8", 4, 8, {{0, 0}, {2, 0}, {1, 1}, {3, 1}, {0, 2}, {2, 2}, {1, 3}, {3, 3}}},
+    {"queens8", 8, 8, {{3, 0}, {6, 1}, {2, 2}, {7, 3}, {1, 4}, {4, 5}, {0, 6}, {5, 7}}},
+};
+
+int rc_pattern_builtin(const char* name, rc_pattern* out) {
+  if (!name || !out) return -1;
+  for (const auto& p : kPatterns) {
+    if (std::strcmp(name, p.name)) continue;
+    std::memset(out, 0, sizeof *out);
+    out->grid = p.grid;
+    out->nsamples = p.nsamples;
+    for (int k = 0; k < p.nsamples; ++k) {
+      out->x[k] = p.xy[k][0];
+      out->y[k] = p.xy[k][1];
+    }
+    return 0;
+  }
+  return -1;
+}
+
+int rc_pattern_check(const rc_pattern* p) {
+  if (!p) {
+    std::fprintf(stderr, "Error: rc_pattern_check: a null pattern\n");
+    return -1;
+  }
+  const int g = p->grid, n = p->nsamples;
+  if (g != 2 && g != 4 && g != 8) {
+    std::fprintf(stderr, "Error: rc_pattern_check: grid %d is not 2, 4 or 8\n", g);
+    return -1;
+  }
+  if (n != 2 && n != 4 && n != 8 && n != 16) {
+    std::fprintf(stderr, "Error: rc_pattern_check: %d samples, not 2, 4, 8 or 16\n", n);
+    return -1;
+  }
+  if (n > g * g) {
+    std::fprintf(stderr, "Error: rc_pattern_check: %d samples on a %d x %d lattice of %d points\n",
+                 n, g, g, g * g);
+    return -1;
+  }
+  for (int k = 0; k < n; ++k) {
+    if (p->x[k] >= g || p->y[k] >= g) {
+      std::fprintf(stderr, "Error: rc_pattern_check: sample %d at (%d, %d) is off the %d x %d "
+                   "lattice\n", k, p->x[k], p->y[k], g, g);
+      return -1;
+    }
+    for (int j = 0; j < k; ++j)
+      if (p->x[j] == p->x[k] && p->y[j] == p->y[k]) {
+        std::fprintf(stderr, "Error: rc_pattern_check: samples %d and %d are both at (%d, %d)\n",
+                     j, k, p->x[k], p->y[k]);
+        return -1;
+      }
+  }
+  return 0;
+}
+
+int rc_pattern_env(const rc_options* opt, rc_pattern* out, int* threshold) {
+  const char* v = std::getenv("RAYCAST_PATTERN");
+  if (!v || !opt || !out || !threshold) return 0;
+  const char* colon = std::strchr(v, ':');
+  const std::string name = colon ? std::string(v, colon) : std::string(v);
+  rc_pattern pat;
+  if (rc_pattern_builtin(name.c_str(), &pat)) {
+    std::fprintf(stderr, "Warning: RAYCAST_PATTERN '%s': '%s' is not diag2, rgss4, checker8 or "
+                 "queens8, ignored\n", v, name.c_str());
+    return 0;
+  }
+  long t = 0;
+  if (colon) {
+    char* end = nullptr;
+    t = std::strtol(colon + 1, &end, 10);
+    if (colon[1] < '0' || colon[1] > '9' || *end != '\0' || t > 255) {
+      std::fprintf(stderr, "Warning: RAYCAST_PATTERN '%s': '%s' is not a threshold 0..255, "
+                   "ignored\n", v, colon + 1);
+      return 0;
+    }
+  }
+  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
+    std::fprintf(stderr, "Warning: RAYCAST_PATTERN '%s' is for fast and cuda mode (a parity image "
+                 "cannot be shot sparsely), ignored\n", v);
+    return 0;
+  }
+  if (RC_SSAA_FACTOR(opt->ssaa) > 1 || RC_SSAA_THRESHOLD(opt->ssaa) > 0) {
+    std::fprintf(stderr, "Warning: RAYCAST_PATTERN '%s' does not combine with RAYCAST_SSAA %d "
+                 "(the pattern carries its own grid), ignored\n", v, RC_SSAA_FACTOR(opt->ssaa));
+    return 0;
+  }
+  *out = pat;
+  *threshold = (int)t;
+  return 1;
+}
+
+// What the pattern entry points refuse from their arguments alone.
+static int pattern_refused(const char* who, const rc_options* opt, int W, int H,
+                           const rc_pattern* pat, int threshold) {
+  const int ss = ssaa_factor(opt, who);
+  if (ss < 0) return -1;   // ssaa_decode has said why (a threshold without a factor included)
+  if (ss > 1) {
+    std::fprintf(stderr, "Error: %s: ssaa %d in the options: the pattern carries the grid, leave "
+                 "ssaa at 0 or 1\n", who, opt->ssaa);
+    return -1;
+  }
+  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
+    std::fprintf(stderr, "Error: %s: a sample pattern is for fast and cuda mode: every pixel of a "
+                 "parity image depends on the scan-order carry of the whole image, so it cannot "
+                 "be shot sparsely; use plain ssaa\n", who);
+    return -1;
+  }
+  if (opt->num_gpus > 1) {
+    std::fprintf(stderr, "Error: %s: num_gpus %d: the row shards take no sample pattern\n", who,
+                 opt->num_gpus);
+    return -1;
+  }
+  if (rc_pattern_check(pat)) return -1;
+  if (threshold < 0 || threshold > 255) {
+    std::fprintf(stderr, "Error: %s: threshold %d is not 0..255\n", who, threshold);
+    return -1;
+  }
+  const int g = pat->grid;
+  if (W <= 0 || H <= 0 || W > (1 << 28) / g || H > (1 << 28) / g) {
+    std::fprintf(stderr, "Error: %s: %d x %d on a lattice of %d: both sides must be 1 .. 2^28 / "
+                 "g\n", who, W, H, g);
+    return -1;
+  }
+  if (threshold > 0 && (unsigned long long)W * (unsigned long long)H >= (1ull << 32)) {
+    std::fprintf(stderr, "Error: %s: %d x %d with a threshold is too large (32-bit pixel "
+                 "indices)\n", who, W, H);
+    return -1;
+  }
+  if (!rc::pattern_supported(W, H, g, pat->nsamples, threshold > 0)) {
+    std::fprintf(stderr, "Error: %s: %d x %d is too large for %d samples a pixel (at most 65535 "
+                 "rows of tiles)\n", who, W, H, pat->nsamples);
+    return -1;
+  }
+  return 0;
+}
+
 void rc_default_options(rc_options* opt, int use_env) {
   opt->max_recursion = 7;   // C/raycast.c:14
   opt->mode = RC_MODE_PARITY;
@@ -1379,6 +1565,7 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
   if (timed && c.aa_ev == ev) c.aa_ev = nullptr;   // the set is recorded anew (rc_adaptive_phase_ms)
   if (timed && c.rate_ev == ev) c.rate_ev = nullptr;   // likewise (rc_rate_phase_ms)
   if (timed && c.filt_ev == ev) c.filt_ev = nullptr;   // likewise (rc_filter_phase_ms)
+  if (timed && c.pat_ev == ev) c.pat_ev = nullptr;     // likewise (rc_pattern_phase_ms)
   if (timed) HIP_TRY(hipEventRecord(ev[0], stream));
   if (!parity) {
     if (fused)   // the subsamples on adjacent lanes, box-filtered in registers
@@ -1491,6 +1678,7 @@ static int enqueue_rates(DevCtx& c, const rc_scene* s, int W, int H, const rc_op
     }
     if (c.aa_ev == ev) c.aa_ev = nullptr;   // the set is recorded anew (rc_adaptive_phase_ms)
     if (c.filt_ev == ev) c.filt_ev = nullptr;   // likewise (rc_filter_phase_ms)
+    if (c.pat_ev == ev) c.pat_ev = nullptr;     // likewise (rc_pattern_phase_ms)
     c.rate_ev = nullptr;
     // The lists follow the map's row-major order, so over a uniform region entry k is pixel
     // k + const and a wave's static stride (workgroups * 4 waves * pixels per step) that is a
@@ -1516,6 +1704,71 @@ static int enqueue_rates(DevCtx& c, const rc_scene* s, int W, int H, const rc_op
     HIP_TRY(hipEventRecord(ev[1], stream));
     c.rate_valid = true;
     c.rate_ev = ev;
+    return 0;
+  };
+  const int rc = body();
+  // recorded even after a failed enqueue: whatever was enqueued stays ordered
+  HIP_TRY(hipEventRecord(c.ws_ev, stream));
+  c.ws_stream = stream;
+  c.ws_valid = true;
+  return rc;
+}
+
+// One pattern frame on `stream` through the device's one-frame workspace (the caller holds c.mu
+// and has passed pattern_refused).  at = 0: the dense kernel.  at > 0: the one-ray image by the
+// plain kernel, the adaptive path's edge list (launch_aa_mark into aa_list), then the pattern
+// kernel over the list: three launches with no host wait in between.
+static int enqueue_pattern(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
+                           const rc_pattern* pat, int at, uint8_t* d_out, hipStream_t stream) {
+  if (flush_phase_c(c, false)) return -1;
+  if (at > 0 && (c.pat_count.ensure(8) || c.aa_list.ensure((size_t)W * H * sizeof(uint32_t)))) {
+    std::fprintf(stderr, "Error: out of device memory for the edge list (%d x %d)\n", W, H);
+    return -1;
+  }
+  if (at > 0 && !c.pat_done)
+    HIP_TRY(hipEventCreateWithFlags(&c.pat_done, hipEventDisableTiming));
+  if (c.ws_valid && c.ws_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, c.ws_ev, 0));
+  auto body = [&]() -> int {
+    rc::LaunchScene ls;
+    if (upload_scene(c.fb, stream, s, ls)) return -1;
+    unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
+    unsigned* cnt = (unsigned*)c.pat_count.p;
+    uint32_t* list = (uint32_t*)c.aa_list.p;
+    HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
+    if (at > 0) HIP_TRY(hipMemsetAsync(cnt, 0, 8, stream));
+    const int maxrec = opt->max_recursion, g = pat->grid, n = pat->nsamples;
+    const bool cuda = opt->mode == RC_MODE_CUDA;
+    hipEvent_t* ev = c.ev[0];
+    if (c.prof_active) {
+      ev = c.ev[c.prof_calls % DevCtx::kEvSets];
+      c.prof_calls++;
+      c.prof_parity = false;
+    }
+    if (c.aa_ev == ev) c.aa_ev = nullptr;   // the set is recorded anew (rc_adaptive_phase_ms)
+    if (c.rate_ev == ev) c.rate_ev = nullptr;   // likewise (rc_rate_phase_ms)
+    if (c.filt_ev == ev) c.filt_ev = nullptr;   // likewise (rc_filter_phase_ms)
+    c.pat_ev = nullptr;
+    HIP_TRY(hipEventRecord(ev[0], stream));
+    if (at == 0) {
+      HIP_TRY(rc::launch_pattern(ls, W, H, g, n, pat->x, pat->y, maxrec, d_out, zc, stream, cuda));
+    } else {
+      HIP_TRY(rc::launch_render(ls, W, H, 0, 1, H, maxrec, d_out, zc, stream, cuda));
+      HIP_TRY(hipEventRecord(ev[2], stream));
+      HIP_TRY(rc::launch_aa_mark(d_out, W, H, at, list, cnt, stream));
+      HIP_TRY(hipEventRecord(ev[3], stream));
+      HIP_TRY(rc::launch_pattern_list(
+          ls, W, H, g, n, pat->x, pat->y, maxrec, list, cnt, d_out, zc,
+          rc::pattern_list_blocks(W, H, n, c.cus, tune().adaptive_blocks), stream, cuda));
+    }
+    HIP_TRY(hipEventRecord(ev[1], stream));
+    // behind the span's end, and only where rc_pattern_stats_get has a count to wait for
+    if (at > 0) HIP_TRY(hipEventRecord(c.pat_done, stream));
+    c.pat_valid = true;
+    c.pat_n = n;
+    c.pat_t = at;
+    c.pat_pixels = (long long)W * H;
+    c.pat_ev = ev;
+    c.pat_ev_listed = at > 0;
     return 0;
   };
   const int rc = body();
@@ -1901,6 +2154,78 @@ int rc_render_rates(const rc_scene* s, int W, int H, const rc_options* opt, cons
   if (enqueue_rates(*c, s, W, H, opt, d_rates, d_out, c->stream)) return -1;
   auto td = std::chrono::steady_clock::now();
   if (copy_to_host(*c, pixmap, d_out, pixels * 3, c->stream, tu)) return -1;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  fill_device_timing(*c, opt, timing);
+  if (timing) {
+    timing->d2h_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
+    timing->total_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return 0;
+}
+
+int rc_render_pattern_device(const rc_scene* s, int W, int H, const rc_options* opt,
+                             const rc_pattern* pat, int threshold, uint8_t* d_out, void* stream,
+                             rc_timing* timing) {
+  if (!s || !opt || !pat || !d_out) {
+    std::fprintf(stderr, "Error: rc_render_pattern_device: a null pointer\n");
+    return -1;
+  }
+  if (pattern_refused("rc_render_pattern_device", opt, W, H, pat, threshold)) return -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  // an earlier frame of this workspace whose hand-off failed is reported by the next call
+  if (c->lone_log.earlier_failed()) {
+    c->lone_log.take(nullptr, nullptr);
+    return -1;
+  }
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if (enqueue_pattern(*c, s, W, H, opt, pat, threshold, d_out, st)) return -1;
+  if (timing) {
+    std::memset(timing, 0, sizeof *timing);
+    HIP_TRY(hipStreamSynchronize(st));
+    fill_device_timing(*c, opt, timing);
+    timing->total_ms = timing->kernel_ms;
+  }
+  return 0;
+}
+
+int rc_render_pattern(const rc_scene* s, int W, int H, const rc_options* opt,
+                      const rc_pattern* pat, int threshold, uint8_t* pixmap, rc_timing* timing) {
+  if (!s || !opt || !pat || !pixmap) {
+    std::fprintf(stderr, "Error: rc_render_pattern: a null pointer\n");
+    return -1;
+  }
+  auto t0 = std::chrono::steady_clock::now();
+  if (pattern_refused("rc_render_pattern", opt, W, H, pat, threshold)) return -1;
+  if (timing) std::memset(timing, 0, sizeof *timing);
+  const rc_tuning tu = tune();
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (opt->device < 0 || opt->device >= ndev) {
+    std::fprintf(stderr, "Error: device %d not available (%d devices)\n", opt->device, ndev);
+    return -1;
+  }
+  DevCtx* c;
+  if (hipSetDevice(opt->device) != hipSuccess || ctx_get(opt->device, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (c->lone_log.earlier_failed()) {
+    c->lone_log.take(nullptr, nullptr);
+    return -1;
+  }
+  const size_t bytes = (size_t)W * H * 3;
+  if (c->out.ensure(bytes)) {
+    std::fprintf(stderr, "Error: out of device memory for the image (%d x %d)\n", W, H);
+    return -1;
+  }
+  uint8_t* d_out = (uint8_t*)c->out.p;
+  if (enqueue_pattern(*c, s, W, H, opt, pat, threshold, d_out, c->stream)) return -1;
+  auto td = std::chrono::steady_clock::now();
+  if (copy_to_host(*c, pixmap, d_out, bytes, c->stream, tu)) return -1;
   HIP_TRY(hipStreamSynchronize(c->stream));
   fill_device_timing(*c, opt, timing);
   if (timing) {
@@ -2750,9 +3075,15 @@ void raycast(json_data_t* json_struct, PPMFormat photo_data) {
   rc_timing t;
   rc_filter filt;
   const bool filtered = rc_filter_env(&opt, &filt) == 1;   // RAYCAST_FILTER
-  if (filtered ? rc_render_filtered(s, photo_data.width, photo_data.height, &opt, &filt,
+  rc_pattern pat;
+  int pat_t = 0;
+  // RAYCAST_PATTERN (never together with a filter: that needs the RAYCAST_SSAA this refuses)
+  const bool patterned = rc_pattern_env(&opt, &pat, &pat_t) == 1;
+  if (patterned ? rc_render_pattern(s, photo_data.width, photo_data.height, &opt, &pat, pat_t,
                                     photo_data.pixmap, &t)
-               : rc_render(s, photo_data.width, photo_data.height, &opt, photo_data.pixmap, &t)) {
+      : filtered ? rc_render_filtered(s, photo_data.width, photo_data.height, &opt, &filt,
+                                      photo_data.pixmap, &t)
+                 : rc_render(s, photo_data.width, photo_data.height, &opt, photo_data.pixmap, &t)) {
     std::fprintf(stderr, "Error: GPU render failed\n");
     std::exit(1);
   }

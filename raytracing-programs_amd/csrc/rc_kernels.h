@@ -150,6 +150,31 @@ hipError_t launch_rates_refine8(const LaunchScene& s, int W, int H, int maxrec,
                                 unsigned long long* zcount, int blocks, hipStream_t stream,
                                 bool cuda_sem);
 
+// Sparse sample patterns (rc_render_pattern*; fast and cuda modes): n samples (2, 4, 8 or 16,
+// n <= g*g) of every refined pixel at the positions (px[k], py[k]) of its g x g subsample lattice
+// (g = 2, 4 or 8), shot with the camera of the g*W x g*H image, n lanes a pixel; the rounded
+// mean (sum + n/2) / n is stored.  The positions travel to the kernels as 4-bit entries of two
+// 64-bit kernel arguments.
+//   launch_pattern       every pixel of the W x H image (256 / n pixels per workgroup);
+//   launch_pattern_list  the pixels launch_aa_mark listed, over `out`'s one-ray pixels, with
+//                        `blocks` workgroups (pattern_list_blocks) striding over the list, whose
+//                        length is read on the device.
+// zcount: the samples' zero-normalize events (fast).
+// pattern_supported: g, n as above; W, H in 1 .. 2^28 / g; a grid the tile layout can address
+// (dense: at most 65535 rows of tiles and 2^31 - 1 tiles; listed: W*H < 2^32 and k_render's
+// rows of tiles).  The launchers return hipErrorInvalidValue for anything it refuses.
+int pattern_supported(int W, int H, int g, int n, bool listed);
+hipError_t launch_pattern(const LaunchScene& s, int W, int H, int g, int n, const uint8_t* px,
+                          const uint8_t* py, int maxrec, uint8_t* out,
+                          unsigned long long* zcount, hipStream_t stream, bool cuda_sem);
+hipError_t launch_pattern_list(const LaunchScene& s, int W, int H, int g, int n,
+                               const uint8_t* px, const uint8_t* py, int maxrec,
+                               const uint32_t* list, const unsigned* count, uint8_t* out,
+                               unsigned long long* zcount, int blocks, hipStream_t stream,
+                               bool cuda_sem);
+// want > 0: that many; else from the CU count, at most the wave steps a W x H list can need
+int pattern_list_blocks(int W, int H, int n, int cus, int want);
+
 hipError_t launch_parity(const LaunchScene& s, int W, int H, int maxrec, uint8_t* out,
                          const ParityWork& w, unsigned long long* zcount, hipStream_t stream,
                          const hipEvent_t* ev);

@@ -719,6 +719,141 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
   }
 }
 
+// ------------------------------------- sparse sample patterns (fast, cuda) --
+// rc_render_pattern*: n samples of a pixel on its g x g subsample lattice (rc_pattern in
+// include/raycast_hip.h; g = 1 << lg in {2, 4, 8}, n = 1 << ln in {2, 4, 8, 16}).  Sample k of
+// pixel (x, y) is pixel (g*x + px[k], g*y + py[k]) of the g*W x g*H image, shot with that image's
+// camera (`cam`) exactly as k_render_ssaa and k_aa_refine shoot theirs, so every sample byte is
+// that image's byte; the image itself is never stored.
+// Lane l of a wave belongs to pixel group l / n and shoots sample l % n.  The pattern travels as
+// two 64-bit words of 4-bit entries (entry k in bits 4k .. 4k+3 of PatWords::x and ::y), kernel
+// arguments held in scalar registers: a lane takes its own entry with one shift, no table in
+// memory or LDS.  The quantised channels are summed over the group with xor butterflies over the
+// lane bits 1 .. n/2, packed R | G << 16 and B (a channel's sum is <= 16 * 255), and the group's
+// first lane stores (sum + n/2) >> ln.  Every lane of a wave executes every butterfly; lanes whose
+// group is outside the image or past the list shoot nothing, add zeros and store nothing.  A
+// group's lanes share one pixel, so a group is wholly inside or wholly outside.
+struct PatWords {
+  unsigned long long x, y;
+};
+__device__ __forceinline__ int pat_entry(unsigned long long word, unsigned k) {
+  return (int)((word >> (4u * k)) & 15ull);
+}
+// One sample's quantised channels: the subsample (xs, ys) of the g*W x g*H image.
+template <bool kCuda>
+__device__ __forceinline__ void pat_shoot(const Scene& sc, const Cam& cam, int xs, int ys,
+                                          int maxrec, unsigned long long* __restrict__ zcount,
+                                          unsigned& rg, unsigned& b) {
+  V3 c;
+  if constexpr (kCuda) {
+    c = cusem::render_pixel(sc, cam, xs, ys, maxrec - 1);
+  } else {
+    int zero = 0;
+    const V3 d = primary_dir(cam, xs, ys, zero);
+    PixelOut po;
+    shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
+    c = po.rgb;
+    flush_events(zero, zcount);
+  }
+  rg = (unsigned)quant(c.x) | ((unsigned)quant(c.y) << 16);
+  b = quant(c.z);
+}
+// Called by every lane of the wave.
+__device__ __forceinline__ void pat_reduce(unsigned& rg, unsigned& b, int ln) {
+  for (int m = 1; m < (1 << ln); m <<= 1) {
+    rg += __shfl_xor(rg, m, 64);
+    b += __shfl_xor(b, m, 64);
+  }
+}
+__device__ __forceinline__ void pat_store(uint8_t* __restrict__ q, unsigned rg, unsigned b,
+                                          int ln) {
+  const unsigned half = 1u << (ln - 1);
+  q[0] = (uint8_t)(((rg & 0xffffu) + half) >> ln);
+  q[1] = (uint8_t)(((rg >> 16) + half) >> ln);
+  q[2] = (uint8_t)((b + half) >> ln);
+}
+
+// The wave block of the dense form: a wave's 64 / n pixels are a compact bw x bh block,
+//   n = 2: 8 x 4    n = 4: 4 x 4    n = 8: 4 x 2    n = 16: 2 x 2     (bw >= bh, both powers of two)
+// and a workgroup's four waves sit 2 x 2, so a workgroup owns a tile of 2*bw x 2*bh = 256 / n
+// output pixels: 16 x 8, 8 x 8, 8 x 4, 4 x 4.
+__host__ __device__ constexpr int pat_lbw(int ln) { return (7 - ln) / 2; }   // log2 bw
+__host__ __device__ constexpr int pat_lbh(int ln) { return (6 - ln) / 2; }   // log2 bh
+static_assert(pat_lbw(1) == 3 && pat_lbh(1) == 2 && pat_lbw(2) == 2 && pat_lbh(2) == 2 &&
+              pat_lbw(3) == 2 && pat_lbh(3) == 1 && pat_lbw(4) == 1 && pat_lbh(4) == 1,
+              "a wave's 64 / n pixels");
+
+// Dense form (threshold 0): every pixel of the image, one workgroup per tile, the tiles taken
+// through xcd_tile in the grid's own order like k_render's.  The tiles are small, so a 128-byte
+// line of the framebuffer spans several of them, but k_phase_a's order (chunks of 8 horizontally
+// adjacent tiles share an L2) measured slower at every n (quadric, rgss4: 1024^2 0.189 against
+// 0.176 ms, 2048^2 0.659 against 0.635 ms), as it did for k_render.
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_pattern(
+    Scene sc, Cam cam, int W, int H, int lg, int ln, PatWords pat, int maxrec,
+    uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount) {
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  stage_scene<kStage>(sc, stage);
+  int bx, by;
+  xcd_tile<0>(bx, by);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lbw = pat_lbw(ln), lbh = pat_lbh(ln);
+  const int grp = lane >> ln;                                    // the wave's pixel group
+  const unsigned k = (unsigned)lane & ((1u << ln) - 1u);         // the lane's sample
+  const int x = (((bx << 1) + (wave & 1)) << lbw) + (grp & ((1 << lbw) - 1));
+  const int y = (((by << 1) + (wave >> 1)) << lbh) + (grp >> lbw);
+  const bool inside = x < W && y < H;
+  unsigned rg = 0u, b = 0u;
+  if (inside)
+    pat_shoot<kCuda>(sc, cam, (x << lg) + pat_entry(pat.x, k), (y << lg) + pat_entry(pat.y, k),
+                     maxrec, zcount, rg, b);
+  pat_reduce(rg, b, ln);
+  if (inside && k == 0u) pat_store(out + ((size_t)y * W + x) * 3, rg, b, ln);
+}
+
+// List form (threshold t > 0): over k_aa_mark's list like k_aa_refine, 64 / n listed pixels per
+// wave step; the list's length is read from device memory and the grid is a fixed number of
+// workgroups whose waves stride over the list.  A wave's trip count depends on the wave alone.
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_pattern_list(
+    Scene sc, Cam cam, int W, int lg, int ln, PatWords pat, int maxrec,
+    const uint32_t* __restrict__ list, const unsigned* __restrict__ count,
+    uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount) {
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  const unsigned n = *count;
+  if (n == 0u) return;   // uniform over the grid: an empty list costs its launch
+  stage_scene<kStage>(sc, stage);   // its barrier comes before the loop: every thread is here
+  const int lane = threadIdx.x & 63;
+  const unsigned per = 64u >> ln;                              // listed pixels per wave step
+  const unsigned k = (unsigned)lane & ((1u << ln) - 1u);       // the lane's sample
+  const int px = pat_entry(pat.x, k), py = pat_entry(pat.y, k);
+  // wave-uniform by construction: told to the compiler, so the loop's counters stay scalar
+  const unsigned wave =
+      __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
+  const unsigned step = gridDim.x * (kBlock / 64) * per;   // <= 4096 * 4 * 32
+  // 64-bit index: n + step may pass 2^32
+  for (unsigned long long first = (unsigned long long)wave * per; first < n; first += step) {
+    const unsigned long long e = first + ((unsigned)lane >> ln);
+    const bool live = e < n;
+    unsigned rg = 0u, b = 0u;
+    if (live) {
+      const unsigned p = list[e];
+      pat_shoot<kCuda>(sc, cam, (int)((p % (unsigned)W) << lg) + px,
+                       (int)((p / (unsigned)W) << lg) + py, maxrec, zcount, rg, b);
+    }
+    pat_reduce(rg, b, ln);
+    if (live && k == 0u) {
+      // the entry is read again (opaque index) rather than kept in a register across shoot, as
+      // in k_aa_refine
+      unsigned g = (unsigned)lane >> ln;
+      asm volatile("" : "+v"(g));
+      pat_store(out + (size_t)list[first + g] * 3, rg, b, ln);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ parity phase A --
 // A writer's carry-out is read only as a segment key: the last writer before a DEP pixel in
 // scan order (seg_init_carry), and by the row shards the last writer before a DEP pixel in its
@@ -3502,14 +3637,19 @@ hipError_t launch_aa_mark(const uint8_t* img, int W, int H, int threshold, uint3
   return hipGetLastError();
 }
 
-int aa_refine_blocks(int W, int H, int ssaa, int cus, int want) {
+// the grid of a kernel that strides over a list of at most W*H pixels with `lanes` lanes a pixel
+static int list_blocks(int W, int H, int lanes, int cus, int want) {
   if (want > 0) return want;
   // the kernels are compiled for RC_PHASE_A_WAVES waves per SIMD: that many 4-wave workgroups
   // per CU are resident at once; never more workgroups than the image has wave steps
-  const unsigned long long per = 64u / (unsigned)(ssaa * ssaa) * (kBlock / 64);
+  const unsigned long long per = 64u / (unsigned)lanes * (kBlock / 64);
   const unsigned long long need = ((unsigned long long)W * H + per - 1) / per;
   const unsigned long long cap = (unsigned long long)(cus > 0 ? cus : 256) * RC_PHASE_A_WAVES;
   return (int)(need < cap ? need : cap);
+}
+
+int aa_refine_blocks(int W, int H, int ssaa, int cus, int want) {
+  return list_blocks(W, H, ssaa * ssaa, cus, want);
 }
 
 hipError_t launch_aa_refine(const LaunchScene& s, int W, int H, int ssaa, int maxrec,
@@ -3578,6 +3718,84 @@ hipError_t launch_rates_refine8(const LaunchScene& s, int W, int H, int maxrec,
     st ? go(k_rates_refine8<true, true>) : go(k_rates_refine8<true, false>);
   else
     st ? go(k_rates_refine8<false, true>) : go(k_rates_refine8<false, false>);
+  return hipGetLastError();
+}
+
+static int pattern_log2(int v, int lo, int hi) {
+  for (int l = lo; l <= hi; ++l)
+    if (v == 1 << l) return l;
+  return -1;
+}
+
+int pattern_supported(int W, int H, int g, int n, bool listed) {
+  const int lg = pattern_log2(g, 1, 3), ln = pattern_log2(n, 1, 4);
+  if (lg < 0 || ln < 0 || n > g * g) return 0;
+  if (W <= 0 || H <= 0 || W > (1 << 28) / g || H > (1 << 28) / g) return 0;   // g*W, g*H within int
+  if (!listed) {   // the dense form's tiles: grid.y, and xcd_tile's int tile index
+    const unsigned long long tx = (((unsigned)W - 1u) >> (pat_lbw(ln) + 1)) + 1u;
+    const unsigned long long ty = (((unsigned)H - 1u) >> (pat_lbh(ln) + 1)) + 1u;
+    return ty <= 65535ull && tx * ty <= 0x7fffffffull;
+  }
+  if ((unsigned long long)W * (unsigned long long)H >= (1ull << 32)) return 0;   // uint32 entries
+  return ((unsigned)H + kTileH - 1) / kTileH <= 65535u;   // grid.y of k_render's tile layout
+}
+
+int pattern_list_blocks(int W, int H, int n, int cus, int want) {
+  return list_blocks(W, H, n, cus, want);
+}
+
+// entry k of the 4-bit words: v[k] < 16 for k < n <= 16 (pattern_supported's g <= 8)
+static PatWords pattern_words(int n, const uint8_t* px, const uint8_t* py) {
+  PatWords w{0ull, 0ull};
+  for (int k = 0; k < n; ++k) {
+    w.x |= (unsigned long long)(px[k] & 15u) << (4 * k);
+    w.y |= (unsigned long long)(py[k] & 15u) << (4 * k);
+  }
+  return w;
+}
+
+hipError_t launch_pattern(const LaunchScene& s, int W, int H, int g, int n, const uint8_t* px,
+                          const uint8_t* py, int maxrec, uint8_t* out,
+                          unsigned long long* zcount, hipStream_t stream, bool cuda_sem) {
+  if (!pattern_supported(W, H, g, n, false)) return hipErrorInvalidValue;
+  const int lg = pattern_log2(g, 1, 3), ln = pattern_log2(n, 1, 4);
+  const int ltw = pat_lbw(ln) + 1, lth = pat_lbh(ln) + 1;   // the workgroup's tile
+  dim3 grid((((unsigned)W - 1u) >> ltw) + 1u, (((unsigned)H - 1u) >> lth) + 1u);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, W * g, H * g);   // the camera of the g*W x g*H image
+  const PatWords pat = pattern_words(n, px, py);
+  const bool st = stage_fits(s);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, stream, sc, cam, W, H, lg, ln, pat, maxrec,
+                       out, zcount);
+  };
+  if (cuda_sem)
+    st ? go(k_pattern<true, true>) : go(k_pattern<true, false>);
+  else
+    st ? go(k_pattern<false, true>) : go(k_pattern<false, false>);
+  return hipGetLastError();
+}
+
+hipError_t launch_pattern_list(const LaunchScene& s, int W, int H, int g, int n,
+                               const uint8_t* px, const uint8_t* py, int maxrec,
+                               const uint32_t* list, const unsigned* count, uint8_t* out,
+                               unsigned long long* zcount, int blocks, hipStream_t stream,
+                               bool cuda_sem) {
+  if (!pattern_supported(W, H, g, n, true) || blocks < 1 || blocks > 4096)
+    return hipErrorInvalidValue;
+  const int lg = pattern_log2(g, 1, 3), ln = pattern_log2(n, 1, 4);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, W * g, H * g);   // the camera of the g*W x g*H image
+  const PatWords pat = pattern_words(n, px, py);
+  const bool st = stage_fits(s);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, sc, cam, W, lg, ln,
+                       pat, maxrec, list, count, out, zcount);
+  };
+  if (cuda_sem)
+    st ? go(k_pattern_list<true, true>) : go(k_pattern_list<true, false>);
+  else
+    st ? go(k_pattern_list<false, true>) : go(k_pattern_list<false, false>);
   return hipGetLastError();
 }
 

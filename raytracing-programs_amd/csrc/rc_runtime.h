@@ -172,7 +172,8 @@ struct DevCtx {
   // event sets: [0] start, then per phase ends (fast: [1] = render; parity: [1] phase A,
   // [2] compaction, [3] resolver, [4] phase C; adaptive supersampling: [2] the one-ray image,
   // [3] the edge list, [1] the refinement; rate maps: [2] the rate-1 pass, [1] the
-  // refinement).  Set 0 serves plain calls; inside an
+  // refinement; sample patterns: [1] the frame, with a threshold [2] [3] as adaptive
+  // supersampling).  Set 0 serves plain calls; inside an
   // rc_profile_begin/end window every call takes the next set of the pool.
   static constexpr int kEvSets = 64;
   hipEvent_t ev[kEvSets][5] = {};
@@ -197,6 +198,17 @@ struct DevCtx {
   bool rate_valid = false;           // a rate-map frame has been enqueued on this device
   hipEvent_t* rate_ev = nullptr;     // the event set of the last timed rate-map frame:
                                      // [0] start, [2] the rate-1 pass, [1] the refinement
+  // sparse sample patterns (rc_render_pattern*): the edge list of a frame with a threshold lives
+  // in aa_list; pat_count is its 8-byte counter block (word 0: entries), the frame's own so that
+  // rc_pattern_stats_get outlives a later adaptive frame, zeroed on the frame's stream
+  DevBuf pat_count;
+  hipEvent_t pat_done = nullptr;     // behind the last refinement of a frame with a threshold
+  bool pat_valid = false;            // a pattern frame has been enqueued on this device
+  int pat_n = 0, pat_t = 0;          // its samples per pixel, threshold and pixels
+  long long pat_pixels = 0;          //   (rc_pattern_stats_get)
+  hipEvent_t* pat_ev = nullptr;      // the event set of the last pattern frame: [0] start, [1]
+                                     // end; with a threshold [2] one-ray image, [3] list
+  bool pat_ev_listed = false;        // that frame had a threshold (rc_pattern_phase_ms)
   // two-pass supersampling's own spans (rc_filter_phase_ms): filt_mid is recorded between the
   // s*W x s*H image and its filter; filt_ev is the event set of the last timed two-pass frame
   // ([0] start, [filt_end] behind the filter), null when that set has been recorded anew
