@@ -556,6 +556,20 @@ def adaptive_compose(a, f, t):
     return np.where(edge_mask(a, t)[:, :, None], f, a)
 
 
+def _pixmap(out, width, height, fresh=np.empty):
+    """The caller's [H, W, 3] uint8 C-contiguous pixmap, or a fresh one when `out` is None."""
+    if out is None:
+        out = fresh((height, width, 3), dtype=np.uint8)
+    assert out.shape == (height, width, 3) and out.dtype == np.uint8 and out.flags.c_contiguous
+    return out
+
+
+def _timing_back(timing, t):
+    """Copy the RcTiming record `t` into the caller's dict (None: the caller wants none)."""
+    if timing is not None:
+        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+
+
 def render(scene, width, height, depth=6, mode="parity", gpus=1, device=0, timing=None, out=None,
            ssaa=1, adaptive=0):
     """Render to a host array [H, W, 3] uint8 through rc_render (the raycast() path); `out`
@@ -564,17 +578,14 @@ def render(scene, width, height, depth=6, mode="parity", gpus=1, device=0, timin
     adaptive = t in 1..255 (fast and cuda mode, with ssaa): only the pixels of the one-ray image
     whose 3 x 3 contrast reaches t are supersampled (adaptive_compose)."""
     lib = hip_lib()
-    if out is None:
-        out = np.empty((height, width, 3), dtype=np.uint8)
-    assert out.shape == (height, width, 3) and out.dtype == np.uint8 and out.flags.c_contiguous
+    out = _pixmap(out, width, height)
     t = RcTiming()
     opt = options(depth, mode, gpus, device, ssaa, adaptive)
     rc = lib.rc_render(scene.packed(), width, height, ctypes.byref(opt),
                        out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
     if rc != 0:
         raise RuntimeError("rc_render failed (no GPU, or HIP error: see stderr)")
-    if timing is not None:
-        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    _timing_back(timing, t)
     return out
 
 
@@ -593,8 +604,7 @@ def render_device(scene, width, height, d_out_ptr, stream_ptr=None, depth=6, mod
                               ctypes.byref(t) if timing is not None else None)
     if rc != 0:
         raise RuntimeError("rc_render_device failed (see stderr)")
-    if timing is not None:
-        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    _timing_back(timing, t)
 
 
 def frame_submit(scene, width, height, d_out_ptr, depth=6, mode="parity", ssaa=1, adaptive=0):
@@ -613,8 +623,7 @@ def frames_wait(timing=None):
     if hip_lib().rc_frames_wait(ctypes.byref(t)) != 0:
         raise RuntimeError(f"rc_frames_wait failed: {t.frames_failed} of {t.frames_checked} "
                            "frames' carry hand-offs failed (see stderr)")
-    if timing is not None:
-        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    _timing_back(timing, t)
 
 
 def adaptive_stats():
@@ -671,9 +680,7 @@ def render_rates(scene, width, height, rates, depth=6, mode="fast", out=None, ti
     if rates.dtype != np.uint8 or rates.shape != (height, width):
         raise ValueError(f"rates: uint8 {(height, width)}, got {rates.dtype} {rates.shape}")
     rates = np.ascontiguousarray(rates)
-    if out is None:
-        out = np.zeros((height, width, 3), dtype=np.uint8)
-    assert out.shape == (height, width, 3) and out.dtype == np.uint8 and out.flags.c_contiguous
+    out = _pixmap(out, width, height, np.zeros)
     t = RcTiming()
     opt = options(depth, mode)
     rc = lib.rc_render_rates(scene.packed(), width, height, ctypes.byref(opt),
@@ -681,8 +688,7 @@ def render_rates(scene, width, height, rates, depth=6, mode="fast", out=None, ti
                              out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
     if rc != 0:
         raise RuntimeError("rc_render_rates failed (see stderr)")
-    if timing is not None:
-        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    _timing_back(timing, t)
     return out
 
 
@@ -700,8 +706,7 @@ def render_rates_device(scene, width, height, d_rates_ptr, d_out_ptr, stream_ptr
                                     ctypes.byref(t) if timing is not None else None)
     if rc != 0:
         raise RuntimeError("rc_render_rates_device failed (see stderr)")
-    if timing is not None:
-        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    _timing_back(timing, t)
 
 
 def rate_stats():
@@ -807,17 +812,14 @@ def render_filtered(scene, width, height, taps, ssaa, depth=6, mode="parity", de
     (filter_downsample), into a host array [H, W, 3] uint8.  ssaa is 2, 4 or 8."""
     lib = hip_lib()
     f = _rc_filter(taps, ssaa)
-    if out is None:
-        out = np.empty((height, width, 3), dtype=np.uint8)
-    assert out.shape == (height, width, 3) and out.dtype == np.uint8 and out.flags.c_contiguous
+    out = _pixmap(out, width, height)
     t = RcTiming()
     opt = options(depth, mode, 1, device, ssaa)
     rc = lib.rc_render_filtered(scene.packed(), width, height, ctypes.byref(opt), ctypes.byref(f),
                                 out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
     if rc != 0:
         raise RuntimeError("rc_render_filtered failed (see stderr)")
-    if timing is not None:
-        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    _timing_back(timing, t)
     return out
 
 
@@ -835,8 +837,7 @@ def render_filtered_device(scene, width, height, taps, ssaa, d_out_ptr, stream_p
                                        ctypes.byref(t) if timing is not None else None)
     if rc != 0:
         raise RuntimeError("rc_render_filtered_device failed (see stderr)")
-    if timing is not None:
-        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    _timing_back(timing, t)
 
 
 def filter_image_device(d_src_ptr, width, height, s, taps, d_dst_ptr, stream_ptr=None):
@@ -935,9 +936,7 @@ def render_pattern(scene, width, height, pat, threshold=0, depth=6, mode="fast",
     (g, [(x, y), ...]) pair.  Fast and cuda mode."""
     lib = hip_lib()
     p = _rc_pattern(pat)
-    if out is None:
-        out = np.empty((height, width, 3), dtype=np.uint8)
-    assert out.shape == (height, width, 3) and out.dtype == np.uint8 and out.flags.c_contiguous
+    out = _pixmap(out, width, height)
     t = RcTiming()
     opt = options(depth, mode, 1, device)
     rc = lib.rc_render_pattern(scene.packed(), width, height, ctypes.byref(opt), ctypes.byref(p),
@@ -945,8 +944,7 @@ def render_pattern(scene, width, height, pat, threshold=0, depth=6, mode="fast",
                                ctypes.byref(t))
     if rc != 0:
         raise RuntimeError("rc_render_pattern failed (see stderr)")
-    if timing is not None:
-        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    _timing_back(timing, t)
     return out
 
 
@@ -964,8 +962,7 @@ def render_pattern_device(scene, width, height, pat, d_out_ptr, threshold=0, str
                                       ctypes.byref(t) if timing is not None else None)
     if rc != 0:
         raise RuntimeError("rc_render_pattern_device failed (see stderr)")
-    if timing is not None:
-        timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+    _timing_back(timing, t)
 
 
 def pattern_stats():
@@ -1169,8 +1166,7 @@ class Group:
                                          ctypes.c_void_p(d_image_ptr or 0), ctypes.byref(t))
         if rc != 0:
             raise RuntimeError("rc_render_sharded failed (see stderr)")
-        if timing is not None:
-            timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
+        _timing_back(timing, t)
 
     def stats(self):
         st = RcShardStats()

@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <random>
@@ -649,6 +650,67 @@ int copy_overlapped(DevCtx& c, uint8_t* host, const uint8_t* dev, size_t bytes,
   return 0;
 }
 
+// ------------------------------------------------------ the frame scaffold: entering --
+// A device call's context with its lock held (one render at a time per device, DevCtx::mu).
+struct Entered {
+  DevCtx* c = nullptr;
+  std::unique_lock<std::mutex> lk;
+};
+constexpr int kCurrentDevice = -1;
+
+// opt->device against the device count (*ndev, optional)
+int device_available(const rc_options* opt, int* ndev) {
+  int n = 0;
+  HIP_TRY(hipGetDeviceCount(&n));
+  if (ndev) *ndev = n;
+  if (opt->device < 0 || opt->device >= n) {
+    std::fprintf(stderr, "Error: device %d not available (%d devices)\n", opt->device, n);
+    return -1;
+  }
+  return 0;
+}
+
+// Enter a call on `device` (made current) or on the current one (kCurrentDevice).  The lock
+// covers the workspace from its (re)allocation on: a concurrent caller's ensure() could
+// otherwise free the buffer another caller is rendering into.  render: an earlier frame of this
+// workspace whose hand-off failed (rc_render_device on another stream) is reported by the next
+// render call, before its own frame is enqueued (once: the report consumes the counts).
+int enter(int device, bool render, Entered& e) {
+  if (device == kCurrentDevice)
+    HIP_TRY(hipGetDevice(&device));
+  else if (hipSetDevice(device) != hipSuccess)
+    return -1;
+  if (ctx_get(device, &e.c)) return -1;
+  e.lk = std::unique_lock<std::mutex>(e.c->mu);
+  if (render && e.c->lone_log.earlier_failed()) {
+    e.c->lone_log.take(nullptr, nullptr);
+    return -1;
+  }
+  return 0;
+}
+
+// a host-pixmap render entry: on opt->device
+int enter_host(const rc_options* opt, Entered& e) {
+  return device_available(opt, nullptr) || enter(opt->device, true, e) ? -1 : 0;
+}
+
+// ms[i] = the span marks[i] -> marks[i + 1], once the last mark has completed
+int read_spans(std::initializer_list<hipEvent_t> marks, double* ms) {
+  const hipEvent_t* m = marks.begin();
+  HIP_TRY(hipEventSynchronize(m[marks.size() - 1]));
+  for (size_t i = 0; i + 1 < marks.size(); ++i) ms[i] = event_ms(m[i], m[i + 1]);
+  return 0;
+}
+
+// the listed pixels of f's frame, from its counter block once its refinement has run
+int list_frame_refined(const ListFrame& f, int64_t* refined) {
+  HIP_TRY(hipEventSynchronize(f.done));   // the frame's stream, up to its refinement
+  unsigned n = 0;
+  HIP_TRY(hipMemcpy(&n, f.count.p, sizeof n, hipMemcpyDeviceToHost));
+  *refined = (int64_t)n;
+  return 0;
+}
+
 }  // namespace rcrt
 
 using namespace rcrt;
@@ -714,48 +776,27 @@ int rc_set_tuning(const rc_tuning* t) {
 double rc_last_kernel_ms(void) { return g_last_kernel_ms; }
 
 int rc_adaptive_stats_get(rc_adaptive_stats* out) {
-  if (!out) return -1;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!c->aa_valid) return -1;
-  HIP_TRY(hipEventSynchronize(c->aa_done));   // the frame's stream, up to its refinement
-  unsigned n = 0;
-  HIP_TRY(hipMemcpy(&n, c->aa_count.p, sizeof n, hipMemcpyDeviceToHost));
-  out->refined_pixels = (int64_t)n;
-  out->rays = (int64_t)c->aa_pixels + (int64_t)c->aa_ss * c->aa_ss * (int64_t)n;
+  Entered e;
+  if (!out || enter(kCurrentDevice, false, e) || !e.c->aa.valid) return -1;
+  const ListFrame& f = e.c->aa;
+  if (list_frame_refined(f, &out->refined_pixels)) return -1;
+  out->rays = (int64_t)f.pixels + (int64_t)f.rays * out->refined_pixels;
   return 0;
 }
 
 int rc_adaptive_phase_ms(double ms[3]) {
-  if (!ms) return -1;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!c->aa_ev) return -1;
-  hipEvent_t* ev = c->aa_ev;
-  HIP_TRY(hipEventSynchronize(ev[1]));
-  ms[0] = event_ms(ev[0], ev[2]);
-  ms[1] = event_ms(ev[2], ev[3]);
-  ms[2] = event_ms(ev[3], ev[1]);
-  return 0;
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanAdaptive];
+  return ev ? read_spans({ev[0], ev[2], ev[3], ev[1]}, ms) : -1;
 }
 
 int rc_rate_stats_get(rc_rate_stats* out) {
-  if (!out) return -1;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!c->rate_valid) return -1;
-  HIP_TRY(hipEventSynchronize(c->rate_done));   // the frame's stream, up to its refinement
+  Entered e;
+  if (!out || enter(kCurrentDevice, false, e) || !e.c->rate_valid) return -1;
+  HIP_TRY(hipEventSynchronize(e.c->rate_done));   // the frame's stream, up to its refinement
   unsigned n[5] = {0, 0, 0, 0, 0};   // launch_rates_render's counter block
-  HIP_TRY(hipMemcpy(n, c->rate_count.p, sizeof n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n, e.c->rate_count.p, sizeof n, hipMemcpyDeviceToHost));
   out->pixels[0] = (int64_t)n[3];
   out->pixels[1] = (int64_t)n[0];
   out->pixels[2] = (int64_t)n[1];
@@ -766,33 +807,17 @@ int rc_rate_stats_get(rc_rate_stats* out) {
 }
 
 int rc_rate_phase_ms(double ms[2]) {
-  if (!ms) return -1;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!c->rate_ev) return -1;
-  hipEvent_t* ev = c->rate_ev;
-  HIP_TRY(hipEventSynchronize(ev[1]));
-  ms[0] = event_ms(ev[0], ev[2]);
-  ms[1] = event_ms(ev[2], ev[1]);
-  return 0;
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanRates];
+  return ev ? read_spans({ev[0], ev[2], ev[1]}, ms) : -1;
 }
 
 int rc_filter_phase_ms(double ms[2]) {
-  if (!ms) return -1;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!c->filt_ev) return -1;
-  hipEvent_t* ev = c->filt_ev;
-  HIP_TRY(hipEventSynchronize(ev[c->filt_end]));
-  ms[0] = event_ms(ev[0], c->filt_mid);
-  ms[1] = event_ms(c->filt_mid, ev[c->filt_end]);
-  return 0;
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanFilter];
+  return ev ? read_spans({ev[0], e.c->filt_mid, ev[e.c->filt_end]}, ms) : -1;
 }
 
 // ---------------------------------------------------------- reconstruction filters --
@@ -913,44 +938,25 @@ static int filtered_refused(const char* who, const rc_options* opt, int W, int H
 
 // ------------------------------------------------------------ sparse sample patterns --
 int rc_pattern_stats_get(rc_pattern_stats* out) {
-  if (!out) return -1;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!c->pat_valid) return -1;
-  int64_t refined = (int64_t)c->pat_pixels;   // without a threshold: known without the device
-  if (c->pat_t > 0) {
-    HIP_TRY(hipEventSynchronize(c->pat_done));   // the frame's stream, up to its refinement
-    unsigned n = 0;
-    HIP_TRY(hipMemcpy(&n, c->pat_count.p, sizeof n, hipMemcpyDeviceToHost));
-    refined = (int64_t)n;
-  }
+  Entered e;
+  if (!out || enter(kCurrentDevice, false, e) || !e.c->pat.valid) return -1;
+  const ListFrame& f = e.c->pat;
+  const bool listed = e.c->pat_t > 0;
+  int64_t refined = (int64_t)f.pixels;   // without a threshold: known without the device
+  if (listed && list_frame_refined(f, &refined)) return -1;
   out->refined_pixels = refined;
-  out->rays = (c->pat_t > 0 ? (int64_t)c->pat_pixels : 0) + (int64_t)c->pat_n * refined;
+  out->rays = (listed ? (int64_t)f.pixels : 0) + (int64_t)f.rays * refined;
   return 0;
 }
 
 int rc_pattern_phase_ms(double ms[3]) {
-  if (!ms) return -1;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (!c->pat_ev) return -1;
-  hipEvent_t* ev = c->pat_ev;
-  HIP_TRY(hipEventSynchronize(ev[1]));
-  if (c->pat_ev_listed) {
-    ms[0] = event_ms(ev[0], ev[2]);
-    ms[1] = event_ms(ev[2], ev[3]);
-    ms[2] = event_ms(ev[3], ev[1]);
-  } else {
-    ms[0] = event_ms(ev[0], ev[1]);
-    ms[1] = ms[2] = 0.0;
-  }
-  return 0;
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanPattern];
+  if (!ev) return -1;
+  if (e.c->pat_ev_listed) return read_spans({ev[0], ev[2], ev[3], ev[1]}, ms);
+  ms[1] = ms[2] = 0.0;
+  return read_spans({ev[0], ev[1]}, ms);
 }
 
 // (x, y) pairs, x to the right and y downwards (include/raycast_hip.h, rc_pattern)
@@ -1410,22 +1416,53 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
                       bool timed, uint32_t* patch, hipEvent_t** evset,
                       const rc_filter* filt = nullptr);
 
-// Enqueue one render of rows (row0 + k*row_step) into d_out on `stream`, using the device's
-// one-frame workspace c.fb: after the previous render that used it, whatever its stream.
-int enqueue_render(DevCtx& c, const rc_scene* s, int W, int H, int row0, int row_step, int nrows,
-                   const rc_options* opt, uint8_t* d_out, hipStream_t stream, bool timed,
-                   uint32_t* patch, hipEvent_t** evset, const rc_filter* filt) {
+// The workspace bracket of a frame on `stream` through the device's one-frame workspace c.fb:
+// after the previous frame that used it, whatever its stream.  prepare() is what the frame
+// allocates before it waits for the workspace (a failure there leaves the stream untouched),
+// body() enqueues the frame.
+template <class Prepare, class Body>
+int ws_frame(DevCtx& c, hipStream_t stream, Prepare prepare, Body body) {
   // a frame in flight's held-back phase C goes out first, so that a device synchronisation
   // after this call completes it (rc_frames_wait stays the frames' completion point)
-  if (flush_phase_c(c, false)) return -1;
+  if (flush_phase_c(c, false) || prepare()) return -1;
   if (c.ws_valid && c.ws_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, c.ws_ev, 0));
-  const int rc = enqueue_render_ws(c, s, W, H, row0, row_step, nrows, opt, d_out, stream, timed,
-                                   patch, evset, filt);
+  const int rc = body();
   // recorded even after a failed enqueue: whatever was enqueued stays ordered
   HIP_TRY(hipEventRecord(c.ws_ev, stream));
   c.ws_stream = stream;
   c.ws_valid = true;
   return rc;
+}
+
+// The event set of the frame being enqueued: set 0, or inside an rc_profile_begin/end window
+// the next set of the pool.  The ownership rule of the sets' spans (DevCtx::span_ev) is here and
+// nowhere else: a frame that records the set anew (`records`) takes it from every feature that
+// still points at it, so no rc_*_phase_ms reads another frame's spans; `owner` (or kSpanOwners
+// for none) loses its own spans whatever set they were in, until the frame's enqueue has
+// succeeded and stores the set in span_ev[owner].  Under profiling consecutive frames record
+// different sets, so several owners can stay valid at once.
+hipEvent_t* claim_event_set(DevCtx& c, int owner, bool parity, bool records) {
+  hipEvent_t* ev = c.ev[0];
+  if (c.prof_active) {
+    ev = c.ev[c.prof_calls % DevCtx::kEvSets];
+    c.prof_calls++;
+    c.prof_parity = parity;
+  }
+  if (records)
+    for (hipEvent_t*& held : c.span_ev)
+      if (held == ev) held = nullptr;
+  if (owner != kSpanOwners) c.span_ev[owner] = nullptr;
+  return ev;
+}
+
+// Enqueue one render of rows (row0 + k*row_step) into d_out on `stream`.
+int enqueue_render(DevCtx& c, const rc_scene* s, int W, int H, int row0, int row_step, int nrows,
+                   const rc_options* opt, uint8_t* d_out, hipStream_t stream, bool timed,
+                   uint32_t* patch, hipEvent_t** evset, const rc_filter* filt) {
+  return ws_frame(c, stream, [] { return 0; }, [&] {
+    return enqueue_render_ws(c, s, W, H, row0, row_step, nrows, opt, d_out, stream, timed, patch,
+                             evset, filt);
+  });
 }
 
 // The one decoding point of rc_options.ssaa = s | (t << 8) (RC_SSAA_ADAPTIVE): s in
@@ -1508,7 +1545,7 @@ int enqueue_render_two_pass(DevCtx& c, const rc_scene* s, int W, int H, int ss, 
   const bool parity = opt->mode == RC_MODE_PARITY && opt->max_recursion > 1;
   if (timed) {
     HIP_TRY(hipEventRecord(ev[parity ? 4 : 1], stream));
-    c.filt_ev = ev;
+    c.span_ev[kSpanFilter] = ev;
     c.filt_end = parity ? 4 : 1;
   }
   return 0;
@@ -1536,11 +1573,11 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
                    "indices)\n", W, H);
       return -1;
     }
-    if (c.aa_list.ensure((size_t)W * H * sizeof(uint32_t)) || c.aa_count.ensure(8)) {
+    if (c.aa_list.ensure((size_t)W * H * sizeof(uint32_t)) || c.aa.count.ensure(8)) {
       std::fprintf(stderr, "Error: out of device memory for the edge list (%d x %d)\n", W, H);
       return -1;
     }
-    if (!c.aa_done) HIP_TRY(hipEventCreateWithFlags(&c.aa_done, hipEventDisableTiming));
+    if (!c.aa.done) HIP_TRY(hipEventCreateWithFlags(&c.aa.done, hipEventDisableTiming));
   }
   if (filt && (ss < 2 || at > 0)) return -1;   // the entry points have refused these
   const bool fused = ss > 1 && at == 0 && opt->mode == RC_MODE_FAST && tune().ssaa_fused && !filt;
@@ -1552,20 +1589,12 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
   unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
   HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
   // the edge list's counter block, here rather than between the render and the list kernel
-  if (at > 0) HIP_TRY(hipMemsetAsync(c.aa_count.p, 0, 8, stream));
+  if (at > 0) HIP_TRY(hipMemsetAsync(c.aa.count.p, 0, 8, stream));
   const int maxrec = opt->max_recursion;
   const bool parity = opt->mode == RC_MODE_PARITY && maxrec > 1;
-  hipEvent_t* ev = c.ev[0];
-  if (c.prof_active) {
-    ev = c.ev[c.prof_calls % DevCtx::kEvSets];
-    c.prof_calls++;
-    c.prof_parity = parity;
-  }
+  // an untimed frame records nothing, so the set's spans stay whose they were
+  hipEvent_t* ev = claim_event_set(c, kSpanOwners, parity, timed);
   if (evset) *evset = ev;
-  if (timed && c.aa_ev == ev) c.aa_ev = nullptr;   // the set is recorded anew (rc_adaptive_phase_ms)
-  if (timed && c.rate_ev == ev) c.rate_ev = nullptr;   // likewise (rc_rate_phase_ms)
-  if (timed && c.filt_ev == ev) c.filt_ev = nullptr;   // likewise (rc_filter_phase_ms)
-  if (timed && c.pat_ev == ev) c.pat_ev = nullptr;     // likewise (rc_pattern_phase_ms)
   if (timed) HIP_TRY(hipEventRecord(ev[0], stream));
   if (!parity) {
     if (fused)   // the subsamples on adjacent lanes, box-filtered in registers
@@ -1575,7 +1604,7 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
       HIP_TRY(rc::launch_render(ls, W, H, row0, row_step, nrows, maxrec, d_out, zc, stream,
                                 opt->mode == RC_MODE_CUDA));
     if (at > 0) {
-      unsigned* cnt = (unsigned*)c.aa_count.p;
+      unsigned* cnt = (unsigned*)c.aa.count.p;
       uint32_t* list = (uint32_t*)c.aa_list.p;
       if (timed) HIP_TRY(hipEventRecord(ev[2], stream));
       HIP_TRY(rc::launch_aa_mark(d_out, W, H, at, list, cnt, stream));
@@ -1583,11 +1612,11 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
       HIP_TRY(rc::launch_aa_refine(ls, W, H, ss, maxrec, list, cnt, d_out, zc,
                                    rc::aa_refine_blocks(W, H, ss, c.cus, tune().adaptive_blocks),
                                    stream, opt->mode == RC_MODE_CUDA));
-      HIP_TRY(hipEventRecord(c.aa_done, stream));
-      c.aa_valid = true;
-      c.aa_ss = ss;
-      c.aa_pixels = (long long)W * H;
-      if (timed) c.aa_ev = ev;
+      HIP_TRY(hipEventRecord(c.aa.done, stream));
+      c.aa.valid = true;
+      c.aa.rays = ss * ss;
+      c.aa.pixels = (long long)W * H;
+      if (timed) c.span_ev[kSpanAdaptive] = ev;
     }
     if (timed) HIP_TRY(hipEventRecord(ev[1], stream));
     return 0;
@@ -1650,16 +1679,17 @@ static int rates_refused(const rc_options* opt, const char* who, int W, int H) {
 // all three are launched.
 static int enqueue_rates(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
                          const uint8_t* d_rates, uint8_t* d_out, hipStream_t stream) {
-  if (flush_phase_c(c, false)) return -1;
-  const size_t entries = (size_t)W * H;
-  if (c.aa_list.ensure(entries * sizeof(uint32_t)) ||
-      c.rate_list.ensure(entries * sizeof(uint32_t)) || c.rate_count.ensure(32)) {
-    std::fprintf(stderr, "Error: out of device memory for the rate lists (%d x %d)\n", W, H);
-    return -1;
-  }
-  if (!c.rate_done) HIP_TRY(hipEventCreateWithFlags(&c.rate_done, hipEventDisableTiming));
-  if (c.ws_valid && c.ws_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, c.ws_ev, 0));
-  auto body = [&]() -> int {
+  auto prepare = [&]() -> int {
+    const size_t entries = (size_t)W * H;
+    if (c.aa_list.ensure(entries * sizeof(uint32_t)) ||
+        c.rate_list.ensure(entries * sizeof(uint32_t)) || c.rate_count.ensure(32)) {
+      std::fprintf(stderr, "Error: out of device memory for the rate lists (%d x %d)\n", W, H);
+      return -1;
+    }
+    if (!c.rate_done) HIP_TRY(hipEventCreateWithFlags(&c.rate_done, hipEventDisableTiming));
+    return 0;
+  };
+  return ws_frame(c, stream, prepare, [&]() -> int {
     rc::LaunchScene ls;
     if (upload_scene(c.fb, stream, s, ls)) return -1;
     unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
@@ -1670,16 +1700,7 @@ static int enqueue_rates(DevCtx& c, const rc_scene* s, int W, int H, const rc_op
     HIP_TRY(hipMemsetAsync(cnt, 0, 32, stream));
     const int maxrec = opt->max_recursion;
     const bool cuda = opt->mode == RC_MODE_CUDA;
-    hipEvent_t* ev = c.ev[0];
-    if (c.prof_active) {
-      ev = c.ev[c.prof_calls % DevCtx::kEvSets];
-      c.prof_calls++;
-      c.prof_parity = false;
-    }
-    if (c.aa_ev == ev) c.aa_ev = nullptr;   // the set is recorded anew (rc_adaptive_phase_ms)
-    if (c.filt_ev == ev) c.filt_ev = nullptr;   // likewise (rc_filter_phase_ms)
-    if (c.pat_ev == ev) c.pat_ev = nullptr;     // likewise (rc_pattern_phase_ms)
-    c.rate_ev = nullptr;
+    hipEvent_t* ev = claim_event_set(c, kSpanRates, false, true);
     // The lists follow the map's row-major order, so over a uniform region entry k is pixel
     // k + const and a wave's static stride (workgroups * 4 waves * pixels per step) that is a
     // multiple of W keeps the wave in one column of the image: the waves whose column crosses
@@ -1703,15 +1724,9 @@ static int enqueue_rates(DevCtx& c, const rc_scene* s, int W, int H, const rc_op
     HIP_TRY(hipEventRecord(c.rate_done, stream));
     HIP_TRY(hipEventRecord(ev[1], stream));
     c.rate_valid = true;
-    c.rate_ev = ev;
+    c.span_ev[kSpanRates] = ev;
     return 0;
-  };
-  const int rc = body();
-  // recorded even after a failed enqueue: whatever was enqueued stays ordered
-  HIP_TRY(hipEventRecord(c.ws_ev, stream));
-  c.ws_stream = stream;
-  c.ws_valid = true;
-  return rc;
+  });
 }
 
 // One pattern frame on `stream` through the device's one-frame workspace (the caller holds c.mu
@@ -1720,34 +1735,26 @@ static int enqueue_rates(DevCtx& c, const rc_scene* s, int W, int H, const rc_op
 // kernel over the list: three launches with no host wait in between.
 static int enqueue_pattern(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
                            const rc_pattern* pat, int at, uint8_t* d_out, hipStream_t stream) {
-  if (flush_phase_c(c, false)) return -1;
-  if (at > 0 && (c.pat_count.ensure(8) || c.aa_list.ensure((size_t)W * H * sizeof(uint32_t)))) {
-    std::fprintf(stderr, "Error: out of device memory for the edge list (%d x %d)\n", W, H);
-    return -1;
-  }
-  if (at > 0 && !c.pat_done)
-    HIP_TRY(hipEventCreateWithFlags(&c.pat_done, hipEventDisableTiming));
-  if (c.ws_valid && c.ws_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, c.ws_ev, 0));
-  auto body = [&]() -> int {
+  auto prepare = [&]() -> int {
+    if (at > 0 && (c.pat.count.ensure(8) || c.aa_list.ensure((size_t)W * H * sizeof(uint32_t)))) {
+      std::fprintf(stderr, "Error: out of device memory for the edge list (%d x %d)\n", W, H);
+      return -1;
+    }
+    if (at > 0 && !c.pat.done)
+      HIP_TRY(hipEventCreateWithFlags(&c.pat.done, hipEventDisableTiming));
+    return 0;
+  };
+  return ws_frame(c, stream, prepare, [&]() -> int {
     rc::LaunchScene ls;
     if (upload_scene(c.fb, stream, s, ls)) return -1;
     unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
-    unsigned* cnt = (unsigned*)c.pat_count.p;
+    unsigned* cnt = (unsigned*)c.pat.count.p;
     uint32_t* list = (uint32_t*)c.aa_list.p;
     HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
     if (at > 0) HIP_TRY(hipMemsetAsync(cnt, 0, 8, stream));
     const int maxrec = opt->max_recursion, g = pat->grid, n = pat->nsamples;
     const bool cuda = opt->mode == RC_MODE_CUDA;
-    hipEvent_t* ev = c.ev[0];
-    if (c.prof_active) {
-      ev = c.ev[c.prof_calls % DevCtx::kEvSets];
-      c.prof_calls++;
-      c.prof_parity = false;
-    }
-    if (c.aa_ev == ev) c.aa_ev = nullptr;   // the set is recorded anew (rc_adaptive_phase_ms)
-    if (c.rate_ev == ev) c.rate_ev = nullptr;   // likewise (rc_rate_phase_ms)
-    if (c.filt_ev == ev) c.filt_ev = nullptr;   // likewise (rc_filter_phase_ms)
-    c.pat_ev = nullptr;
+    hipEvent_t* ev = claim_event_set(c, kSpanPattern, false, true);
     HIP_TRY(hipEventRecord(ev[0], stream));
     if (at == 0) {
       HIP_TRY(rc::launch_pattern(ls, W, H, g, n, pat->x, pat->y, maxrec, d_out, zc, stream, cuda));
@@ -1762,21 +1769,15 @@ static int enqueue_pattern(DevCtx& c, const rc_scene* s, int W, int H, const rc_
     }
     HIP_TRY(hipEventRecord(ev[1], stream));
     // behind the span's end, and only where rc_pattern_stats_get has a count to wait for
-    if (at > 0) HIP_TRY(hipEventRecord(c.pat_done, stream));
-    c.pat_valid = true;
-    c.pat_n = n;
+    if (at > 0) HIP_TRY(hipEventRecord(c.pat.done, stream));
+    c.pat.valid = true;
+    c.pat.rays = n;
     c.pat_t = at;
-    c.pat_pixels = (long long)W * H;
-    c.pat_ev = ev;
+    c.pat.pixels = (long long)W * H;
+    c.span_ev[kSpanPattern] = ev;
     c.pat_ev_listed = at > 0;
     return 0;
-  };
-  const int rc = body();
-  // recorded even after a failed enqueue: whatever was enqueued stays ordered
-  HIP_TRY(hipEventRecord(c.ws_ev, stream));
-  c.ws_stream = stream;
-  c.ws_valid = true;
-  return rc;
+  });
 }
 
 // After a synchronised parity render: the resolver's and phase C's bounded spins set
@@ -2027,6 +2028,89 @@ void fill_device_timing(DevCtx& c, const rc_options* opt, rc_timing* t,
   }
 }
 
+// ------------------------------------------------------- the frame scaffold: tails --
+constexpr long long kNoLog = -1;   // `own` of a frame that logs no hand-off entry
+
+// After the frame's stream has been synchronised: its own latched hand-off words (ring entry
+// `own`).  Its own failure is reported by this call and consumed; another stream's frame that
+// failed meanwhile is left to the next call.
+int own_frame_failed(DevCtx& c, long long own, const rc_options* opt) {
+  const bool failed = c.lone_log.entry_failed(own);
+  c.lone_log.poll();
+  if (!failed) return 0;
+  (void)check_spin_error(c.fb, opt);   // the details, while the workspace still holds them
+  c.lone_log.take(nullptr, nullptr);
+  return -1;
+}
+
+// The tail of a device-resident call: without a timing record it returns with its frame
+// enqueued; with one it waits for the frame.  own (or kNoLog): the frame's entry in lone_log,
+// for the calls whose frame may be a parity frame.
+int finish_device(DevCtx& c, const rc_options* opt, hipStream_t st, rc_timing* timing,
+                  long long own) {
+  if (!timing) return 0;
+  std::memset(timing, 0, sizeof *timing);
+  HIP_TRY(hipStreamSynchronize(st));
+  if (own != kNoLog) {
+    const long long before = c.lone_log.checked;
+    const bool failed = c.lone_log.entry_failed(own);
+    c.lone_log.poll();
+    if (failed) {
+      c.lone_log.take(nullptr, nullptr);
+      return -1;
+    }
+    if (check_spin_error(c.fb, opt)) return -1;
+    timing->frames_checked = c.lone_log.checked - before;
+  }
+  fill_device_timing(c, opt, timing);
+  timing->total_ms = timing->kernel_ms;
+  return 0;
+}
+
+// the frame's counts for rc_timing / raycast()'s stderr lines (those of the s*W x s*H image in a
+// two-pass frame), into pin_tail behind its last kernel
+int enqueue_tail_counts(DevCtx& c, bool parity) {
+  if (!c.pin_tail) HIP_TRY(hipHostMalloc((void**)&c.pin_tail, 64, hipHostMallocDefault));
+  HIP_TRY(hipMemcpyAsync(c.pin_tail, c.fb.zcount.p, 8, hipMemcpyDeviceToHost, c.stream));
+  if (parity)
+    HIP_TRY(hipMemcpyAsync(c.pin_tail + 16, c.fb.counters.p, 16, hipMemcpyDeviceToHost,
+                           c.stream));
+  return 0;
+}
+
+using HostClock = std::chrono::steady_clock;
+
+// the host-side pair of rc_timing: the copy since td, the call since t0
+void stamp_host_ms(rc_timing* t, HostClock::time_point td, HostClock::time_point t0) {
+  if (!t) return;
+  t->d2h_ms = std::chrono::duration<double, std::milli>(HostClock::now() - td).count();
+  t->total_ms = std::chrono::duration<double, std::milli>(HostClock::now() - t0).count();
+}
+
+// The tail of a host-pixmap call whose frame is enqueued on c.stream with its image in c.out:
+// the copy into the caller's pixmap, the wait, the timing record (t0: the call's entry).
+// What the entry points do differently is explicit: tail_counts (the frame's counts through
+// pin_tail rather than two copies after the frame), prefault (the pixmap is faulted in while the
+// GPU renders), own (or kNoLog: the frame's hand-off entry is verified).
+struct HostTail {
+  bool tail_counts, prefault;
+  long long own;
+};
+int finish_host(DevCtx& c, const rc_options* opt, uint8_t* pixmap, size_t bytes,
+                const rc_tuning& tu, const HostTail& how, rc_timing* timing,
+                HostClock::time_point t0) {
+  const bool parity = opt->mode == RC_MODE_PARITY && opt->max_recursion > 1;
+  if (how.tail_counts && enqueue_tail_counts(c, parity)) return -1;
+  if (how.prefault) prefault(c, pixmap, bytes, tu);
+  const auto td = HostClock::now();
+  if (copy_to_host(c, pixmap, (const uint8_t*)c.out.p, bytes, c.stream, tu)) return -1;
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  if (how.own != kNoLog && own_frame_failed(c, how.own, opt)) return -1;
+  fill_device_timing(c, opt, timing, how.tail_counts ? c.pin_tail : nullptr);
+  stamp_host_ms(timing, td, t0);
+  return 0;
+}
+
 }  // namespace rcrt
 
 extern "C" {
@@ -2037,45 +2121,17 @@ int rc_render_device(const rc_scene* s, int W, int H, int row0, int row_step, in
   if (row0 < 0 || (nrows > 0 && row0 + (long long)(nrows - 1) * row_step >= H)) return -1;
   if (ssaa_factor(opt, "rc_render_device") < 0) return -1;
   if (nrows == 0) return 0;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  // an earlier frame of this workspace whose hand-off failed is reported by the next call
-  // (once: the report consumes the counts)
-  if (c->lone_log.earlier_failed()) {
-    c->lone_log.take(nullptr, nullptr);
-    return -1;
-  }
+  Entered e;
+  if (enter(kCurrentDevice, true, e)) return -1;
+  DevCtx* c = e.c;
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   const long long own = c->lone_log.head;   // this frame's ring entry (parity frames log one)
   // the scene upload and events live on the ctx stream: order them with the caller's stream
-  if (st != c->stream) {
-    hipStream_t saved = c->stream;
-    c->stream = st;
-    int rc = enqueue_render(*c, s, W, H, row0, row_step, nrows, opt, d_out, st, true);
-    c->stream = saved;
-    if (rc) return rc;
-  } else if (enqueue_render(*c, s, W, H, row0, row_step, nrows, opt, d_out, st, true)) {
-    return -1;
-  }
-  if (timing) {
-    std::memset(timing, 0, sizeof *timing);
-    HIP_TRY(hipStreamSynchronize(st));
-    const long long before = c->lone_log.checked;
-    const bool failed = c->lone_log.entry_failed(own);
-    c->lone_log.poll();
-    if (failed) {
-      c->lone_log.take(nullptr, nullptr);
-      return -1;
-    }
-    if (check_spin_error(c->fb, opt)) return -1;
-    timing->frames_checked = c->lone_log.checked - before;
-    fill_device_timing(*c, opt, timing);
-    timing->total_ms = timing->kernel_ms;
-  }
-  return 0;
+  hipStream_t saved = c->stream;
+  c->stream = st;
+  const int rc = enqueue_render(*c, s, W, H, row0, row_step, nrows, opt, d_out, st, true);
+  c->stream = saved;
+  return rc ? -1 : finish_device(*c, opt, st, timing, own);
 }
 
 int rc_render_rates_device(const rc_scene* s, int W, int H, const rc_options* opt,
@@ -2087,25 +2143,11 @@ int rc_render_rates_device(const rc_scene* s, int W, int H, const rc_options* op
   }
   if (W <= 0 || H <= 0) return -1;
   if (rates_refused(opt, "rc_render_rates_device", W, H)) return -1;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  // an earlier frame of this workspace whose hand-off failed is reported by the next call
-  if (c->lone_log.earlier_failed()) {
-    c->lone_log.take(nullptr, nullptr);
-    return -1;
-  }
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-  if (enqueue_rates(*c, s, W, H, opt, d_rates, d_out, st)) return -1;
-  if (timing) {
-    std::memset(timing, 0, sizeof *timing);
-    HIP_TRY(hipStreamSynchronize(st));
-    fill_device_timing(*c, opt, timing);
-    timing->total_ms = timing->kernel_ms;
-  }
-  return 0;
+  Entered e;
+  if (enter(kCurrentDevice, true, e)) return -1;
+  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
+  if (enqueue_rates(*e.c, s, W, H, opt, d_rates, d_out, st)) return -1;
+  return finish_device(*e.c, opt, st, timing, kNoLog);
 }
 
 int rc_render_rates(const rc_scene* s, int W, int H, const rc_options* opt, const uint8_t* rates,
@@ -2115,7 +2157,7 @@ int rc_render_rates(const rc_scene* s, int W, int H, const rc_options* opt, cons
     return -1;
   }
   if (W <= 0 || H <= 0) return -1;
-  auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = HostClock::now();
   if (rates_refused(opt, "rc_render_rates", W, H)) return -1;
   const size_t pixels = (size_t)W * H;
   for (size_t i = 0; i < pixels; ++i) {
@@ -2128,19 +2170,9 @@ int rc_render_rates(const rc_scene* s, int W, int H, const rc_options* opt, cons
   }
   if (timing) std::memset(timing, 0, sizeof *timing);
   const rc_tuning tu = tune();
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (opt->device < 0 || opt->device >= ndev) {
-    std::fprintf(stderr, "Error: device %d not available (%d devices)\n", opt->device, ndev);
-    return -1;
-  }
-  DevCtx* c;
-  if (hipSetDevice(opt->device) != hipSuccess || ctx_get(opt->device, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (c->lone_log.earlier_failed()) {
-    c->lone_log.take(nullptr, nullptr);
-    return -1;
-  }
+  Entered e;
+  if (enter_host(opt, e)) return -1;
+  DevCtx* c = e.c;
   if (c->out.ensure(pixels * 3) || c->rate_map.ensure(pixels)) {
     std::fprintf(stderr, "Error: out of device memory for the image and its rate map (%d x %d)\n",
                  W, H);
@@ -2152,17 +2184,7 @@ int rc_render_rates(const rc_scene* s, int W, int H, const rc_options* opt, cons
   HIP_TRY(hipMemcpyAsync(d_rates, rates, pixels, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d_out, pixmap, pixels * 3, hipMemcpyHostToDevice, c->stream));
   if (enqueue_rates(*c, s, W, H, opt, d_rates, d_out, c->stream)) return -1;
-  auto td = std::chrono::steady_clock::now();
-  if (copy_to_host(*c, pixmap, d_out, pixels * 3, c->stream, tu)) return -1;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  fill_device_timing(*c, opt, timing);
-  if (timing) {
-    timing->d2h_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
-    timing->total_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return 0;
+  return finish_host(*c, opt, pixmap, pixels * 3, tu, {false, false, kNoLog}, timing, t0);
 }
 
 int rc_render_pattern_device(const rc_scene* s, int W, int H, const rc_options* opt,
@@ -2173,25 +2195,11 @@ int rc_render_pattern_device(const rc_scene* s, int W, int H, const rc_options* 
     return -1;
   }
   if (pattern_refused("rc_render_pattern_device", opt, W, H, pat, threshold)) return -1;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  // an earlier frame of this workspace whose hand-off failed is reported by the next call
-  if (c->lone_log.earlier_failed()) {
-    c->lone_log.take(nullptr, nullptr);
-    return -1;
-  }
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-  if (enqueue_pattern(*c, s, W, H, opt, pat, threshold, d_out, st)) return -1;
-  if (timing) {
-    std::memset(timing, 0, sizeof *timing);
-    HIP_TRY(hipStreamSynchronize(st));
-    fill_device_timing(*c, opt, timing);
-    timing->total_ms = timing->kernel_ms;
-  }
-  return 0;
+  Entered e;
+  if (enter(kCurrentDevice, true, e)) return -1;
+  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
+  if (enqueue_pattern(*e.c, s, W, H, opt, pat, threshold, d_out, st)) return -1;
+  return finish_device(*e.c, opt, st, timing, kNoLog);
 }
 
 int rc_render_pattern(const rc_scene* s, int W, int H, const rc_options* opt,
@@ -2200,41 +2208,20 @@ int rc_render_pattern(const rc_scene* s, int W, int H, const rc_options* opt,
     std::fprintf(stderr, "Error: rc_render_pattern: a null pointer\n");
     return -1;
   }
-  auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = HostClock::now();
   if (pattern_refused("rc_render_pattern", opt, W, H, pat, threshold)) return -1;
   if (timing) std::memset(timing, 0, sizeof *timing);
   const rc_tuning tu = tune();
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (opt->device < 0 || opt->device >= ndev) {
-    std::fprintf(stderr, "Error: device %d not available (%d devices)\n", opt->device, ndev);
-    return -1;
-  }
-  DevCtx* c;
-  if (hipSetDevice(opt->device) != hipSuccess || ctx_get(opt->device, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (c->lone_log.earlier_failed()) {
-    c->lone_log.take(nullptr, nullptr);
-    return -1;
-  }
+  Entered e;
+  if (enter_host(opt, e)) return -1;
+  DevCtx* c = e.c;
   const size_t bytes = (size_t)W * H * 3;
   if (c->out.ensure(bytes)) {
     std::fprintf(stderr, "Error: out of device memory for the image (%d x %d)\n", W, H);
     return -1;
   }
-  uint8_t* d_out = (uint8_t*)c->out.p;
-  if (enqueue_pattern(*c, s, W, H, opt, pat, threshold, d_out, c->stream)) return -1;
-  auto td = std::chrono::steady_clock::now();
-  if (copy_to_host(*c, pixmap, d_out, bytes, c->stream, tu)) return -1;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  fill_device_timing(*c, opt, timing);
-  if (timing) {
-    timing->d2h_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
-    timing->total_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return 0;
+  if (enqueue_pattern(*c, s, W, H, opt, pat, threshold, (uint8_t*)c->out.p, c->stream)) return -1;
+  return finish_host(*c, opt, pixmap, bytes, tu, {false, false, kNoLog}, timing, t0);
 }
 
 int rc_render_filtered_device(const rc_scene* s, int W, int H, const rc_options* opt,
@@ -2245,38 +2232,16 @@ int rc_render_filtered_device(const rc_scene* s, int W, int H, const rc_options*
     return -1;
   }
   if (filtered_refused("rc_render_filtered_device", opt, W, H, f) < 0) return -1;
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (c->lone_log.earlier_failed()) {   // as rc_render_device
-    c->lone_log.take(nullptr, nullptr);
-    return -1;
-  }
+  Entered e;
+  if (enter(kCurrentDevice, true, e)) return -1;
+  DevCtx* c = e.c;
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   const long long own = c->lone_log.head;
   hipStream_t saved = c->stream;   // the scene upload and events follow the caller's stream
   c->stream = st;
   const int rc = enqueue_render(*c, s, W, H, 0, 1, H, opt, d_out, st, true, nullptr, nullptr, f);
   c->stream = saved;
-  if (rc) return -1;
-  if (timing) {
-    std::memset(timing, 0, sizeof *timing);
-    HIP_TRY(hipStreamSynchronize(st));
-    const long long before = c->lone_log.checked;
-    const bool failed = c->lone_log.entry_failed(own);
-    c->lone_log.poll();
-    if (failed) {
-      c->lone_log.take(nullptr, nullptr);
-      return -1;
-    }
-    if (check_spin_error(c->fb, opt)) return -1;
-    timing->frames_checked = c->lone_log.checked - before;
-    fill_device_timing(*c, opt, timing);
-    timing->total_ms = timing->kernel_ms;
-  }
-  return 0;
+  return rc ? -1 : finish_device(*c, opt, st, timing, own);
 }
 
 int rc_render_filtered(const rc_scene* s, int W, int H, const rc_options* opt, const rc_filter* f,
@@ -2285,55 +2250,20 @@ int rc_render_filtered(const rc_scene* s, int W, int H, const rc_options* opt, c
     std::fprintf(stderr, "Error: rc_render_filtered: a null pointer\n");
     return -1;
   }
-  auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = HostClock::now();
   if (filtered_refused("rc_render_filtered", opt, W, H, f) < 0) return -1;
   if (timing) std::memset(timing, 0, sizeof *timing);
   const rc_tuning tu = tune();
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (opt->device < 0 || opt->device >= ndev) {
-    std::fprintf(stderr, "Error: device %d not available (%d devices)\n", opt->device, ndev);
-    return -1;
-  }
-  DevCtx* c;
-  if (hipSetDevice(opt->device) != hipSuccess || ctx_get(opt->device, &c)) return -1;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (c->lone_log.earlier_failed()) {   // as rc_render
-    c->lone_log.take(nullptr, nullptr);
-    return -1;
-  }
+  Entered e;
+  if (enter_host(opt, e)) return -1;
+  DevCtx* c = e.c;
   const size_t bytes = (size_t)W * H * 3;
   if (c->out.ensure(bytes)) return -1;
-  uint8_t* d_out = (uint8_t*)c->out.p;
-  const bool parity = opt->mode == RC_MODE_PARITY && opt->max_recursion > 1;
   const long long own = c->lone_log.head;
-  if (enqueue_render(*c, s, W, H, 0, 1, H, opt, d_out, c->stream, true, nullptr, nullptr, f))
+  if (enqueue_render(*c, s, W, H, 0, 1, H, opt, (uint8_t*)c->out.p, c->stream, true, nullptr,
+                     nullptr, f))
     return -1;
-  // the frame's counts (those of the s*W x s*H image), behind its last kernel
-  if (!c->pin_tail) HIP_TRY(hipHostMalloc((void**)&c->pin_tail, 64, hipHostMallocDefault));
-  HIP_TRY(hipMemcpyAsync(c->pin_tail, c->fb.zcount.p, 8, hipMemcpyDeviceToHost, c->stream));
-  if (parity)
-    HIP_TRY(hipMemcpyAsync(c->pin_tail + 16, c->fb.counters.p, 16, hipMemcpyDeviceToHost,
-                           c->stream));
-  prefault(*c, pixmap, bytes, tu);
-  auto td = std::chrono::steady_clock::now();
-  if (copy_to_host(*c, pixmap, d_out, bytes, c->stream, tu)) return -1;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->lone_log.entry_failed(own)) {
-    c->lone_log.poll();
-    (void)check_spin_error(c->fb, opt);
-    c->lone_log.take(nullptr, nullptr);
-    return -1;
-  }
-  c->lone_log.poll();
-  fill_device_timing(*c, opt, timing, c->pin_tail);
-  if (timing) {
-    timing->d2h_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
-    timing->total_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return 0;
+  return finish_host(*c, opt, pixmap, bytes, tu, {true, true, own}, timing, t0);
 }
 
 int rc_filter_image_device(const uint8_t* d_src, int W, int H, int s, const rc_filter* f,
@@ -2885,12 +2815,8 @@ int rc_render(const rc_scene* s, int W, int H, const rc_options* opt, uint8_t* p
   const int at = ssaa_threshold(opt, "rc_render");
   if (at > 0 && adaptive_refused(opt, "rc_render", ss, at)) return -1;
   int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device_available(opt, &ndev)) return -1;
   int G = opt->num_gpus;
-  if (opt->device < 0 || opt->device >= ndev) {
-    std::fprintf(stderr, "Error: device %d not available (%d devices)\n", opt->device, ndev);
-    return -1;
-  }
   // share_device: every rank on opt->device (device copies between the ranks: tests of the
   // multi-GPU entry on a one-GPU box); otherwise one device per rank
   const int avail = tu.share_device ? rc::kMaxShards : ndev - opt->device;
@@ -2917,35 +2843,21 @@ int rc_render(const rc_scene* s, int W, int H, const rc_options* opt, uint8_t* p
     rc_timing tg;
     if (render_local_group(opt->device, G, tu.share_device != 0, s, W, H, opt, &d_image, &tg))
       return -1;
-    DevCtx* c;
-    if (hipSetDevice(opt->device) != hipSuccess || ctx_get(opt->device, &c)) return -1;
-    std::lock_guard<std::mutex> lk(c->mu);
+    Entered e;
+    if (enter(opt->device, false, e)) return -1;
+    DevCtx* c = e.c;
     prefault(*c, pixmap, (size_t)H * row_bytes, tu);
     auto td = std::chrono::steady_clock::now();
     if (copy_to_host(*c, pixmap, d_image, (size_t)H * row_bytes, c->stream, tu)) return -1;
-    if (timing) {
-      *timing = tg;
-      timing->d2h_ms =
-          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
-      timing->total_ms =
-          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
+    if (timing) *timing = tg;
+    stamp_host_ms(timing, td, t0);
     g_last_kernel_ms = tg.resolve_ms > 0.0 ? tg.resolve_ms : tg.kernel_ms;
     return 0;
   }
   // one device
-  const int dev = opt->device;
-  DevCtx* c;
-  if (hipSetDevice(dev) != hipSuccess || ctx_get(dev, &c)) return -1;
-  // the lock covers the workspace from its (re)allocation on: a concurrent caller's ensure()
-  // could otherwise free the buffer another caller is rendering into
-  std::lock_guard<std::mutex> lk(c->mu);
-  // an earlier frame's failure (rc_render_device on another stream) is reported before this
-  // frame is enqueued, as rc_render_device does, so the result below is this frame's own
-  if (c->lone_log.earlier_failed()) {
-    c->lone_log.take(nullptr, nullptr);
-    return -1;
-  }
+  Entered e;
+  if (enter(opt->device, true, e)) return -1;
+  DevCtx* c = e.c;
   if (c->out.ensure((size_t)H * row_bytes)) return -1;
   uint8_t* d_out = (uint8_t*)c->out.p;
   // parity: the copy overlaps the resolver (copy_overlapped); split shading leaves the non-DEP
@@ -2983,12 +2895,7 @@ int rc_render(const rc_scene* s, int W, int H, const rc_options* opt, uint8_t* p
     std::fprintf(stderr, "Error: rc_render: frame epoch %u, expected %u\n", c->fb.epoch, epoch);
     return -1;
   }
-  // the frame's counts for rc_timing / raycast()'s stderr lines, behind its last kernel
-  if (!c->pin_tail) HIP_TRY(hipHostMalloc((void**)&c->pin_tail, 64, hipHostMallocDefault));
-  HIP_TRY(hipMemcpyAsync(c->pin_tail, c->fb.zcount.p, 8, hipMemcpyDeviceToHost, c->stream));
-  if (parity)
-    HIP_TRY(hipMemcpyAsync(c->pin_tail + 16, c->fb.counters.p, 16, hipMemcpyDeviceToHost,
-                           c->stream));
+  if (enqueue_tail_counts(*c, parity)) return -1;
   trace.mark(0);
   prefault(*c, pixmap, (size_t)H * row_bytes, tu);
   trace.mark(1);
@@ -3000,26 +2907,11 @@ int rc_render(const rc_scene* s, int W, int H, const rc_options* opt, uint8_t* p
   } else if (copy_to_host(*c, pixmap, d_out, (size_t)H * row_bytes, c->stream, tu)) {
     return -1;
   }
-  // this frame's latched hand-off words: its own failure is reported by this call and
-  // consumed; another stream's frame that failed meanwhile is left to the next call
   HIP_TRY(hipStreamSynchronize(c->stream));
   trace.mark(6);
-  if (c->lone_log.entry_failed(own)) {
-    c->lone_log.poll();
-    (void)check_spin_error(c->fb, opt);   // the details, while the workspace still holds them
-    c->lone_log.take(nullptr, nullptr);
-    return -1;
-  }
-  c->lone_log.poll();
-  if (timing) {
-    fill_device_timing(*c, opt, timing, c->pin_tail);
-    timing->d2h_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
-    timing->total_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  } else {
-    fill_device_timing(*c, opt, nullptr, c->pin_tail);
-  }
+  if (own_frame_failed(*c, own, opt)) return -1;
+  fill_device_timing(*c, opt, timing, c->pin_tail);
+  stamp_host_ms(timing, td, t0);
   trace.mark(7);
   trace.print();
   return 0;

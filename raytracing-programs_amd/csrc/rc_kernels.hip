@@ -33,6 +33,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "rc_cudasem.hpp"
 #include "rc_device.hpp"
@@ -276,6 +277,45 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
   }, nx * 3);
 }
 
+// ---------------------------------------- one subsample, for the supersampling kernels --
+// The quantised channels of subsample (xs, ys) of the image whose camera is `cam`, in fast
+// mode's arithmetic or (kCuda) the CUDA port's (k_render_cuda's pixel routine), packed for the
+// sums below: R | G << 16 and B (a channel's sum over a wave is <= 64 * 255).
+template <bool kCuda>
+__device__ __forceinline__ void sample_shoot(const Scene& sc, const Cam& cam, int xs, int ys,
+                                             int maxrec, unsigned long long* __restrict__ zcount,
+                                             unsigned& rg, unsigned& b) {
+  V3 c;
+  if constexpr (kCuda) {
+    c = cusem::render_pixel(sc, cam, xs, ys, maxrec - 1);
+  } else {
+    int zero = 0;
+    const V3 d = primary_dir(cam, xs, ys, zero);
+    PixelOut po;
+    shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
+    c = po.rgb;
+    flush_events(zero, zcount);
+  }
+  rg = (unsigned)quant(c.x) | ((unsigned)quant(c.y) << 16);
+  b = quant(c.z);
+}
+// The sums over the 1 << ln lanes of a group (xor butterflies over the lane bits 1 .. n/2).
+// Called by every lane of the wave.
+__device__ __forceinline__ void sample_reduce(unsigned& rg, unsigned& b, int ln) {
+  for (int m = 1; m < (1 << ln); m <<= 1) {
+    rg += __shfl_xor(rg, m, 64);
+    b += __shfl_xor(b, m, 64);
+  }
+}
+// The rounded mean of 1 << ln samples, (sum + n/2) >> ln per channel, stored at q.
+__device__ __forceinline__ void sample_store(uint8_t* __restrict__ q, unsigned rg, unsigned b,
+                                             int ln) {
+  const unsigned half = 1u << (ln - 1);
+  q[0] = (uint8_t)(((rg & 0xffffu) + half) >> ln);
+  q[1] = (uint8_t)(((rg >> 16) + half) >> ln);
+  q[2] = (uint8_t)((b + half) >> ln);
+}
+
 // ------------------------------------------------- fast mode, supersampled (ssaa) --
 // k_render over the subsample grid of an s x s supersampled image (s = 1 << ls; 2, 4 or 8):
 // one lane shoots one subsample with the camera of the s*W x s*H image, the same tiles as
@@ -513,35 +553,16 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
       p = list[k];
       const int xs = (int)((p % (unsigned)W) << ls) + (int)(sub & ((1u << ls) - 1u));
       const int ys = (int)((p / (unsigned)W) << ls) + (int)(sub >> ls);
-      V3 c;
-      if constexpr (kCuda) {
-        c = cusem::render_pixel(sc, cam, xs, ys, maxrec - 1);
-      } else {
-        int zero = 0;
-        const V3 d = primary_dir(cam, xs, ys, zero);
-        PixelOut po;
-        shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
-        c = po.rgb;
-        flush_events(zero, zcount);
-      }
-      rg = (unsigned)quant(c.x) | ((unsigned)quant(c.y) << 16);
-      b = quant(c.z);
+      sample_shoot<kCuda>(sc, cam, xs, ys, maxrec, zcount, rg, b);
     }
-    for (int m = 1; m < (1 << (2 * ls)); m <<= 1) {
-      rg += __shfl_xor(rg, m, 64);
-      b += __shfl_xor(b, m, 64);
-    }
+    sample_reduce(rg, b, 2 * ls);
     if (live && sub == 0u) {
       // the entry is read again (opaque index) rather than kept in a register across shoot,
       // where the kernel sits at the 128-register edge
       unsigned g = (unsigned)lane >> (2 * ls);
       asm volatile("" : "+v"(g));
       p = list[first + g];
-      const unsigned half = 1u << (2 * ls - 1);
-      uint8_t* q = out + (size_t)p * 3;
-      q[0] = (uint8_t)(((rg & 0xffffu) + half) >> (2 * ls));
-      q[1] = (uint8_t)(((rg >> 16) + half) >> (2 * ls));
-      q[2] = (uint8_t)((b + half) >> (2 * ls));
+      sample_store(out + (size_t)p * 3, rg, b, 2 * ls);
     }
   }
 }
@@ -739,39 +760,6 @@ struct PatWords {
 __device__ __forceinline__ int pat_entry(unsigned long long word, unsigned k) {
   return (int)((word >> (4u * k)) & 15ull);
 }
-// One sample's quantised channels: the subsample (xs, ys) of the g*W x g*H image.
-template <bool kCuda>
-__device__ __forceinline__ void pat_shoot(const Scene& sc, const Cam& cam, int xs, int ys,
-                                          int maxrec, unsigned long long* __restrict__ zcount,
-                                          unsigned& rg, unsigned& b) {
-  V3 c;
-  if constexpr (kCuda) {
-    c = cusem::render_pixel(sc, cam, xs, ys, maxrec - 1);
-  } else {
-    int zero = 0;
-    const V3 d = primary_dir(cam, xs, ys, zero);
-    PixelOut po;
-    shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
-    c = po.rgb;
-    flush_events(zero, zcount);
-  }
-  rg = (unsigned)quant(c.x) | ((unsigned)quant(c.y) << 16);
-  b = quant(c.z);
-}
-// Called by every lane of the wave.
-__device__ __forceinline__ void pat_reduce(unsigned& rg, unsigned& b, int ln) {
-  for (int m = 1; m < (1 << ln); m <<= 1) {
-    rg += __shfl_xor(rg, m, 64);
-    b += __shfl_xor(b, m, 64);
-  }
-}
-__device__ __forceinline__ void pat_store(uint8_t* __restrict__ q, unsigned rg, unsigned b,
-                                          int ln) {
-  const unsigned half = 1u << (ln - 1);
-  q[0] = (uint8_t)(((rg & 0xffffu) + half) >> ln);
-  q[1] = (uint8_t)(((rg >> 16) + half) >> ln);
-  q[2] = (uint8_t)((b + half) >> ln);
-}
 
 // The wave block of the dense form: a wave's 64 / n pixels are a compact bw x bh block,
 //   n = 2: 8 x 4    n = 4: 4 x 4    n = 8: 4 x 2    n = 16: 2 x 2     (bw >= bh, both powers of two)
@@ -806,10 +794,10 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
   const bool inside = x < W && y < H;
   unsigned rg = 0u, b = 0u;
   if (inside)
-    pat_shoot<kCuda>(sc, cam, (x << lg) + pat_entry(pat.x, k), (y << lg) + pat_entry(pat.y, k),
+    sample_shoot<kCuda>(sc, cam, (x << lg) + pat_entry(pat.x, k), (y << lg) + pat_entry(pat.y, k),
                      maxrec, zcount, rg, b);
-  pat_reduce(rg, b, ln);
-  if (inside && k == 0u) pat_store(out + ((size_t)y * W + x) * 3, rg, b, ln);
+  sample_reduce(rg, b, ln);
+  if (inside && k == 0u) sample_store(out + ((size_t)y * W + x) * 3, rg, b, ln);
 }
 
 // List form (threshold t > 0): over k_aa_mark's list like k_aa_refine, 64 / n listed pixels per
@@ -840,16 +828,16 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
     unsigned rg = 0u, b = 0u;
     if (live) {
       const unsigned p = list[e];
-      pat_shoot<kCuda>(sc, cam, (int)((p % (unsigned)W) << lg) + px,
+      sample_shoot<kCuda>(sc, cam, (int)((p % (unsigned)W) << lg) + px,
                        (int)((p / (unsigned)W) << lg) + py, maxrec, zcount, rg, b);
     }
-    pat_reduce(rg, b, ln);
+    sample_reduce(rg, b, ln);
     if (live && k == 0u) {
       // the entry is read again (opaque index) rather than kept in a register across shoot, as
       // in k_aa_refine
       unsigned g = (unsigned)lane >> ln;
       asm volatile("" : "+v"(g));
-      pat_store(out + (size_t)list[first + g] * 3, rg, b, ln);
+      sample_store(out + (size_t)list[first + g] * 3, rg, b, ln);
     }
   }
 }
@@ -3583,18 +3571,37 @@ static Cam make_cam(const LaunchScene& s, int W, int H) {
   return c;
 }
 
+// The launchers' runtime flags as the kernels' template flags: fn(st) or fn(cuda, st) with
+// std::bool_constant arguments, so a launcher names its kernel once as k<cuda.value, st.value>.
+// cuda_sem is the outer branch: kernels are emitted in the order they are instantiated, and
+// <true, true>, <true, false>, <false, true>, <false, false> keeps the code object's layout as
+// it has been measured.
+template <class Fn>
+static void dispatch(bool st, Fn fn) {
+  st ? fn(std::true_type{}) : fn(std::false_type{});
+}
+template <class Fn>
+static void dispatch(bool cuda_sem, bool st, Fn fn) {
+  if (cuda_sem)
+    dispatch(st, [&](auto s) { fn(std::true_type{}, s); });
+  else
+    dispatch(st, [&](auto s) { fn(std::false_type{}, s); });
+}
+
 hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_step, int nrows,
                          int maxrec, uint8_t* out, unsigned long long* zcount,
                          hipStream_t stream, bool cuda_sem) {
   dim3 grid((W + kTileW - 1) / kTileW, (nrows + kTileH - 1) / kTileH);
-  if (cuda_sem) {
-    hipLaunchKernelGGL(stage_fits(s) ? k_render_cuda<true> : k_render_cuda<false>, grid,
-                       dim3(kBlock), 0, stream, make_scene(s), make_cam(s, W, H), W, row0,
-                       row_step, nrows, maxrec, out);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(stage_fits(s) ? k_render<true> : k_render<false>, grid, dim3(kBlock), 0, stream, make_scene(s), make_cam(s, W, H),
-                     W, H, row0, row_step, nrows, maxrec, out, zcount);
+  if (cuda_sem)
+    dispatch(stage_fits(s), [&](auto st) {
+      hipLaunchKernelGGL(k_render_cuda<st.value>, grid, dim3(kBlock), 0, stream, make_scene(s),
+                         make_cam(s, W, H), W, row0, row_step, nrows, maxrec, out);
+    });
+  else
+    dispatch(stage_fits(s), [&](auto st) {
+      hipLaunchKernelGGL(k_render<st.value>, grid, dim3(kBlock), 0, stream, make_scene(s),
+                         make_cam(s, W, H), W, H, row0, row_step, nrows, maxrec, out, zcount);
+    });
   return hipGetLastError();
 }
 
@@ -3609,9 +3616,11 @@ hipError_t launch_render_ssaa(const LaunchScene& s, int W, int H, int ssaa, int 
   const int sw = W * ssaa, sr = nrows * ssaa;
   dim3 grid((sw + kTileW - 1) / kTileW, (sr + kTileH - 1) / kTileH);
   if (grid.y > 65535u) return hipErrorInvalidValue;   // grid.y of k_render's tile layout
-  hipLaunchKernelGGL(stage_fits(s) ? k_render_ssaa<true> : k_render_ssaa<false>, grid,
-                     dim3(kBlock), 0, stream, make_scene(s), make_cam(s, sw, H * ssaa), W, ls, row0,
-                     row_step, nrows, maxrec, out, zcount);
+  dispatch(stage_fits(s), [&](auto st) {
+    hipLaunchKernelGGL(k_render_ssaa<st.value>, grid, dim3(kBlock), 0, stream, make_scene(s),
+                       make_cam(s, sw, H * ssaa), W, ls, row0, row_step, nrows, maxrec, out,
+                       zcount);
+  });
   return hipGetLastError();
 }
 
@@ -3662,15 +3671,10 @@ hipError_t launch_aa_refine(const LaunchScene& s, int W, int H, int ssaa, int ma
     return hipErrorInvalidValue;
   const Scene sc = make_scene(s);
   const Cam cam = make_cam(s, W * ssaa, H * ssaa);   // the camera of the s*W x s*H image
-  const bool st = stage_fits(s);
-  auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, sc, cam, W, ls,
-                       maxrec, list, count, out, zcount);
-  };
-  if (cuda_sem)
-    st ? go(k_aa_refine<true, true>) : go(k_aa_refine<true, false>);
-  else
-    st ? go(k_aa_refine<false, true>) : go(k_aa_refine<false, false>);
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_aa_refine<cuda.value, st.value>), dim3((unsigned)blocks), dim3(kBlock),
+                       0, stream, sc, cam, W, ls, maxrec, list, count, out, zcount);
+  });
   return hipGetLastError();
 }
 
@@ -3689,15 +3693,11 @@ hipError_t launch_rates_render(const LaunchScene& s, int W, int H, int maxrec,
   dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
   const Scene sc = make_scene(s);
   const Cam cam = make_cam(s, W, H);
-  const bool st = stage_fits(s);
-  auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, stream, sc, cam, W, H, maxrec, rates, out,
-                       list28, list4, list28 + ((size_t)W * H - 1), cnt, zcount);
-  };
-  if (cuda_sem)
-    st ? go(k_rates_render<true, true>) : go(k_rates_render<true, false>);
-  else
-    st ? go(k_rates_render<false, true>) : go(k_rates_render<false, false>);
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_rates_render<cuda.value, st.value>), grid, dim3(kBlock), 0, stream, sc,
+                       cam, W, H, maxrec, rates, out, list28, list4,
+                       list28 + ((size_t)W * H - 1), cnt, zcount);
+  });
   return hipGetLastError();
 }
 
@@ -3708,16 +3708,11 @@ hipError_t launch_rates_refine8(const LaunchScene& s, int W, int H, int maxrec,
   if (!rates_supported(W, H) || blocks < 1 || blocks > 4096) return hipErrorInvalidValue;
   const Scene sc = make_scene(s);
   const Cam cam = make_cam(s, W * 8, H * 8);   // the camera of the 8*W x 8*H image
-  const bool st = stage_fits(s);
   const uint32_t* last = list28 + ((size_t)W * H - 1);
-  auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, sc, cam, W,
-                       maxrec, last, count, out, zcount);
-  };
-  if (cuda_sem)
-    st ? go(k_rates_refine8<true, true>) : go(k_rates_refine8<true, false>);
-  else
-    st ? go(k_rates_refine8<false, true>) : go(k_rates_refine8<false, false>);
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_rates_refine8<cuda.value, st.value>), dim3((unsigned)blocks),
+                       dim3(kBlock), 0, stream, sc, cam, W, maxrec, last, count, out, zcount);
+  });
   return hipGetLastError();
 }
 
@@ -3764,15 +3759,10 @@ hipError_t launch_pattern(const LaunchScene& s, int W, int H, int g, int n, cons
   const Scene sc = make_scene(s);
   const Cam cam = make_cam(s, W * g, H * g);   // the camera of the g*W x g*H image
   const PatWords pat = pattern_words(n, px, py);
-  const bool st = stage_fits(s);
-  auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, stream, sc, cam, W, H, lg, ln, pat, maxrec,
-                       out, zcount);
-  };
-  if (cuda_sem)
-    st ? go(k_pattern<true, true>) : go(k_pattern<true, false>);
-  else
-    st ? go(k_pattern<false, true>) : go(k_pattern<false, false>);
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_pattern<cuda.value, st.value>), grid, dim3(kBlock), 0, stream, sc, cam,
+                       W, H, lg, ln, pat, maxrec, out, zcount);
+  });
   return hipGetLastError();
 }
 
@@ -3787,15 +3777,11 @@ hipError_t launch_pattern_list(const LaunchScene& s, int W, int H, int g, int n,
   const Scene sc = make_scene(s);
   const Cam cam = make_cam(s, W * g, H * g);   // the camera of the g*W x g*H image
   const PatWords pat = pattern_words(n, px, py);
-  const bool st = stage_fits(s);
-  auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, sc, cam, W, lg, ln,
-                       pat, maxrec, list, count, out, zcount);
-  };
-  if (cuda_sem)
-    st ? go(k_pattern_list<true, true>) : go(k_pattern_list<true, false>);
-  else
-    st ? go(k_pattern_list<false, true>) : go(k_pattern_list<false, false>);
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_pattern_list<cuda.value, st.value>), dim3((unsigned)blocks),
+                       dim3(kBlock), 0, stream, sc, cam, W, lg, ln, pat, maxrec, list, count, out,
+                       zcount);
+  });
   return hipGetLastError();
 }
 

@@ -160,6 +160,20 @@ struct Pipe {
   unsigned long long* cdefer_zc = nullptr;
 };
 
+// The sampling features whose frames leave phase spans behind (DevCtx::span_ev).
+enum SpanOwner { kSpanAdaptive, kSpanRates, kSpanFilter, kSpanPattern, kSpanOwners };
+
+// The last list-refined frame of one feature on a device (adaptive supersampling, a pattern
+// frame with a threshold): what its stats getter reads.
+struct ListFrame {
+  DevBuf count;                // 8-byte counter block (word 0: entries), zeroed on the frame's
+                               // stream before the list is made
+  hipEvent_t done = nullptr;   // behind the frame's refinement
+  bool valid = false;          // such a frame has been enqueued on this device
+  long long pixels = 0;        // its W*H
+  int rays = 0;                // rays per refined pixel
+};
+
 struct DevCtx {
   bool init = false;
   int device = 0;
@@ -180,15 +194,10 @@ struct DevCtx {
   int prof_active = 0, prof_calls = 0, prof_parity = 0;
   DevBuf out;          // rc_render output pixmap
   DevBuf ssaa;         // two-pass supersampling: the s*W x s*H image before the box filter
-  // adaptive supersampling: the edge list (uint32 pixel index, W*H entries of room) and its
-  // 8-byte counter block (word 0: entries), zeroed on the frame's stream before the list is made
-  DevBuf aa_list, aa_count;
-  hipEvent_t aa_done = nullptr;      // behind the last adaptive frame's refinement
-  bool aa_valid = false;             // an adaptive frame has been enqueued on this device
-  int aa_ss = 0;                     // its factor and pixels (rc_adaptive_stats_get)
-  long long aa_pixels = 0;
-  hipEvent_t* aa_ev = nullptr;       // the event set of the last timed adaptive frame:
-                                     // [0] start, [2] one-ray image, [3] list, [1] refinement
+  // adaptive supersampling: the edge list (uint32 pixel index, W*H entries of room); its frame
+  // record is `aa`
+  DevBuf aa_list;
+  ListFrame aa;
   // rate-map supersampling (rc_render_rates*): the rate-4 list lives in aa_list; rate_list holds
   // the rate-2 list (upwards from its start) and the rate-8 list (downwards from its end), W*H
   // entries; rate_count is the counter block (five words, launch_rates_render), zeroed on the
@@ -196,25 +205,22 @@ struct DevCtx {
   DevBuf rate_list, rate_count, rate_map;
   hipEvent_t rate_done = nullptr;    // behind the last rate-map frame's refinement
   bool rate_valid = false;           // a rate-map frame has been enqueued on this device
-  hipEvent_t* rate_ev = nullptr;     // the event set of the last timed rate-map frame:
-                                     // [0] start, [2] the rate-1 pass, [1] the refinement
   // sparse sample patterns (rc_render_pattern*): the edge list of a frame with a threshold lives
-  // in aa_list; pat_count is its 8-byte counter block (word 0: entries), the frame's own so that
-  // rc_pattern_stats_get outlives a later adaptive frame, zeroed on the frame's stream
-  DevBuf pat_count;
-  hipEvent_t pat_done = nullptr;     // behind the last refinement of a frame with a threshold
-  bool pat_valid = false;            // a pattern frame has been enqueued on this device
-  int pat_n = 0, pat_t = 0;          // its samples per pixel, threshold and pixels
-  long long pat_pixels = 0;          //   (rc_pattern_stats_get)
-  hipEvent_t* pat_ev = nullptr;      // the event set of the last pattern frame: [0] start, [1]
-                                     // end; with a threshold [2] one-ray image, [3] list
-  bool pat_ev_listed = false;        // that frame had a threshold (rc_pattern_phase_ms)
-  // two-pass supersampling's own spans (rc_filter_phase_ms): filt_mid is recorded between the
-  // s*W x s*H image and its filter; filt_ev is the event set of the last timed two-pass frame
-  // ([0] start, [filt_end] behind the filter), null when that set has been recorded anew
+  // in aa_list; its record `pat` keeps a counter block of its own so that rc_pattern_stats_get
+  // outlives a later adaptive frame.  Without a threshold (pat_t = 0) every pixel is refined and
+  // neither the counter nor pat.done is used.
+  ListFrame pat;
+  int pat_t = 0;
+  // The event set whose spans each sampling feature's rc_*_phase_ms may still read, null once
+  // another frame has recorded that set anew (claim_event_set).  adaptive: [0] start, [2]
+  // one-ray image, [3] list, [1] refinement; rates: [0] start, [2] the rate-1 pass, [1] the
+  // refinement; filter (a timed two-pass frame): [0] start, filt_mid between the s*W x s*H image
+  // and its filter, [filt_end] behind the filter; pattern: [0] start, [1] end, and with a
+  // threshold (pat_ev_listed) [2] [3] as adaptive.
+  hipEvent_t* span_ev[kSpanOwners] = {};
   hipEvent_t filt_mid = nullptr;
-  hipEvent_t* filt_ev = nullptr;
   int filt_end = 1;
+  bool pat_ev_listed = false;
   uint8_t* stage[2] = {nullptr, nullptr};   // pinned bounce buffers of copy_to_host
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   FrameBufs fb;        // scene, counter and parity workspace of the plain path
