@@ -458,6 +458,107 @@ int rc_pattern_stats_get(rc_pattern_stats *out);
  * list, ms[2] the refinement.  Returns -1 if there was none. */
 int rc_pattern_phase_ms(double ms[3]);
 
+/* Progressive supersampling: samples accumulated across calls (rc_accum_pass_device,
+ * rc_render_accum; fast and cuda mode).  Every other sampling entry shoots all of a pixel's
+ * samples in one call, stores the rounded mean and keeps nothing.  Here the caller keeps the sums,
+ * so a one-ray image exists after one ray a pixel and every later pass refines it, by any number
+ * of samples (3, 5, 11, ...), everywhere or only where the image as it stands has an edge.
+ * Fix the scene, the mode, the depth, W, H and a lattice g in {2, 4, 8}.  Let B_g be that mode's
+ * g*W x g*H image with ssaa = 1 (the B of the ssaa contract above, at s = g).
+ * State: one rc_accum_px per pixel, row-major, top row first, owned by the caller (device memory,
+ *     8-byte aligned).  sum[c] is the sum of the n sample bytes taken so far; n <= 256, so
+ *     sum <= 256 * 255 = 65280 fits.  The layout is public: save it, restore it, inspect it.
+ * Resolve: res(sum, n)[c] = (sum[c] + n/2) / n in integers (n/2 rounds down); n = 0: (0, 0, 0).
+ * Sample sequence: rc_sample_seq, (g, nsamples, x[], y[]) with g in {2, 4, 8},
+ *     1 <= nsamples <= min(64, g*g), every point on the lattice and the points pairwise distinct
+ *     (x to the right, y downwards).  Built in (rc_sample_seq_builtin): the four pattern names
+ *     (diag2, rgss4, checker8, queens8: rc_pattern_builtin's points in its order) and hier2,
+ *     hier4, hier8, the whole lattice coarse to fine: with lg = log2 g, point k is the
+ *     bit-reversal r of k over 2*lg bits, x takes r's even bits (bit 2i of r is bit i of x) and y
+ *     its odd bits.  hier2: (0,0) (0,1) (1,0) (1,1).  hier4: (0,0) (0,2) (2,0) (2,2) (0,1) (0,3)
+ *     (2,1) (2,3) ...  hier8: (0,0) (0,4) (4,0) (4,4) (0,2) (0,6) (4,2) (4,6) ...
+ * A pass is (seq, first, count, threshold t, reset) on (acc, out), with 1 <= count <= 16 and
+ *     first + count <= nsamples.  The active set M is fixed once, from what `out` holds on entry:
+ *       reset = 1:            M is every pixel, acc is not read and counts as zero, t must be 0;
+ *       reset = 0, t = 0:     M is every pixel;
+ *       reset = 0, t 1..255:  M = {contrast(out on entry)(x, y) >= t}, contrast exactly the
+ *                             adaptive contract's above (3 x 3 window clipped to the image, the
+ *                             maximum over the three channels).
+ *     For each pixel p of M: if n + count > 256, p is saturated: nothing of it changes and it is
+ *     counted.  Otherwise
+ *       sum[c] += sum over k in [first, first + count) of B_g[g*y + y[k]][g*x + x[k]][c],
+ *       n += count, and out[p] = res(sum, n).
+ *     Pixels outside M keep their acc and out bytes; they are not stored to.
+ * So after a reset pass and further t = 0 passes that together cover seq[0..k), in any split into
+ * calls, out is the k-sample mean; for a pattern's own n that is rc_render_pattern's image, and
+ * for all g*g points of hier<g> it is the ssaa = g image.  Every byte stays an exact integer
+ * function of the reference's own g*W x g*H image.
+ * On the device: one lane a pixel shoots the pass's samples one after the other (the positions in
+ * scalar registers, as the pattern kernels'), then one 8-byte load, the add and one 8-byte store
+ * of the record.  t = 0 is one kernel over k_render's tiles.  t > 0 is two launches on one stream
+ * with no host wait: the adaptive path's edge list over `out`, then the accumulation kernel
+ * striding over the list (its grid follows rc_tuning.adaptive_blocks), so an acc or out written
+ * on that stream just before the call is honoured.
+ * rc_options: mode fast or cuda; ssaa 0 or 1 (the sequence carries the grid); max_recursion as
+ * everywhere.  rc_timing.zero_normalize counts the rays actually shot.  Whole images only.
+ * Refused, each with a message and -1, from the arguments alone (before any device work): parity
+ * mode (every pixel of its g*W x g*H image depends on the scan-order carry of the whole image, so
+ * it cannot be shot sparsely); a factor above 1 or a threshold in opt->ssaa; num_gpus > 1; a
+ * sequence that fails rc_sample_seq_check; first, count or dense out of range; a threshold outside
+ * 0..255; reset with t > 0; null pointers, or an accumulator that is not 8-byte aligned; W or H
+ * below 1 or above 2^28 / g; with t > 0, W * H >= 2^32; an image of more than 65535 rows of tiles
+ * (16 rows each).
+ * raycast(), rc_render, rc_frame_submit, rc_render_sharded and the other sampling entries take no
+ * accumulator, and no RAYCAST_* variable selects one: state that lives across calls has no
+ * meaning for the one-call drop-in. */
+typedef struct rc_accum_px {
+  uint16_t sum[3];   /* per channel, the sum of the n sample bytes */
+  uint16_t n;        /* samples taken, 0..256                      */
+} rc_accum_px;
+_Static_assert(sizeof(rc_accum_px) == 8, "rc_accum_px layout (the kernels' 8-byte record)");
+#define RC_ACCUM_MAX_SAMPLES 64
+typedef struct rc_sample_seq {
+  int32_t grid, nsamples;                /* g and the sequence's length        */
+  uint8_t x[RC_ACCUM_MAX_SAMPLES];       /* x[0..nsamples); the rest is ignored */
+  uint8_t y[RC_ACCUM_MAX_SAMPLES];       /* y[0..nsamples)                      */
+} rc_sample_seq;
+_Static_assert(sizeof(rc_sample_seq) == 136, "rc_sample_seq layout (ctypes binding)");
+/* The built-in sequence of that name into *out: 0, or -1 for an unknown name or a null pointer. */
+int rc_sample_seq_builtin(const char *name, rc_sample_seq *out);
+/* 0 when *s is a valid sequence, else -1 with a message naming the rule broken. */
+int rc_sample_seq_check(const rc_sample_seq *s);
+/* One pass on the current device and the given HIP stream (NULL: the library's stream of that
+ * device, as rc_render_device); asynchronous unless timing is requested.  d_acc: W*H records,
+ * d_out: W*H*3 bytes, both device memory. */
+int rc_accum_pass_device(const rc_scene *scene, int width, int height, const rc_options *opt,
+                         const rc_sample_seq *seq, int first, int count, int threshold, int reset,
+                         rc_accum_px *d_acc, uint8_t *d_out, void *stream, rc_timing *timing);
+/* out = res(acc) for every pixel, nothing shot: for a restored state.  Asynchronous, on the
+ * current device and the given stream (NULL as above). */
+int rc_accum_resolve_device(const rc_accum_px *d_acc, int width, int height, uint8_t *d_out,
+                            void *stream);
+/* The host-pixmap form, synchronous on opt->device, the accumulator owned by the library:
+ * samples [0, dense) go to every pixel (a reset pass, in chunks of at most 16), then one
+ * single-sample pass with threshold t for each of seq[dense..nsamples) (t = 0: every pass takes
+ * every pixel).  1 <= dense <= nsamples. */
+int rc_render_accum(const rc_scene *scene, int width, int height, const rc_options *opt,
+                    const rc_sample_seq *seq, int dense, int threshold, uint8_t *pixmap,
+                    rc_timing *timing);
+typedef struct rc_accum_stats {
+  int64_t passes;          /* launch groups of the call (rc_accum_pass_device: 1)          */
+  int64_t active_pixels;   /* |M| of the last pass                                         */
+  int64_t saturated;       /* the pixels of M the last pass left alone (n + count > 256)   */
+  int64_t rays;            /* shot by the whole call: sum of (|M| - saturated) * count     */
+} rc_accum_stats;
+_Static_assert(sizeof(rc_accum_stats) == 32, "rc_accum_stats layout (ctypes binding)");
+/* The last accumulation call enqueued on the current device: waits for it, then reads its device
+ * counters (one slot a pass, so the passes never wait for the host).  -1 if there was none. */
+int rc_accum_stats_get(rc_accum_stats *out);
+/* The kernel spans (ms, HIP events) of the last pass of the last accumulation call on the current
+ * device: ms[0] the edge list (0 for a pass that takes every pixel), ms[1] the samples.  Returns
+ * -1 if there was none. */
+int rc_accum_phase_ms(double ms[2]);
+
 /* Frames in flight (an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out
  * (W*H*3 bytes, device memory, ready for use: synchronise the stream that produced it

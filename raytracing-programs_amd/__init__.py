@@ -121,6 +121,45 @@ PATTERNS = {
     "queens8": (8, [(c, r) for r, c in enumerate([3, 6, 2, 7, 1, 4, 0, 5])]),
 }
 
+ACCUM_MAX_SAMPLES = 64    # a sample sequence's length at most
+ACCUM_MAX_N = 256         # samples a pixel's record can hold
+ACCUM_MAX_COUNT = 16      # samples a pass adds at most
+
+
+class RcAccumPx(ctypes.Structure):
+    """rc_accum_px (8 bytes): a pixel's sums of the n sample bytes taken so far, and n."""
+    _fields_ = [("sum", ctypes.c_uint16 * 3), ("n", ctypes.c_uint16)]
+
+
+class RcSampleSeq(ctypes.Structure):
+    """rc_sample_seq (136 bytes): the lattice g, the length and the positions x, y."""
+    _fields_ = [("grid", ctypes.c_int32), ("nsamples", ctypes.c_int32),
+                ("x", ctypes.c_uint8 * ACCUM_MAX_SAMPLES),
+                ("y", ctypes.c_uint8 * ACCUM_MAX_SAMPLES)]
+
+
+class RcAccumStats(ctypes.Structure):
+    _fields_ = [("passes", ctypes.c_int64), ("active_pixels", ctypes.c_int64),
+                ("saturated", ctypes.c_int64), ("rays", ctypes.c_int64)]
+
+
+def _hier_points(g):
+    """hier<g> (include/raycast_hip.h, rc_sample_seq): point k is the bit-reversal r of k over
+    2 * log2 g bits; x takes r's even bits and y its odd bits."""
+    lg = g.bit_length() - 1
+    pts = []
+    for k in range(g * g):
+        r = sum(((k >> b) & 1) << (2 * lg - 1 - b) for b in range(2 * lg))
+        pts.append((sum(((r >> (2 * i)) & 1) << i for i in range(lg)),
+                    sum(((r >> (2 * i + 1)) & 1) << i for i in range(lg))))
+    return pts
+
+
+# the built-in sample sequences (rc_sample_seq_builtin): name -> (g, [(x, y), ...]); the patterns
+# in their own order and the whole lattice coarse to fine
+SAMPLE_SEQS = dict({name: (g, list(pts)) for name, (g, pts) in PATTERNS.items()},
+                   **{f"hier{g}": (g, _hier_points(g)) for g in (2, 4, 8)})
+
 
 # the values a rate map's bytes may take (rc_render_rates): 0 leaves the pixel alone
 RATE_VALUES = (0, 1, 2, 4, 8)
@@ -194,7 +233,10 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_filter_check", "rc_filter_env", "rc_render_filtered",
                "rc_render_filtered_device", "rc_filter_image_device", "rc_filter_phase_ms",
                "rc_pattern_builtin", "rc_pattern_check", "rc_pattern_env", "rc_render_pattern",
-               "rc_render_pattern_device", "rc_pattern_stats_get", "rc_pattern_phase_ms"]
+               "rc_render_pattern_device", "rc_pattern_stats_get", "rc_pattern_phase_ms",
+               "rc_sample_seq_builtin", "rc_sample_seq_check", "rc_accum_pass_device",
+               "rc_accum_resolve_device", "rc_render_accum", "rc_accum_stats_get",
+               "rc_accum_phase_ms"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -347,6 +389,21 @@ def _hip_lib_locked():
                                              ctypes.POINTER(RcTiming)]
     lib.rc_pattern_stats_get.argtypes = [ctypes.POINTER(RcPatternStats)]
     lib.rc_pattern_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    lib.rc_sample_seq_builtin.argtypes = [ctypes.c_char_p, ctypes.POINTER(RcSampleSeq)]
+    lib.rc_sample_seq_check.argtypes = [ctypes.POINTER(RcSampleSeq)]
+    lib.rc_accum_pass_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                         ctypes.POINTER(RcOptions), ctypes.POINTER(RcSampleSeq),
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.POINTER(RcTiming)]
+    lib.rc_accum_resolve_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p]
+    lib.rc_render_accum.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                    ctypes.POINTER(RcOptions), ctypes.POINTER(RcSampleSeq),
+                                    ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                    ctypes.POINTER(RcTiming)]
+    lib.rc_accum_stats_get.argtypes = [ctypes.POINTER(RcAccumStats)]
+    lib.rc_accum_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
     _hip = lib
     return lib
 
@@ -993,6 +1050,187 @@ def pattern_from_env(mode="fast", ssaa=1, adaptive=0):
     if hip_lib().rc_pattern_env(ctypes.byref(opt), ctypes.byref(p), ctypes.byref(t)) != 1:
         return None
     return p.grid, [(int(p.x[k]), int(p.y[k])) for k in range(p.nsamples)], t.value
+
+
+def sample_seq_check(g, points):
+    """The rules of a sample sequence (include/raycast_hip.h, rc_sample_seq), stated here so that
+    they hold without the library; returns the length, raises ValueError naming the rule."""
+    g = int(g)
+    if g not in (2, 4, 8):
+        raise ValueError(f"sample sequence: grid {g} is not 2, 4 or 8")
+    pts = [(int(x), int(y)) for x, y in points]
+    n, most = len(pts), min(ACCUM_MAX_SAMPLES, g * g)
+    if not 1 <= n <= most:
+        raise ValueError(f"sample sequence: {n} samples, not 1..{most}")
+    for k, (x, y) in enumerate(pts):
+        if not (0 <= x < g and 0 <= y < g):
+            raise ValueError(f"sample sequence: sample {k} at ({x}, {y}) is off the {g} x {g} "
+                             "lattice")
+        if (x, y) in pts[:k]:
+            raise ValueError(f"sample sequence: sample {k} repeats ({x}, {y})")
+    return n
+
+
+def sample_seq(p):
+    """A checked sequence (g, [(x, y), ...]) from a built-in name (SAMPLE_SEQS) or a (g, points)
+    pair."""
+    if isinstance(p, str):
+        if p not in SAMPLE_SEQS:
+            raise ValueError(f"sample sequence: '{p}' is not one of {sorted(SAMPLE_SEQS)}")
+        p = SAMPLE_SEQS[p]
+    g, points = p
+    pts = [(int(x), int(y)) for x, y in points]
+    sample_seq_check(g, pts)
+    return int(g), pts
+
+
+def _accum_state(acc):
+    acc = np.asarray(acc)
+    if acc.dtype != np.uint16 or acc.ndim != 3 or acc.shape[2] != 4:
+        raise ValueError(f"an accumulator is [H, W, 4] uint16 (three sums and n), got {acc.dtype} "
+                         f"{acc.shape}")
+    return acc
+
+
+def accum_resolve(acc):
+    """The accumulation contract's resolve (include/raycast_hip.h, rc_accum_px) in numpy: the
+    [H, W, 3] uint8 image (sum + n/2) // n of an [H, W, 4] uint16 accumulator; (0, 0, 0) where
+    n = 0."""
+    acc = _accum_state(acc).astype(np.uint32)
+    n = acc[:, :, 3:4]
+    res = (acc[:, :, :3] + n // 2) // np.maximum(n, 1)
+    return np.where(n > 0, res, 0).astype(np.uint8)
+
+
+def accum_step(acc, out, big, g, points, t=0, reset=False):
+    """One pass of the accumulation contract in numpy: the samples `points` (1..16 lattice points,
+    the pass's slice of its sequence) of the [g*H, g*W, 3] uint8 image `big` are added to the
+    pixels of the active set, every pixel (t = 0, or reset, which also zeroes the accumulator
+    first) or edge_mask(out, t); an active pixel whose n would pass 256 is saturated and keeps
+    everything.  Returns (acc', out', active, saturated); the arguments are not written."""
+    big, g, t = np.asarray(big), int(g), int(t)
+    points = [(int(x), int(y)) for x, y in points]
+    count = len(points)
+    if not 1 <= count <= ACCUM_MAX_COUNT:
+        raise ValueError(f"accum_step: {count} samples, a pass takes 1..{ACCUM_MAX_COUNT}")
+    if g not in (2, 4, 8) or any(not (0 <= x < g and 0 <= y < g) for x, y in points):
+        raise ValueError(f"accum_step: points off the {g} x {g} lattice (g is 2, 4 or 8)")
+    if not 0 <= t <= 255 or (reset and t):
+        raise ValueError(f"accum_step: threshold {t} (0..255, and 0 with reset)")
+    if big.dtype != np.uint8 or big.ndim != 3 or big.shape[0] % g or big.shape[1] % g:
+        raise ValueError(f"accum_step: a uint8 [g*H, g*W, C] image, got {big.dtype} {big.shape}")
+    acc, out = _accum_state(acc), np.asarray(out)
+    h, w = big.shape[0] // g, big.shape[1] // g
+    if acc.shape[:2] != (h, w) or out.shape != (h, w, 3) or out.dtype != np.uint8:
+        raise ValueError(f"accum_step: acc {acc.shape} and out {out.dtype} {out.shape} do not fit "
+                         f"a {w} x {h} image")
+    state = np.zeros((h, w, 4), dtype=np.uint32) if reset else acc.astype(np.uint32)
+    mask = edge_mask(out, t) if t > 0 else np.ones((h, w), dtype=bool)
+    saturated = mask & (state[:, :, 3] + count > ACCUM_MAX_N)
+    take = mask & ~saturated
+    add = sum(big[y::g, x::g].astype(np.uint32) for x, y in points)
+    state[:, :, :3] += add * take[:, :, None]
+    state[:, :, 3] += (count * take).astype(np.uint32)
+    new_acc = np.where(take[:, :, None], state, acc).astype(np.uint16)
+    new_out = np.where(take[:, :, None], accum_resolve(new_acc), out)
+    return new_acc, new_out, int(mask.sum()), int(saturated.sum())
+
+
+def accum_run(big, g, points, dense, t=0):
+    """rc_render_accum's contract in numpy: samples [0, dense) of the sequence for every pixel
+    (a reset pass in chunks of at most 16), then one single-sample pass with threshold t for each
+    of the others.  Returns the [H, W, 3] uint8 image."""
+    big, g = np.asarray(big), int(g)
+    points = [(int(x), int(y)) for x, y in points]
+    n = sample_seq_check(g, points)
+    if not 1 <= int(dense) <= n:
+        raise ValueError(f"accum_run: dense {dense} is not 1..{n}")
+    h, w = big.shape[0] // g, big.shape[1] // g
+    acc = np.zeros((h, w, 4), dtype=np.uint16)
+    out = np.zeros((h, w, 3), dtype=np.uint8)
+    for k in range(0, dense, ACCUM_MAX_COUNT):
+        acc, out, _, _ = accum_step(acc, out, big, g, points[k:min(dense, k + ACCUM_MAX_COUNT)], 0,
+                                    reset=k == 0)
+    for k in range(dense, n):
+        acc, out, _, _ = accum_step(acc, out, big, g, points[k:k + 1], t)
+    return out
+
+
+def _rc_sample_seq(p):
+    g, pts = sample_seq(p)
+    seq = RcSampleSeq()
+    seq.grid, seq.nsamples = g, len(pts)
+    for k, (x, y) in enumerate(pts):
+        seq.x[k], seq.y[k] = x, y
+    return seq
+
+
+def accum_pass_device(scene, width, height, seq, first, count, d_acc_ptr, d_out_ptr, threshold=0,
+                      reset=False, stream_ptr=None, depth=6, mode="fast", timing=None):
+    """rc_accum_pass_device: samples [first, first + count) of `seq` (a built-in name or a
+    (g, [(x, y), ...]) pair) are added to the accumulator (W*H*8 bytes of device memory, an
+    [H, W, 4] uint16 array) and the means stored in the image (W*H*3 bytes), for every pixel
+    (threshold 0) or the pixels of the image as it stands whose 3 x 3 contrast reaches
+    `threshold` (accum_step).  Enqueued on the stream and asynchronous unless `timing` is given."""
+    lib = hip_lib()
+    s = _rc_sample_seq(seq)
+    opt = options(depth, mode)
+    t = RcTiming()
+    rc = lib.rc_accum_pass_device(scene.packed(), width, height, ctypes.byref(opt),
+                                  ctypes.byref(s), int(first), int(count), int(threshold),
+                                  1 if reset else 0, ctypes.c_void_p(d_acc_ptr),
+                                  ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(stream_ptr or 0),
+                                  ctypes.byref(t) if timing is not None else None)
+    if rc != 0:
+        raise RuntimeError("rc_accum_pass_device failed (see stderr)")
+    _timing_back(timing, t)
+
+
+def accum_resolve_device(d_acc_ptr, width, height, d_out_ptr, stream_ptr=None):
+    """rc_accum_resolve_device: the image of an accumulator (accum_resolve), nothing shot."""
+    rc = hip_lib().rc_accum_resolve_device(ctypes.c_void_p(d_acc_ptr), width, height,
+                                           ctypes.c_void_p(d_out_ptr),
+                                           ctypes.c_void_p(stream_ptr or 0))
+    if rc != 0:
+        raise RuntimeError("rc_accum_resolve_device failed (see stderr)")
+
+
+def render_accum(scene, width, height, seq, dense=None, threshold=0, depth=6, mode="fast",
+                 device=0, timing=None, out=None):
+    """rc_render_accum (accum_run): samples [0, dense) of `seq` for every pixel, then one
+    single-sample pass with `threshold` for each of the others.  dense = None: the whole sequence.
+    Fast and cuda mode."""
+    lib = hip_lib()
+    s = _rc_sample_seq(seq)
+    out = _pixmap(out, width, height)
+    t = RcTiming()
+    opt = options(depth, mode, 1, device)
+    rc = lib.rc_render_accum(scene.packed(), width, height, ctypes.byref(opt), ctypes.byref(s),
+                             s.nsamples if dense is None else int(dense), int(threshold),
+                             out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
+    if rc != 0:
+        raise RuntimeError("rc_render_accum failed (see stderr)")
+    _timing_back(timing, t)
+    return out
+
+
+def accum_stats():
+    """The last accumulation call enqueued on the current device (rc_accum_stats_get, which waits
+    for it): {"passes", "active_pixels", "saturated", "rays"}; the pixel counts are the last
+    pass's, the rays the whole call's."""
+    st = RcAccumStats()
+    if hip_lib().rc_accum_stats_get(ctypes.byref(st)) != 0:
+        raise RuntimeError("rc_accum_stats_get: no accumulation call on this device")
+    return {k: getattr(st, k) for k, _ in RcAccumStats._fields_}
+
+
+def accum_phase_ms():
+    """Kernel spans of the last pass of the last accumulation call (rc_accum_phase_ms), in ms:
+    {"mark", "shoot"}; "mark" is 0 for a pass that takes every pixel."""
+    ms = (ctypes.c_double * 2)()
+    if hip_lib().rc_accum_phase_ms(ms) != 0:
+        raise RuntimeError("rc_accum_phase_ms: no accumulation call on this device")
+    return {"mark": ms[0], "shoot": ms[1]}
 
 
 SPIN_SITES = ("team_handoff", "phase_c_carry_in", "ready_queue", "helper_queue")

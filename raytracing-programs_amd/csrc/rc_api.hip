@@ -1103,6 +1103,150 @@ static int pattern_refused(const char* who, const rc_options* opt, int W, int H,
   return 0;
 }
 
+// ------------------------------------------------------- progressive supersampling --
+int rc_accum_stats_get(rc_accum_stats* out) {
+  Entered e;
+  if (!out || enter(kCurrentDevice, false, e) || !e.c->acc.valid) return -1;
+  const AccumFrame& f = e.c->acc;
+  HIP_TRY(hipEventSynchronize(f.done));   // the call's stream, up to its last pass
+  unsigned n[AccumFrame::kSlots][2] = {};   // per pass {listed, saturated}
+  HIP_TRY(hipMemcpy(n, f.count.p, (size_t)f.passes * sizeof n[0], hipMemcpyDeviceToHost));
+  out->passes = f.passes;
+  out->rays = 0;
+  for (int k = 0; k < f.passes; ++k) {
+    out->active_pixels = f.listed[k] ? (int64_t)n[k][0] : (int64_t)f.pixels;
+    out->saturated = (int64_t)n[k][1];
+    out->rays += (out->active_pixels - out->saturated) * f.samples[k];
+  }
+  return 0;
+}
+
+int rc_accum_phase_ms(double ms[2]) {
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanAccum];
+  if (!ev) return -1;
+  hipEvent_t first = ev[e.c->acc_ev_first];
+  if (e.c->acc_ev_listed) return read_spans({first, ev[3], ev[1]}, ms);
+  ms[0] = 0.0;
+  return read_spans({first, ev[1]}, ms + 1);
+}
+
+// hier<g>: point k is the bit-reversal r of k over 2 * lg bits; x takes r's even bits, y its odd
+// bits (include/raycast_hip.h, rc_sample_seq)
+static void hier_seq(int lg, rc_sample_seq* out) {
+  out->grid = 1 << lg;
+  out->nsamples = 1 << (2 * lg);
+  for (int k = 0; k < out->nsamples; ++k) {
+    int r = 0;
+    for (int b = 0; b < 2 * lg; ++b) r |= ((k >> b) & 1) << (2 * lg - 1 - b);
+    int x = 0, y = 0;
+    for (int i = 0; i < lg; ++i) {
+      x |= ((r >> (2 * i)) & 1) << i;
+      y |= ((r >> (2 * i + 1)) & 1) << i;
+    }
+    out->x[k] = (uint8_t)x;
+    out->y[k] = (uint8_t)y;
+  }
+}
+
+int rc_sample_seq_builtin(const char* name, rc_sample_seq* out) {
+  if (!name || !out) return -1;
+  std::memset(out, 0, sizeof *out);
+  for (int lg = 1; lg <= 3; ++lg) {
+    const char hier[] = {'h', 'i', 'e', 'r', (char)('0' + (1 << lg)), '\0'};
+    if (std::strcmp(name, hier)) continue;
+    hier_seq(lg, out);
+    return 0;
+  }
+  rc_pattern p;
+  if (rc_pattern_builtin(name, &p)) return -1;
+  out->grid = p.grid;
+  out->nsamples = p.nsamples;
+  std::memcpy(out->x, p.x, (size_t)p.nsamples);
+  std::memcpy(out->y, p.y, (size_t)p.nsamples);
+  return 0;
+}
+
+int rc_sample_seq_check(const rc_sample_seq* s) {
+  if (!s) {
+    std::fprintf(stderr, "Error: rc_sample_seq_check: a null sequence\n");
+    return -1;
+  }
+  const int g = s->grid, n = s->nsamples;
+  if (g != 2 && g != 4 && g != 8) {
+    std::fprintf(stderr, "Error: rc_sample_seq_check: grid %d is not 2, 4 or 8\n", g);
+    return -1;
+  }
+  const int most = g * g < RC_ACCUM_MAX_SAMPLES ? g * g : RC_ACCUM_MAX_SAMPLES;
+  if (n < 1 || n > most) {
+    std::fprintf(stderr, "Error: rc_sample_seq_check: %d samples, not 1..%d (a %d x %d lattice, at "
+                 "most %d)\n", n, most, g, g, RC_ACCUM_MAX_SAMPLES);
+    return -1;
+  }
+  for (int k = 0; k < n; ++k) {
+    if (s->x[k] >= g || s->y[k] >= g) {
+      std::fprintf(stderr, "Error: rc_sample_seq_check: sample %d at (%d, %d) is off the %d x %d "
+                   "lattice\n", k, s->x[k], s->y[k], g, g);
+      return -1;
+    }
+    for (int j = 0; j < k; ++j)
+      if (s->x[j] == s->x[k] && s->y[j] == s->y[k]) {
+        std::fprintf(stderr, "Error: rc_sample_seq_check: samples %d and %d are both at (%d, %d)\n",
+                     j, k, s->x[k], s->y[k]);
+        return -1;
+      }
+  }
+  return 0;
+}
+
+// What the accumulation entry points refuse from their arguments alone, whatever the passes:
+// `masked`: the call has a pass over the edge list, `dense`: one over every pixel.
+static int accum_refused(const char* who, const rc_options* opt, int W, int H,
+                         const rc_sample_seq* seq, int threshold, bool dense, bool masked) {
+  const int ss = ssaa_factor(opt, who);
+  if (ss < 0) return -1;   // ssaa_decode has said why (a threshold without a factor included)
+  if (ss > 1) {
+    std::fprintf(stderr, "Error: %s: ssaa %d in the options: the sample sequence carries the "
+                 "grid, leave ssaa at 0 or 1\n", who, opt->ssaa);
+    return -1;
+  }
+  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
+    std::fprintf(stderr, "Error: %s: accumulated samples are for fast and cuda mode: every pixel "
+                 "of a parity image depends on the scan-order carry of the whole image, so it "
+                 "cannot be shot sparsely; use plain ssaa\n", who);
+    return -1;
+  }
+  if (opt->num_gpus > 1) {
+    std::fprintf(stderr, "Error: %s: num_gpus %d: the row shards take no accumulator\n", who,
+                 opt->num_gpus);
+    return -1;
+  }
+  if (rc_sample_seq_check(seq)) return -1;
+  if (threshold < 0 || threshold > 255) {
+    std::fprintf(stderr, "Error: %s: threshold %d is not 0..255\n", who, threshold);
+    return -1;
+  }
+  const int g = seq->grid;
+  if (W <= 0 || H <= 0 || W > (1 << 28) / g || H > (1 << 28) / g) {
+    std::fprintf(stderr, "Error: %s: %d x %d on a lattice of %d: both sides must be 1 .. 2^28 / "
+                 "g\n", who, W, H, g);
+    return -1;
+  }
+  if (masked && (unsigned long long)W * (unsigned long long)H >= (1ull << 32)) {
+    std::fprintf(stderr, "Error: %s: %d x %d with a threshold is too large (32-bit pixel "
+                 "indices)\n", who, W, H);
+    return -1;
+  }
+  if ((dense && !rc::accum_supported(W, H, g, false)) ||
+      (masked && !rc::accum_supported(W, H, g, true))) {
+    std::fprintf(stderr, "Error: %s: %d x %d is too large for the kernels' grids (at most 65535 "
+                 "rows of tiles)\n", who, W, H);
+    return -1;
+  }
+  return 0;
+}
+
 void rc_default_options(rc_options* opt, int use_env) {
   opt->max_recursion = 7;   // C/raycast.c:14
   opt->mode = RC_MODE_PARITY;
@@ -1780,6 +1924,78 @@ static int enqueue_pattern(DevCtx& c, const rc_scene* s, int W, int H, const rc_
   });
 }
 
+// One pass of an accumulation call: samples [first, first + count) of the sequence, over every
+// pixel (at = 0) or over the pixels whose contrast in `out` reaches at; reset: the records count
+// as zero and are not read.
+struct AccumPass {
+  int first, count, at;
+  bool reset;
+};
+
+// The passes of one accumulation call on `stream` through the device's one-frame workspace (the
+// caller holds c.mu and has passed accum_refused and the range checks; at most
+// AccumFrame::kSlots passes).  A pass over every pixel is one launch; a masked pass is the
+// adaptive path's edge list (launch_aa_mark over d_out into aa_list) and the list kernel.
+// Nothing waits for the host: pass k counts into slot k of the call's counter block.
+static int enqueue_accum(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
+                         const rc_sample_seq* seq, const AccumPass* passes, int npasses,
+                         rc_accum_px* d_acc, uint8_t* d_out, hipStream_t stream) {
+  bool masked = false;
+  for (int k = 0; k < npasses; ++k) masked = masked || passes[k].at > 0;
+  auto prepare = [&]() -> int {
+    if (c.acc.count.ensure(AccumFrame::kSlots * 8) ||
+        (masked && c.aa_list.ensure((size_t)W * H * sizeof(uint32_t)))) {
+      std::fprintf(stderr, "Error: out of device memory for the edge list (%d x %d)\n", W, H);
+      return -1;
+    }
+    if (!c.acc.done) HIP_TRY(hipEventCreateWithFlags(&c.acc.done, hipEventDisableTiming));
+    return 0;
+  };
+  return ws_frame(c, stream, prepare, [&]() -> int {
+    rc::LaunchScene ls;
+    if (upload_scene(c.fb, stream, s, ls)) return -1;
+    unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
+    unsigned* cnt = (unsigned*)c.acc.count.p;
+    uint32_t* list = (uint32_t*)c.aa_list.p;
+    c.acc.valid = false;   // the block is this call's from here on
+    HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)npasses * 8, stream));
+    const int maxrec = opt->max_recursion, g = seq->grid;
+    const bool cuda = opt->mode == RC_MODE_CUDA;
+    hipEvent_t* ev = claim_event_set(c, kSpanAccum, false, true);
+    HIP_TRY(hipEventRecord(ev[0], stream));
+    for (int k = 0; k < npasses; ++k) {
+      const AccumPass& p = passes[k];
+      const bool last = k + 1 == npasses;
+      if (last && k > 0) HIP_TRY(hipEventRecord(ev[2], stream));
+      const uint8_t* px = seq->x + p.first;
+      const uint8_t* py = seq->y + p.first;
+      unsigned* slot = cnt + 2 * k;
+      if (p.at == 0) {
+        HIP_TRY(rc::launch_accum(ls, W, H, g, p.count, px, py, p.reset, maxrec, d_acc, d_out, zc,
+                                 slot + 1, stream, cuda));
+      } else {
+        HIP_TRY(rc::launch_aa_mark(d_out, W, H, p.at, list, slot, stream));
+        if (last) HIP_TRY(hipEventRecord(ev[3], stream));
+        HIP_TRY(rc::launch_accum_list(
+            ls, W, H, g, p.count, px, py, maxrec, list, slot, d_acc, d_out, zc, slot + 1,
+            rc::accum_list_blocks(W, H, c.cus, tune().adaptive_blocks), stream, cuda));
+      }
+      c.acc.samples[k] = (uint8_t)p.count;
+      c.acc.listed[k] = p.at > 0;
+    }
+    HIP_TRY(hipEventRecord(ev[1], stream));
+    HIP_TRY(hipEventRecord(c.acc.done, stream));
+    c.acc.valid = true;
+    c.acc.passes = npasses;
+    c.acc.pixels = (long long)W * H;
+    c.span_ev[kSpanAccum] = ev;
+    c.acc_ev_first = npasses > 1 ? 2 : 0;
+    c.acc_ev_listed = passes[npasses - 1].at > 0;
+    return 0;
+  });
+}
+
 // After a synchronised parity render: the resolver's and phase C's bounded spins set
 // TeamState.error (first word) if a hand-off never completed; the image is then invalid.
 // The report names the first spin that failed (TeamState: code, workgroup, site detail), the
@@ -2222,6 +2438,101 @@ int rc_render_pattern(const rc_scene* s, int W, int H, const rc_options* opt,
   }
   if (enqueue_pattern(*c, s, W, H, opt, pat, threshold, (uint8_t*)c->out.p, c->stream)) return -1;
   return finish_host(*c, opt, pixmap, bytes, tu, {false, false, kNoLog}, timing, t0);
+}
+
+int rc_accum_pass_device(const rc_scene* s, int W, int H, const rc_options* opt,
+                         const rc_sample_seq* seq, int first, int count, int threshold, int reset,
+                         rc_accum_px* d_acc, uint8_t* d_out, void* stream, rc_timing* timing) {
+  const char* who = "rc_accum_pass_device";
+  if (!s || !opt || !seq || !d_acc || !d_out) {
+    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
+    return -1;
+  }
+  if ((uintptr_t)d_acc & 7u) {
+    std::fprintf(stderr, "Error: %s: the accumulator is not 8-byte aligned\n", who);
+    return -1;
+  }
+  if (accum_refused(who, opt, W, H, seq, threshold, threshold == 0, threshold > 0)) return -1;
+  if (count < 1 || count > 16 || first < 0 || first > seq->nsamples - count) {
+    std::fprintf(stderr, "Error: %s: samples [%d, %d + %d) of a sequence of %d: a pass takes 1..16 "
+                 "samples inside the sequence\n", who, first, first, count, seq->nsamples);
+    return -1;
+  }
+  if (reset && threshold > 0) {
+    std::fprintf(stderr, "Error: %s: reset with threshold %d: a reset pass takes every pixel "
+                 "(there is no image yet to find edges in), leave the threshold at 0\n", who,
+                 threshold);
+    return -1;
+  }
+  Entered e;
+  if (enter(kCurrentDevice, true, e)) return -1;
+  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
+  const AccumPass pass{first, count, threshold, reset != 0};
+  if (enqueue_accum(*e.c, s, W, H, opt, seq, &pass, 1, d_acc, d_out, st)) return -1;
+  return finish_device(*e.c, opt, st, timing, kNoLog);
+}
+
+int rc_accum_resolve_device(const rc_accum_px* d_acc, int W, int H, uint8_t* d_out, void* stream) {
+  const char* who = "rc_accum_resolve_device";
+  if (!d_acc || !d_out) {
+    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
+    return -1;
+  }
+  if ((uintptr_t)d_acc & 7u) {
+    std::fprintf(stderr, "Error: %s: the accumulator is not 8-byte aligned\n", who);
+    return -1;
+  }
+  if (W <= 0 || H <= 0 || ((unsigned long long)W * (unsigned long long)H + 255) / 256 > 0x7fffffffull) {
+    std::fprintf(stderr, "Error: %s: %d x %d: both sides must be at least 1 and the image at most "
+                 "2^39 - 256 pixels (one grid)\n", who, W, H);
+    return -1;
+  }
+  Entered e;
+  if (enter(kCurrentDevice, false, e)) return -1;
+  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
+  HIP_TRY(rc::launch_accum_resolve(d_acc, W, H, d_out, st));
+  return 0;
+}
+
+int rc_render_accum(const rc_scene* s, int W, int H, const rc_options* opt,
+                    const rc_sample_seq* seq, int dense, int threshold, uint8_t* pixmap,
+                    rc_timing* timing) {
+  const char* who = "rc_render_accum";
+  if (!s || !opt || !seq || !pixmap) {
+    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
+    return -1;
+  }
+  const auto t0 = HostClock::now();
+  // which kernels run is known once the sequence and dense have been checked; the limits of both
+  // are tested here, a call that needs only one of them being a sub-case of no interest
+  if (accum_refused(who, opt, W, H, seq, threshold, true, threshold > 0)) return -1;
+  if (dense < 1 || dense > seq->nsamples) {
+    std::fprintf(stderr, "Error: %s: dense %d is not 1..%d (the sequence's length)\n", who, dense,
+                 seq->nsamples);
+    return -1;
+  }
+  // samples [0, dense) for every pixel in chunks of at most 16, the first chunk resetting the
+  // accumulator; then one single-sample pass for each of the others
+  AccumPass passes[AccumFrame::kSlots];
+  int np = 0;
+  for (int k = 0; k < dense; k += 16)
+    passes[np++] = {k, dense - k < 16 ? dense - k : 16, 0, k == 0};
+  for (int k = dense; k < seq->nsamples; ++k) passes[np++] = {k, 1, threshold, false};
+  if (timing) std::memset(timing, 0, sizeof *timing);
+  const rc_tuning tu = tune();
+  Entered e;
+  if (enter_host(opt, e)) return -1;
+  DevCtx* c = e.c;
+  const size_t pixels = (size_t)W * H;
+  if (c->out.ensure(pixels * 3) || c->accum_px.ensure(pixels * sizeof(rc_accum_px))) {
+    std::fprintf(stderr, "Error: out of device memory for the image and its accumulator "
+                 "(%d x %d)\n", W, H);
+    return -1;
+  }
+  if (enqueue_accum(*c, s, W, H, opt, seq, passes, np, (rc_accum_px*)c->accum_px.p,
+                    (uint8_t*)c->out.p, c->stream))
+    return -1;
+  return finish_host(*c, opt, pixmap, pixels * 3, tu, {false, false, kNoLog}, timing, t0);
 }
 
 int rc_render_filtered_device(const rc_scene* s, int W, int H, const rc_options* opt,

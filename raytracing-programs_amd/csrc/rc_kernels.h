@@ -175,6 +175,36 @@ hipError_t launch_pattern_list(const LaunchScene& s, int W, int H, int g, int n,
 // want > 0: that many; else from the CU count, at most the wave steps a W x H list can need
 int pattern_list_blocks(int W, int H, int n, int cus, int want);
 
+// Progressive supersampling (rc_accum_pass_device, rc_render_accum; fast and cuda modes): `acc`
+// holds one rc_accum_px per pixel (8 bytes, 8-byte aligned: the sums of the sample bytes taken so
+// far and their number n); a pass shoots `count` (1..16) further samples at the positions
+// (px[j], py[j]), j < count, of the g x g lattice with the camera of the g*W x g*H image, one
+// lane a pixel, adds them to the record and stores the rounded mean of all n + count samples in
+// `out`.  A pixel with n + count > 256 is left as it is and counted in *sat (zeroed by the caller
+// on the stream).
+//   launch_accum          every pixel (k_render's tiles); reset: the records are not read and
+//                         count as zero;
+//   launch_accum_list     the pixels launch_aa_mark listed from `out`, with `blocks` workgroups
+//                         (accum_list_blocks) striding over the list, whose length is read on the
+//                         device; the other pixels' records and bytes are not stored to;
+//   launch_accum_resolve  out = the rounded means of `acc`, nothing shot ((0, 0, 0) where n = 0).
+// accum_supported: g in {2, 4, 8}; W, H in 1 .. 2^28 / g; dense: at most 65535 rows of tiles and
+// 2^31 - 1 tiles; listed: W*H < 2^32 and a grid launch_aa_mark can address.  The launchers return
+// hipErrorInvalidValue for anything it refuses.
+int accum_supported(int W, int H, int g, bool listed);
+hipError_t launch_accum(const LaunchScene& s, int W, int H, int g, int count, const uint8_t* px,
+                        const uint8_t* py, bool reset, int maxrec, void* acc, uint8_t* out,
+                        unsigned long long* zcount, unsigned* sat, hipStream_t stream,
+                        bool cuda_sem);
+hipError_t launch_accum_list(const LaunchScene& s, int W, int H, int g, int count,
+                             const uint8_t* px, const uint8_t* py, int maxrec,
+                             const uint32_t* list, const unsigned* nlist, void* acc, uint8_t* out,
+                             unsigned long long* zcount, unsigned* sat, int blocks,
+                             hipStream_t stream, bool cuda_sem);
+hipError_t launch_accum_resolve(const void* acc, int W, int H, uint8_t* out, hipStream_t stream);
+// want > 0: that many; else from the CU count, at most the wave steps a W x H list can need
+int accum_list_blocks(int W, int H, int cus, int want);
+
 hipError_t launch_parity(const LaunchScene& s, int W, int H, int maxrec, uint8_t* out,
                          const ParityWork& w, unsigned long long* zcount, hipStream_t stream,
                          const hipEvent_t* ev);

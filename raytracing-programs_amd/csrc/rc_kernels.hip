@@ -4070,4 +4070,233 @@ hipError_t launch_deinterleave(const uint8_t* gathered, const uint8_t* block0, i
 size_t deprec_bytes() { return sizeof(DepLine); }   // one line per pixel (DepLine)
 size_t row_stats_bytes() { return sizeof(RowStats); }
 
+// -------------------------------------- progressive supersampling (fast, cuda) --
+// rc_accum_pass_device / rc_render_accum (include/raycast_hip.h, rc_accum_px): the caller keeps
+// one 8-byte record per pixel, the sums of the n sample bytes taken so far and n itself, and a
+// pass adds `count` (1..16) further samples of a sequence on the g x g subsample lattice and
+// stores the rounded mean of all of them.  Sample k of pixel (x, y) is pixel
+// (g*x + px[k], g*y + py[k]) of the g*W x g*H image, shot with that image's camera (`cam`) through
+// sample_shoot exactly as k_pattern shoots its samples, so every sample byte is that image's byte.
+// The pass's slice of the sequence travels as PatWords (entry j of the words is sample first + j),
+// read with a uniform index, so the positions stay in scalar registers.  These kernels and their
+// launchers stand behind every other kernel of the file: kernels are emitted in instantiation
+// order, and the layout of the code object before them stays the parent's.
+//
+// One lane per pixel shoots its `count` samples one after the other (a uniform trip count), so any
+// count works, not only the powers of two a lane butterfly can reduce.  The record is a uint2:
+// .x = sum[0] | sum[1] << 16, .y = sum[2] | n << 16.  sample_shoot's packing R | G << 16 and B
+// adds onto it directly: a channel's sum is at most 256 * 255 = 65280 < 2^16, so nothing carries
+// from R into G or from B into n.  A pixel with n + count > 256 is saturated: nothing of it
+// changes, and the pass counts it in *sat (one ballot a wave, an atomic by its first lane only
+// when the ballot is not empty).
+__device__ __forceinline__ void accum_resolve_px(uint2 rec, uint8_t& r, uint8_t& g, uint8_t& b) {
+  const unsigned n = rec.y >> 16;
+  if (n == 0u) {
+    r = g = b = 0;
+    return;
+  }
+  const unsigned half = n >> 1;
+  r = (uint8_t)(((rec.x & 0xffffu) + half) / n);
+  g = (uint8_t)(((rec.x >> 16) + half) / n);
+  b = (uint8_t)(((rec.y & 0xffffu) + half) / n);
+}
+
+// Called by every lane of the wave.
+__device__ __forceinline__ void accum_count_saturated(bool saturated, unsigned* __restrict__ sat) {
+  const unsigned long long m = __ballot(saturated);
+  if (m && (threadIdx.x & 63) == 0) atomicAdd(sat, (unsigned)__popcll(m));
+}
+
+// Dense pass: every pixel of the image, k_render's grid, tiles and framebuffer stores.  The
+// record's n is read alone before the samples (two bytes; the branch keeps it in the exec mask,
+// not in a register across shoot) and the whole record once after them: one 8-byte load and one
+// 8-byte store a lane, adjacent lanes of a tile row adjacent in memory.  `reset`: the record is
+// not read at all and counts as zero.
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum(
+    Scene sc, Cam cam, int W, int H, int lg, int count, PatWords pat, int reset, int maxrec,
+    uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
+    unsigned* __restrict__ sat) {
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  __shared__ TileBytes tb;
+  tile_init(tb);
+  stage_scene<kStage>(sc, stage);
+  if (!kStage) __syncthreads();
+  int lx, ly;
+  tile_pixel(lx, ly);
+  int bx, by;
+  xcd_tile<0>(bx, by);
+  const int x0 = bx * kTileW, y0 = by * kTileH;
+  const int x = x0 + lx, y = y0 + ly;
+  bool saturated = false;
+  if (x < W && y < H) {
+    const size_t p = (size_t)y * W + x;
+    const unsigned had = reset ? 0u : (unsigned)((const uint16_t*)(acc + p))[3];
+    saturated = had + (unsigned)count > 256u;
+    if (!saturated) {
+      unsigned rg = 0u, b = 0u;
+      for (int k = 0; k < count; ++k) {   // uniform
+        unsigned srg, sb;
+        sample_shoot<kCuda>(sc, cam, (x << lg) + pat_entry(pat.x, (unsigned)k),
+                            (y << lg) + pat_entry(pat.y, (unsigned)k), maxrec, zcount, srg, sb);
+        rg += srg;
+        b += sb;
+      }
+      uint2 rec = make_uint2(0u, 0u);
+      if (!reset) rec = acc[p];
+      rec.x += rg;
+      rec.y += b + ((unsigned)count << 16);
+      acc[p] = rec;
+      uint8_t r8, g8, b8;
+      accum_resolve_px(rec, r8, g8, b8);
+      tile_put_rgb(tb, lx, ly, r8, g8, b8, out + p * 3);
+    } else if (RC_TILE_STAGE) {   // the staged tile's whole-row stores write this pixel too
+      const uint8_t* q = out + p * 3;
+      tile_put_rgb(tb, lx, ly, q[0], q[1], q[2], out + p * 3);
+    }
+  }
+  accum_count_saturated(saturated, sat);
+  if (!tile_last_wave(tb)) return;
+  const int nx = W - x0 < kTileW ? W - x0 : kTileW;
+  tile_write_rows<kTileW * 3 / 4>(tb.rgb, [&](int q) -> uint8_t* {
+    return y0 + q < H ? out + ((size_t)(y0 + q) * W + x0) * 3 : nullptr;
+  }, nx * 3);
+}
+
+// Masked pass: over k_aa_mark's list like k_pattern_list, one lane per listed pixel (64 a wave
+// step); the list's length is read from device memory and the grid is a fixed number of
+// workgroups whose waves stride over the list.  A wave's trip count depends on the wave alone, so
+// every lane reaches the ballot.  A listed pixel is in the list once, so its record and its three
+// bytes have one writer.
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_list(
+    Scene sc, Cam cam, int W, int lg, int count, PatWords pat, int maxrec,
+    const uint32_t* __restrict__ list, const unsigned* __restrict__ nlist,
+    uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
+    unsigned* __restrict__ sat) {
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  const unsigned n = *nlist;
+  if (n == 0u) return;   // uniform over the grid: an empty list costs its launch
+  stage_scene<kStage>(sc, stage);   // its barrier comes before the loop: every thread is here
+  const int lane = threadIdx.x & 63;
+  // wave-uniform by construction: told to the compiler, so the loop's counters stay scalar
+  const unsigned wave =
+      __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
+  const unsigned step = gridDim.x * (kBlock / 64) * 64u;   // <= 4096 * 4 * 64
+  // 64-bit index: n + step may pass 2^32
+  for (unsigned long long first = (unsigned long long)wave * 64u; first < n; first += step) {
+    const unsigned long long e = first + (unsigned)lane;
+    bool saturated = false;
+    if (e < n) {
+      const unsigned p = list[e];
+      saturated = (unsigned)((const uint16_t*)(acc + p))[3] + (unsigned)count > 256u;
+      if (!saturated) {
+        const int xs = (int)((p % (unsigned)W) << lg), ys = (int)((p / (unsigned)W) << lg);
+        unsigned rg = 0u, b = 0u;
+        for (int k = 0; k < count; ++k) {   // uniform
+          unsigned srg, sb;
+          sample_shoot<kCuda>(sc, cam, xs + pat_entry(pat.x, (unsigned)k),
+                              ys + pat_entry(pat.y, (unsigned)k), maxrec, zcount, srg, sb);
+          rg += srg;
+          b += sb;
+        }
+        // the entry is read again (opaque index) rather than kept in a register across shoot, as
+        // in k_aa_refine
+        unsigned l = (unsigned)lane;
+        asm volatile("" : "+v"(l));
+        const size_t q = list[first + l];
+        uint2 rec = acc[q];
+        rec.x += rg;
+        rec.y += b + ((unsigned)count << 16);
+        acc[q] = rec;
+        uint8_t r8, g8, b8;
+        accum_resolve_px(rec, r8, g8, b8);
+        uint8_t* o = out + q * 3;
+        o[0] = r8;
+        o[1] = g8;
+        o[2] = b8;
+      }
+    }
+    accum_count_saturated(saturated, sat);
+  }
+}
+
+// out = res(acc) for every pixel, nothing shot: 8 bytes in and 3 out a pixel, memory-bound.
+__global__ void __launch_bounds__(256) k_accum_resolve(const uint2* __restrict__ acc,
+                                                       unsigned long long pixels,
+                                                       uint8_t* __restrict__ out) {
+  const unsigned long long p = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+  if (p >= pixels) return;
+  uint8_t r8, g8, b8;
+  accum_resolve_px(acc[p], r8, g8, b8);
+  uint8_t* o = out + p * 3;
+  o[0] = r8;
+  o[1] = g8;
+  o[2] = b8;
+}
+
+int accum_supported(int W, int H, int g, bool listed) {
+  if (pattern_log2(g, 1, 3) < 0) return 0;
+  if (W <= 0 || H <= 0 || W > (1 << 28) / g || H > (1 << 28) / g) return 0;   // g*W, g*H within int
+  if (!listed) {   // k_render's tiles: grid.y, and xcd_tile's int tile index
+    const unsigned long long tx = ((unsigned)W + kTileW - 1) / kTileW;
+    const unsigned long long ty = ((unsigned)H + kTileH - 1) / kTileH;
+    return ty <= 65535ull && tx * ty <= 0x7fffffffull;
+  }
+  if ((unsigned long long)W * (unsigned long long)H >= (1ull << 32)) return 0;   // uint32 entries
+  const unsigned long long mx = ((unsigned long long)W + kMarkBlock - 1) / kMarkBlock;
+  const unsigned long long my = ((unsigned long long)H + kMarkRows - 1) / kMarkRows;
+  return mx * my <= 0x7fffffffull;   // k_aa_mark's grid
+}
+
+int accum_list_blocks(int W, int H, int cus, int want) { return list_blocks(W, H, 1, cus, want); }
+
+hipError_t launch_accum(const LaunchScene& s, int W, int H, int g, int count, const uint8_t* px,
+                        const uint8_t* py, bool reset, int maxrec, void* acc, uint8_t* out,
+                        unsigned long long* zcount, unsigned* sat, hipStream_t stream,
+                        bool cuda_sem) {
+  if (!accum_supported(W, H, g, false) || count < 1 || count > 16) return hipErrorInvalidValue;
+  const int lg = pattern_log2(g, 1, 3);
+  dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, W * g, H * g);   // the camera of the g*W x g*H image
+  const PatWords pat = pattern_words(count, px, py);
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_accum<cuda.value, st.value>), grid, dim3(kBlock), 0, stream, sc, cam, W,
+                       H, lg, count, pat, reset ? 1 : 0, maxrec, (uint2*)acc, out, zcount, sat);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_accum_list(const LaunchScene& s, int W, int H, int g, int count,
+                             const uint8_t* px, const uint8_t* py, int maxrec,
+                             const uint32_t* list, const unsigned* nlist, void* acc, uint8_t* out,
+                             unsigned long long* zcount, unsigned* sat, int blocks,
+                             hipStream_t stream, bool cuda_sem) {
+  if (!accum_supported(W, H, g, true) || count < 1 || count > 16 || blocks < 1 || blocks > 4096)
+    return hipErrorInvalidValue;
+  const int lg = pattern_log2(g, 1, 3);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, W * g, H * g);   // the camera of the g*W x g*H image
+  const PatWords pat = pattern_words(count, px, py);
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_accum_list<cuda.value, st.value>), dim3((unsigned)blocks), dim3(kBlock),
+                       0, stream, sc, cam, W, lg, count, pat, maxrec, list, nlist, (uint2*)acc,
+                       out, zcount, sat);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_accum_resolve(const void* acc, int W, int H, uint8_t* out, hipStream_t stream) {
+  if (W <= 0 || H <= 0) return hipErrorInvalidValue;
+  const unsigned long long pixels = (unsigned long long)W * (unsigned long long)H;
+  const unsigned long long blocks = (pixels + 255) / 256;
+  if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_accum_resolve, dim3((unsigned)blocks), dim3(256), 0, stream,
+                     (const uint2*)acc, pixels, out);
+  return hipGetLastError();
+}
+
 }  // namespace rc

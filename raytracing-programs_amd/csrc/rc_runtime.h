@@ -161,7 +161,7 @@ struct Pipe {
 };
 
 // The sampling features whose frames leave phase spans behind (DevCtx::span_ev).
-enum SpanOwner { kSpanAdaptive, kSpanRates, kSpanFilter, kSpanPattern, kSpanOwners };
+enum SpanOwner { kSpanAdaptive, kSpanRates, kSpanFilter, kSpanPattern, kSpanAccum, kSpanOwners };
 
 // The last list-refined frame of one feature on a device (adaptive supersampling, a pattern
 // frame with a threshold): what its stats getter reads.
@@ -172,6 +172,21 @@ struct ListFrame {
   bool valid = false;          // such a frame has been enqueued on this device
   long long pixels = 0;        // its W*H
   int rays = 0;                // rays per refined pixel
+};
+
+// The last accumulation call of a device (rc_accum_pass_device: one pass; rc_render_accum: all
+// of its passes): what rc_accum_stats_get reads.  Pass k owns slot k of the counter block, two
+// words {pixels listed by the edge list, saturated pixels}, so no pass waits for the host; the
+// block is the call's own, so the counts outlive the other sampling features' frames.
+struct AccumFrame {
+  static constexpr int kSlots = 128;   // >= 4 dense chunks + 63 single-sample passes
+  DevBuf count;                // kSlots * 8 bytes, zeroed on the call's stream before its passes
+  hipEvent_t done = nullptr;   // behind the call's last pass
+  bool valid = false;          // such a call has been enqueued on this device
+  long long pixels = 0;        // its W*H
+  int passes = 0;
+  uint8_t samples[kSlots] = {};   // per pass: its sample count
+  bool listed[kSlots] = {};       // per pass: it ran over the edge list (threshold > 0)
 };
 
 struct DevCtx {
@@ -211,16 +226,24 @@ struct DevCtx {
   // neither the counter nor pat.done is used.
   ListFrame pat;
   int pat_t = 0;
+  // progressive supersampling: rc_render_accum's accumulator (rc_accum_pass_device's is the
+  // caller's); a masked pass's edge list lives in aa_list; `acc` is the last call's record
+  DevBuf accum_px;
+  AccumFrame acc;
   // The event set whose spans each sampling feature's rc_*_phase_ms may still read, null once
   // another frame has recorded that set anew (claim_event_set).  adaptive: [0] start, [2]
   // one-ray image, [3] list, [1] refinement; rates: [0] start, [2] the rate-1 pass, [1] the
   // refinement; filter (a timed two-pass frame): [0] start, filt_mid between the s*W x s*H image
   // and its filter, [filt_end] behind the filter; pattern: [0] start, [1] end, and with a
-  // threshold (pat_ev_listed) [2] [3] as adaptive.
+  // threshold (pat_ev_listed) [2] [3] as adaptive; accumulation: [0] start and [1] end of the
+  // call, [acc_ev_first] the start of its last pass and, when that pass ran over the edge list
+  // (acc_ev_listed), [3] behind the list.
   hipEvent_t* span_ev[kSpanOwners] = {};
   hipEvent_t filt_mid = nullptr;
   int filt_end = 1;
   bool pat_ev_listed = false;
+  int acc_ev_first = 0;
+  bool acc_ev_listed = false;
   uint8_t* stage[2] = {nullptr, nullptr};   // pinned bounce buffers of copy_to_host
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   FrameBufs fb;        // scene, counter and parity workspace of the plain path
