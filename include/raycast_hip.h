@@ -135,6 +135,11 @@ _Static_assert(sizeof(light_t) == 72, "light_t must match C/objects.h layout");
  *                    1..255 for the edge pixels only; fast and cuda mode, RAYCAST_SSAA unset or
  *                    1.  An unknown name, a bad t, parity mode or RAYCAST_SSAA 2, 4 or 8 set as
  *                    well: a warning, ignored
+ *   RAYCAST_WINDOW = FWxFH+X0+Y0: the image asked for is the window at (X0, Y0) of the FW x FH
+ *                    image (rc_window below; fast and cuda mode, RAYCAST_SSAA 1, 2, 4 or 8).
+ *                    Malformed, parity mode, RAYCAST_SSAA_ADAPTIVE, RAYCAST_PATTERN,
+ *                    RAYCAST_FILTER=tent, RAYCAST_GPUS > 1 or a window the image does not hold:
+ *                    a warning, ignored
  *   RAYCAST_STATS = 1: one JSON metrics line on stderr
  * Any HIP failure prints a message to stderr and exit(1)s (reference error convention). */
 void raycast(json_data_t *json_struct, PPMFormat photo_data);
@@ -558,6 +563,85 @@ int rc_accum_stats_get(rc_accum_stats *out);
  * device: ms[0] the edge list (0 for a pass that takes every pixel), ms[1] the samples.  Returns
  * -1 if there was none. */
 int rc_accum_phase_ms(double ms[2]);
+
+/* Windows of a virtual image: pan, zoom and tiles (rc_render_window, rc_render_window_device,
+ * rc_accum_pass_window_device; fast and cuda mode).  Every other entry renders the whole picture
+ * the scene's camera defines (origin (0,0,0), view plane camera_width x camera_height at z = -1,
+ * C/raycast.c:80-81,115-117).  A window is a rectangle of a virtual full_w x full_h image: the
+ * caller chooses which part of the picture to look at and at which magnification, and only that
+ * part is shot.  A 7x zoom of a W x H frame is a W x H window of the 7W x 7H image; a poster too
+ * large for the device is rendered tile by tile; tiles go to any number of streams or devices.
+ * Fix the scene, the mode (fast or cuda) and the depth.
+ * Plain rendering.  Let V_s be that mode's full_w x full_h image with ssaa = s, s in {1, 2, 4, 8}:
+ *     the box filter of the s*full_w x s*full_h image B, as in rc_options.ssaa's contract above.
+ *     A window call with output size W x H stores  out[y][x] = V_s[y0 + y][x0 + x].
+ *     The virtual pixel is (x0 + x, y0 + y) and the pixel size is cam / (float)(s*full_w) (and
+ *     full_h): nothing else changes, so a window is a crop of the image the reference produces
+ *     at that size, whatever the size (full_w = 33 554 433 is as good as 97).
+ * Accumulation.  rc_accum_pass_device's contract above holds word for word with one substitution:
+ *     B_g is the g*full_w x g*full_h image, and sample k of window pixel (x, y) is
+ *     B_g[g*(y0 + y) + y[k]][g*(x0 + x) + x[k]].  The active set, the contrast (3 x 3, clipped to
+ *     the window, read from `out` as it stands), saturation, res, reset and the counters are
+ *     unchanged; acc and out are the window's own W x H.
+ * Window independence.  After a reset pass and t = 0 passes covering seq[0..k), the record of
+ *     virtual pixel (X, Y) does not depend on the window it was rendered through.  So a viewer that
+ *     pans by whole pixels keeps the overlap's records, moving them itself, and renders only the
+ *     exposed strip, as a window of its own.  With t > 0 the contrast of a window's border pixels
+ *     is clipped to the window, so their membership in the active set depends on the window.
+ * Identity window.  full = (W, H), origin (0, 0) gives the bytes of rc_render_device (whole image,
+ *     the same ssaa) and of rc_accum_pass_device.
+ * rc_timing.zero_normalize counts the rays actually shot (the window's).
+ * On the device: one kernel over the window's own subsample grid, one lane per subsample, the
+ * s x s subsamples of a pixel on adjacent lanes of a wave, reduced in registers; the subsample
+ * image is never stored, in cuda mode either (whose plain ssaa stores it).  The accumulation
+ * kernels are rc_accum_pass_device's with the origin added to the pixel.
+ * rc_options: mode fast or cuda; ssaa a plain factor 0, 1, 2, 4 or 8 (accumulation: 0 or 1, the
+ * sequence carries g); max_recursion as everywhere.
+ * Refused, each with a message and -1, from the arguments alone (before any device work): parity
+ * mode (a window of its image depends on the scan-order carry of every pixel before it); a
+ * threshold in opt->ssaa (adaptive refinement of a window is an accumulation pass with t > 0); a
+ * factor outside 0, 1, 2, 4, 8; num_gpus > 1; null pointers; full_w, full_h, W or H below 1; x0 or
+ * y0 negative; x0 + W > full_w or y0 + H > full_h (tested without overflow); s*full_w or s*full_h
+ * (g for accumulation) above 2^31 - 1; more than 65535 rows of 16-subsample tiles in the window's
+ * own s*H subsample rows (or 2^31 - 1 tiles in all).  For accumulation every refusal of
+ * rc_accum_pass_device applies as it does there, on W and H.
+ * rc_frame_submit, rc_render_sharded, the rate-map, pattern and filtered entries, rc_render_accum
+ * (it owns a whole-image state) and rc_accum_resolve_device (it has no camera in it) take no
+ * window.  raycast() takes one through
+ *   RAYCAST_WINDOW = FWxFH+X0+Y0   (four decimal numbers): the W x H image raycast() is asked for
+ *                    is the window at (X0, Y0) of the FW x FH image, in fast and cuda mode with
+ *                    RAYCAST_SSAA 1, 2, 4 or 8, so bin/raytrace writes the tiles of a poster one
+ *                    at a time.  Malformed, parity mode, RAYCAST_SSAA_ADAPTIVE, RAYCAST_PATTERN,
+ *                    RAYCAST_FILTER=tent, RAYCAST_GPUS > 1 or a window that fails
+ *                    rc_window_check: a warning, ignored (the whole frame is rendered). */
+typedef struct rc_window {
+  int32_t full_w, full_h;   /* the virtual image                      */
+  int32_t x0, y0;           /* the window's top left pixel inside it   */
+} rc_window;
+_Static_assert(sizeof(rc_window) == 16, "rc_window layout (ctypes binding)");
+/* 0 when a W x H window at *w can be rendered at factor s (0 counts as 1), else -1 with a message
+ * naming the rule broken. */
+int rc_window_check(const rc_window *w, int width, int height, int s);
+/* raycast()'s reading of RAYCAST_WINDOW for a width x height frame against the options
+ * rc_default_options(.., 1) gave: 1 and the window in *out when the frame goes through
+ * rc_render_window; 0 when unset, and 0 after one of the warnings above. */
+int rc_window_env(const rc_options *opt, int width, int height, rc_window *out);
+/* rc_render_window: host pixmap (W*H*3 bytes), synchronous, on opt->device.
+ * rc_render_window_device: device image on the current device and the given HIP stream (NULL: the
+ * library's stream of that device, as rc_render_device); asynchronous unless timing is requested.
+ * Both return 0 on success. */
+int rc_render_window(const rc_scene *scene, const rc_window *win, int width, int height,
+                     const rc_options *opt, uint8_t *pixmap, rc_timing *timing);
+int rc_render_window_device(const rc_scene *scene, const rc_window *win, int width, int height,
+                            const rc_options *opt, uint8_t *d_out, void *stream,
+                            rc_timing *timing);
+/* rc_accum_pass_device through a window: d_acc (W*H records) and d_out (W*H*3 bytes) are the
+ * window's own.  Its stats and phase getters are the accumulation family's (rc_accum_stats_get,
+ * rc_accum_phase_ms). */
+int rc_accum_pass_window_device(const rc_scene *scene, const rc_window *win, int width, int height,
+                                const rc_options *opt, const rc_sample_seq *seq, int first,
+                                int count, int threshold, int reset, rc_accum_px *d_acc,
+                                uint8_t *d_out, void *stream, rc_timing *timing);
 
 /* Frames in flight (an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out

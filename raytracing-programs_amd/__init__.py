@@ -143,6 +143,12 @@ class RcAccumStats(ctypes.Structure):
                 ("saturated", ctypes.c_int64), ("rays", ctypes.c_int64)]
 
 
+class RcWindow(ctypes.Structure):
+    """rc_window (16 bytes): the virtual image and the window's top left pixel inside it."""
+    _fields_ = [("full_w", ctypes.c_int32), ("full_h", ctypes.c_int32),
+                ("x0", ctypes.c_int32), ("y0", ctypes.c_int32)]
+
+
 def _hier_points(g):
     """hier<g> (include/raycast_hip.h, rc_sample_seq): point k is the bit-reversal r of k over
     2 * log2 g bits; x takes r's even bits and y its odd bits."""
@@ -236,7 +242,8 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_render_pattern_device", "rc_pattern_stats_get", "rc_pattern_phase_ms",
                "rc_sample_seq_builtin", "rc_sample_seq_check", "rc_accum_pass_device",
                "rc_accum_resolve_device", "rc_render_accum", "rc_accum_stats_get",
-               "rc_accum_phase_ms"]
+               "rc_accum_phase_ms", "rc_window_check", "rc_window_env", "rc_render_window",
+               "rc_render_window_device", "rc_accum_pass_window_device"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -404,6 +411,24 @@ def _hip_lib_locked():
                                     ctypes.POINTER(RcTiming)]
     lib.rc_accum_stats_get.argtypes = [ctypes.POINTER(RcAccumStats)]
     lib.rc_accum_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    lib.rc_window_check.argtypes = [ctypes.POINTER(RcWindow), ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int]
+    lib.rc_window_env.argtypes = [ctypes.POINTER(RcOptions), ctypes.c_int, ctypes.c_int,
+                                  ctypes.POINTER(RcWindow)]
+    lib.rc_render_window.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcWindow), ctypes.c_int,
+                                     ctypes.c_int, ctypes.POINTER(RcOptions), ctypes.c_void_p,
+                                     ctypes.POINTER(RcTiming)]
+    lib.rc_render_window_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcWindow),
+                                            ctypes.c_int, ctypes.c_int, ctypes.POINTER(RcOptions),
+                                            ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.POINTER(RcTiming)]
+    lib.rc_accum_pass_window_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcWindow),
+                                                ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(RcOptions),
+                                                ctypes.POINTER(RcSampleSeq), ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.POINTER(RcTiming)]
     _hip = lib
     return lib
 
@@ -1231,6 +1256,141 @@ def accum_phase_ms():
     if hip_lib().rc_accum_phase_ms(ms) != 0:
         raise RuntimeError("rc_accum_phase_ms: no accumulation call on this device")
     return {"mark": ms[0], "shoot": ms[1]}
+
+
+def _window(window, width, height, s=1):
+    """The checked (full_w, full_h, x0, y0) of a width x height window at factor s (the rules of
+    rc_window_check that do not depend on the kernels' grids, stated here so that they hold
+    without the library); raises ValueError naming the rule."""
+    fw, fh, x0, y0 = (int(v) for v in window)
+    w, h, s = int(width), int(height), int(s)
+    if s not in (1, 2, 4, 8):
+        raise ValueError(f"window: factor {s} is not 1, 2, 4 or 8")
+    if fw < 1 or fh < 1 or w < 1 or h < 1:
+        raise ValueError(f"window: a {w} x {h} window of a {fw} x {fh} image: sizes below 1")
+    if x0 < 0 or y0 < 0:
+        raise ValueError(f"window: origin ({x0}, {y0}) is negative")
+    if x0 + w > fw or y0 + h > fh:
+        raise ValueError(f"window: {w} x {h} at ({x0}, {y0}) reaches outside {fw} x {fh}")
+    if s * fw > 2 ** 31 - 1 or s * fh > 2 ** 31 - 1:
+        raise ValueError(f"window: {s} times {fw} x {fh} passes 2^31 - 1")
+    return fw, fh, x0, y0
+
+
+def _rc_window(window):
+    win = RcWindow()
+    win.full_w, win.full_h, win.x0, win.y0 = (int(v) for v in window)
+    return win
+
+
+def window_check(window, width, height, s=1):
+    """rc_window_check: True when the library renders that window at factor s (its message goes
+    to stderr otherwise)."""
+    win = _rc_window(window)
+    return hip_lib().rc_window_check(ctypes.byref(win), int(width), int(height), int(s)) == 0
+
+
+def window_crop(img, s, window, width, height):
+    """The window contract (include/raycast_hip.h, rc_window) in numpy: the rows s*y0 ..
+    s*(y0 + H) and columns s*x0 .. s*(x0 + W) of an [s*full_h, s*full_w, C] image, so with s = 1
+    out[y][x] = img[y0 + y][x0 + x], and with s = g the [g*H, g*W, C] image whose samples an
+    accumulation pass through the window takes."""
+    img = np.asarray(img)
+    fw, fh, x0, y0 = _window(window, width, height, s)
+    s = int(s)
+    if img.ndim != 3 or img.shape[0] != s * fh or img.shape[1] != s * fw:
+        raise ValueError(f"window_crop: an [{s * fh}, {s * fw}, C] image, got {img.shape}")
+    return img[s * y0:s * (y0 + int(height)), s * x0:s * (x0 + int(width))]
+
+
+def window_tiles(full_w, full_h, tw, th):
+    """The windows that cover a full_w x full_h image in tiles of tw x th, row by row, the last
+    column and row clipped: [((full_w, full_h, x0, y0), W, H), ...]."""
+    full_w, full_h, tw, th = int(full_w), int(full_h), int(tw), int(th)
+    if full_w < 1 or full_h < 1 or tw < 1 or th < 1:
+        raise ValueError(f"window_tiles: {full_w} x {full_h} in tiles of {tw} x {th}")
+    return [((full_w, full_h, x0, y0), min(tw, full_w - x0), min(th, full_h - y0))
+            for y0 in range(0, full_h, th) for x0 in range(0, full_w, tw)]
+
+
+def window_for_zoom(width, height, zoom, cx, cy):
+    """The W x H window of the zoom*W x zoom*H image (an integer zoom >= 1) centred on pixel
+    (cx, cy) of the unzoomed W x H frame, clamped to the frame: the window's pixel (W // 2, H // 2)
+    is the virtual pixel (zoom*cx + zoom // 2, zoom*cy + zoom // 2) unless the clamp moved it."""
+    w, h, z, cx, cy = int(width), int(height), int(zoom), int(cx), int(cy)
+    if w < 1 or h < 1 or z < 1 or not (0 <= cx < w and 0 <= cy < h):
+        raise ValueError(f"window_for_zoom: zoom {z} on pixel ({cx}, {cy}) of a {w} x {h} frame")
+    x0 = min(max(z * cx + z // 2 - w // 2, 0), z * w - w)
+    y0 = min(max(z * cy + z // 2 - h // 2, 0), z * h - h)
+    return z * w, z * h, x0, y0
+
+
+def render_window(scene, window, width, height, ssaa=1, depth=6, mode="fast", device=0,
+                  timing=None, out=None):
+    """rc_render_window: the W x H window at window = (full_w, full_h, x0, y0) of the full_w x
+    full_h image of that mode with that ssaa (window_crop of it, s = 1).  Fast and cuda mode."""
+    lib = hip_lib()
+    win = _rc_window(window)
+    out = _pixmap(out, width, height)
+    t = RcTiming()
+    opt = options(depth, mode, 1, device, ssaa)
+    rc = lib.rc_render_window(scene.packed(), ctypes.byref(win), width, height, ctypes.byref(opt),
+                              out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
+    if rc != 0:
+        raise RuntimeError("rc_render_window failed (see stderr)")
+    _timing_back(timing, t)
+    return out
+
+
+def render_window_device(scene, window, width, height, d_out_ptr, ssaa=1, stream_ptr=None,
+                         depth=6, mode="fast", timing=None):
+    """rc_render_window_device: the window's image (W*H*3 bytes) is device memory; enqueued on the
+    stream and asynchronous unless `timing` is given."""
+    lib = hip_lib()
+    win = _rc_window(window)
+    opt = options(depth, mode, ssaa=ssaa)
+    t = RcTiming()
+    rc = lib.rc_render_window_device(scene.packed(), ctypes.byref(win), width, height,
+                                     ctypes.byref(opt), ctypes.c_void_p(d_out_ptr),
+                                     ctypes.c_void_p(stream_ptr or 0),
+                                     ctypes.byref(t) if timing is not None else None)
+    if rc != 0:
+        raise RuntimeError("rc_render_window_device failed (see stderr)")
+    _timing_back(timing, t)
+
+
+def accum_pass_window_device(scene, window, width, height, seq, first, count, d_acc_ptr,
+                             d_out_ptr, threshold=0, reset=False, stream_ptr=None, depth=6,
+                             mode="fast", timing=None):
+    """rc_accum_pass_window_device: accum_pass_device with the samples of the window at window =
+    (full_w, full_h, x0, y0) of the virtual image (accum_step on window_crop of its g*full_w x
+    g*full_h image, s = g); the accumulator and the image are the window's own W x H."""
+    lib = hip_lib()
+    win = _rc_window(window)
+    s = _rc_sample_seq(seq)
+    opt = options(depth, mode)
+    t = RcTiming()
+    rc = lib.rc_accum_pass_window_device(scene.packed(), ctypes.byref(win), width, height,
+                                         ctypes.byref(opt), ctypes.byref(s), int(first),
+                                         int(count), int(threshold), 1 if reset else 0,
+                                         ctypes.c_void_p(d_acc_ptr), ctypes.c_void_p(d_out_ptr),
+                                         ctypes.c_void_p(stream_ptr or 0),
+                                         ctypes.byref(t) if timing is not None else None)
+    if rc != 0:
+        raise RuntimeError("rc_accum_pass_window_device failed (see stderr)")
+    _timing_back(timing, t)
+
+
+def window_from_env(width, height, mode="fast", ssaa=1, adaptive=0, gpus=1):
+    """raycast()'s reading of RAYCAST_WINDOW (rc_window_env) for a width x height frame of that
+    mode, factor, adaptive threshold and GPU count: (full_w, full_h, x0, y0) when the frame goes
+    through the window path, None when it does not (the warnings go to stderr)."""
+    win = RcWindow()
+    opt = options(mode=mode, gpus=gpus, ssaa=ssaa, adaptive=adaptive)
+    if hip_lib().rc_window_env(ctypes.byref(opt), int(width), int(height),
+                               ctypes.byref(win)) != 1:
+        return None
+    return win.full_w, win.full_h, win.x0, win.y0
 
 
 SPIN_SITES = ("team_handoff", "phase_c_carry_in", "ready_queue", "helper_queue")

@@ -1247,6 +1247,137 @@ static int accum_refused(const char* who, const rc_options* opt, int W, int H,
   return 0;
 }
 
+// ------------------------------------------------------- windows of a virtual image --
+int rc_window_check(const rc_window* w, int W, int H, int s) {
+  const char* who = "rc_window_check";
+  if (!w) {
+    std::fprintf(stderr, "Error: %s: a null window\n", who);
+    return -1;
+  }
+  if (s == 0) s = 1;   // as rc_options.ssaa
+  if (s != 1 && s != 2 && s != 4 && s != 8) {
+    std::fprintf(stderr, "Error: %s: factor %d is not 0, 1, 2, 4 or 8\n", who, s);
+    return -1;
+  }
+  if (w->full_w < 1 || w->full_h < 1 || W < 1 || H < 1) {
+    std::fprintf(stderr, "Error: %s: a %d x %d window of a %d x %d image: every size must be at "
+                 "least 1\n", who, W, H, w->full_w, w->full_h);
+    return -1;
+  }
+  if (w->x0 < 0 || w->y0 < 0) {
+    std::fprintf(stderr, "Error: %s: origin (%d, %d): a window starts inside the image, at 0 or "
+                 "above\n", who, w->x0, w->y0);
+    return -1;
+  }
+  // W > full_w - x0 rather than x0 + W > full_w: no sum that could overflow
+  if (w->x0 > w->full_w || W > w->full_w - w->x0 || w->y0 > w->full_h || H > w->full_h - w->y0) {
+    std::fprintf(stderr, "Error: %s: a %d x %d window at (%d, %d) reaches outside the %d x %d "
+                 "image\n", who, W, H, w->x0, w->y0, w->full_w, w->full_h);
+    return -1;
+  }
+  if (w->full_w > 0x7fffffff / s || w->full_h > 0x7fffffff / s) {
+    std::fprintf(stderr, "Error: %s: %d times %d x %d: the subsample image's sides must stay "
+                 "within 2^31 - 1\n", who, s, w->full_w, w->full_h);
+    return -1;
+  }
+  if (!rc::window_supported(rc::Window{w->full_w, w->full_h, w->x0, w->y0}, W, H, s)) {
+    std::fprintf(stderr, "Error: %s: a %d x %d window at factor %d is too large for the kernel's "
+                 "grid (at most 65535 rows of 16-subsample tiles, 2^31 - 1 tiles)\n", who, W, H, s);
+    return -1;
+  }
+  return 0;
+}
+
+// one decimal field of RAYCAST_WINDOW: digits only, within int; *p moves behind it
+static bool window_field(const char** p, int* out) {
+  const char* q = *p;
+  long long v = 0;
+  if (*q < '0' || *q > '9') return false;
+  for (; *q >= '0' && *q <= '9'; ++q) {
+    v = v * 10 + (*q - '0');
+    if (v > 0x7fffffffll) return false;
+  }
+  *p = q;
+  *out = (int)v;
+  return true;
+}
+
+int rc_window_env(const rc_options* opt, int W, int H, rc_window* out) {
+  const char* v = std::getenv("RAYCAST_WINDOW");
+  if (!v || !opt || !out) return 0;
+  rc_window w;
+  const char* p = v;
+  int f[4] = {0, 0, 0, 0};
+  bool ok = window_field(&p, &f[0]);
+  const char seps[3] = {'x', '+', '+'};
+  for (int k = 0; ok && k < 3; ++k) ok = *p++ == seps[k] && window_field(&p, &f[k + 1]);
+  if (!ok || *p != '\0') {
+    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' is not FWxFH+X0+Y0 (four decimal numbers), "
+                 "ignored\n", v);
+    return 0;
+  }
+  w.full_w = f[0], w.full_h = f[1], w.x0 = f[2], w.y0 = f[3];
+  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
+    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' is for fast and cuda mode (a window of a "
+                 "parity image depends on the scan-order carry of every pixel before it), "
+                 "ignored\n", v);
+    return 0;
+  }
+  if (RC_SSAA_THRESHOLD(opt->ssaa) > 0) {
+    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' does not combine with "
+                 "RAYCAST_SSAA_ADAPTIVE, ignored\n", v);
+    return 0;
+  }
+  const char* pat = std::getenv("RAYCAST_PATTERN");
+  if (pat && pat[0]) {
+    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' does not combine with RAYCAST_PATTERN, "
+                 "ignored\n", v);
+    return 0;
+  }
+  const char* filt = std::getenv("RAYCAST_FILTER");
+  if (filt && !std::strcmp(filt, "tent")) {
+    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' does not combine with RAYCAST_FILTER=tent, "
+                 "ignored\n", v);
+    return 0;
+  }
+  if (opt->num_gpus > 1) {
+    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' does not combine with RAYCAST_GPUS %d (the "
+                 "row shards take no window), ignored\n", v, opt->num_gpus);
+    return 0;
+  }
+  if (rc_window_check(&w, W, H, RC_SSAA_FACTOR(opt->ssaa))) {
+    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' does not hold a %d x %d window, ignored\n",
+                 v, W, H);
+    return 0;
+  }
+  *out = w;
+  return 1;
+}
+
+// What the window render entry points refuse from their arguments alone.
+static int window_refused(const char* who, const rc_options* opt, const rc_window* win, int W,
+                          int H) {
+  const int ss = ssaa_factor(opt, who);
+  if (ss < 0) return -1;   // ssaa_decode has said why
+  if (ssaa_threshold(opt, who) > 0) {
+    std::fprintf(stderr, "Error: %s: ssaa %d carries an adaptive threshold: adaptive refinement of "
+                 "a window is an accumulation pass with a threshold "
+                 "(rc_accum_pass_window_device)\n", who, opt->ssaa);
+    return -1;
+  }
+  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
+    std::fprintf(stderr, "Error: %s: windows are for fast and cuda mode: a window of a parity "
+                 "image depends on the scan-order carry of every pixel before it\n", who);
+    return -1;
+  }
+  if (opt->num_gpus > 1) {
+    std::fprintf(stderr, "Error: %s: num_gpus %d: the row shards take no window\n", who,
+                 opt->num_gpus);
+    return -1;
+  }
+  return rc_window_check(win, W, H, ss);
+}
+
 void rc_default_options(rc_options* opt, int use_env) {
   opt->max_recursion = 7;   // C/raycast.c:14
   opt->mode = RC_MODE_PARITY;
@@ -1937,9 +2068,13 @@ struct AccumPass {
 // AccumFrame::kSlots passes).  A pass over every pixel is one launch; a masked pass is the
 // adaptive path's edge list (launch_aa_mark over d_out into aa_list) and the list kernel.
 // Nothing waits for the host: pass k counts into slot k of the call's counter block.
+// win (or null): the samples are those of this window of a virtual image (it has passed
+// rc_window_check at the sequence's g); the edge list, the records and the image stay the
+// window's own W x H.
 static int enqueue_accum(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
                          const rc_sample_seq* seq, const AccumPass* passes, int npasses,
-                         rc_accum_px* d_acc, uint8_t* d_out, hipStream_t stream) {
+                         rc_accum_px* d_acc, uint8_t* d_out, hipStream_t stream,
+                         const rc_window* win = nullptr) {
   bool masked = false;
   for (int k = 0; k < npasses; ++k) masked = masked || passes[k].at > 0;
   auto prepare = [&]() -> int {
@@ -1962,6 +2097,8 @@ static int enqueue_accum(DevCtx& c, const rc_scene* s, int W, int H, const rc_op
     HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)npasses * 8, stream));
     const int maxrec = opt->max_recursion, g = seq->grid;
     const bool cuda = opt->mode == RC_MODE_CUDA;
+    const rc::Window vw = win ? rc::Window{win->full_w, win->full_h, win->x0, win->y0}
+                              : rc::Window{W, H, 0, 0};
     hipEvent_t* ev = claim_event_set(c, kSpanAccum, false, true);
     HIP_TRY(hipEventRecord(ev[0], stream));
     for (int k = 0; k < npasses; ++k) {
@@ -1972,14 +2109,22 @@ static int enqueue_accum(DevCtx& c, const rc_scene* s, int W, int H, const rc_op
       const uint8_t* py = seq->y + p.first;
       unsigned* slot = cnt + 2 * k;
       if (p.at == 0) {
-        HIP_TRY(rc::launch_accum(ls, W, H, g, p.count, px, py, p.reset, maxrec, d_acc, d_out, zc,
-                                 slot + 1, stream, cuda));
+        if (win)
+          HIP_TRY(rc::launch_accum_window(ls, vw, W, H, g, p.count, px, py, p.reset, maxrec, d_acc,
+                                          d_out, zc, slot + 1, stream, cuda));
+        else
+          HIP_TRY(rc::launch_accum(ls, W, H, g, p.count, px, py, p.reset, maxrec, d_acc, d_out, zc,
+                                   slot + 1, stream, cuda));
       } else {
         HIP_TRY(rc::launch_aa_mark(d_out, W, H, p.at, list, slot, stream));
         if (last) HIP_TRY(hipEventRecord(ev[3], stream));
-        HIP_TRY(rc::launch_accum_list(
-            ls, W, H, g, p.count, px, py, maxrec, list, slot, d_acc, d_out, zc, slot + 1,
-            rc::accum_list_blocks(W, H, c.cus, tune().adaptive_blocks), stream, cuda));
+        const int blocks = rc::accum_list_blocks(W, H, c.cus, tune().adaptive_blocks);
+        if (win)
+          HIP_TRY(rc::launch_accum_list_window(ls, vw, W, H, g, p.count, px, py, maxrec, list, slot,
+                                               d_acc, d_out, zc, slot + 1, blocks, stream, cuda));
+        else
+          HIP_TRY(rc::launch_accum_list(ls, W, H, g, p.count, px, py, maxrec, list, slot, d_acc,
+                                        d_out, zc, slot + 1, blocks, stream, cuda));
       }
       c.acc.samples[k] = (uint8_t)p.count;
       c.acc.listed[k] = p.at > 0;
@@ -1992,6 +2137,26 @@ static int enqueue_accum(DevCtx& c, const rc_scene* s, int W, int H, const rc_op
     c.span_ev[kSpanAccum] = ev;
     c.acc_ev_first = npasses > 1 ? 2 : 0;
     c.acc_ev_listed = passes[npasses - 1].at > 0;
+    return 0;
+  });
+}
+
+// One window frame on `stream` through the device's one-frame workspace (the caller holds c.mu
+// and has passed window_refused): one launch of k_window at the options' factor.
+static int enqueue_window(DevCtx& c, const rc_scene* s, const rc_window* win, int W, int H,
+                          const rc_options* opt, uint8_t* d_out, hipStream_t stream) {
+  return ws_frame(c, stream, [] { return 0; }, [&]() -> int {
+    rc::LaunchScene ls;
+    if (upload_scene(c.fb, stream, s, ls)) return -1;
+    unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
+    HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
+    hipEvent_t* ev = claim_event_set(c, kSpanWindow, false, true);
+    HIP_TRY(hipEventRecord(ev[0], stream));
+    HIP_TRY(rc::launch_window(ls, rc::Window{win->full_w, win->full_h, win->x0, win->y0}, W, H,
+                              ssaa_factor(opt, "rc_render_window"), opt->max_recursion, d_out, zc,
+                              stream, opt->mode == RC_MODE_CUDA));
+    HIP_TRY(hipEventRecord(ev[1], stream));
+    c.span_ev[kSpanWindow] = ev;
     return 0;
   });
 }
@@ -2440,10 +2605,11 @@ int rc_render_pattern(const rc_scene* s, int W, int H, const rc_options* opt,
   return finish_host(*c, opt, pixmap, bytes, tu, {false, false, kNoLog}, timing, t0);
 }
 
-int rc_accum_pass_device(const rc_scene* s, int W, int H, const rc_options* opt,
-                         const rc_sample_seq* seq, int first, int count, int threshold, int reset,
-                         rc_accum_px* d_acc, uint8_t* d_out, void* stream, rc_timing* timing) {
-  const char* who = "rc_accum_pass_device";
+// rc_accum_pass_device and rc_accum_pass_window_device (win: null for the former)
+static int accum_pass(const char* who, const rc_scene* s, const rc_window* win, int W, int H,
+                      const rc_options* opt, const rc_sample_seq* seq, int first, int count,
+                      int threshold, int reset, rc_accum_px* d_acc, uint8_t* d_out, void* stream,
+                      rc_timing* timing) {
   if (!s || !opt || !seq || !d_acc || !d_out) {
     std::fprintf(stderr, "Error: %s: a null pointer\n", who);
     return -1;
@@ -2453,6 +2619,7 @@ int rc_accum_pass_device(const rc_scene* s, int W, int H, const rc_options* opt,
     return -1;
   }
   if (accum_refused(who, opt, W, H, seq, threshold, threshold == 0, threshold > 0)) return -1;
+  if (win && rc_window_check(win, W, H, seq->grid)) return -1;
   if (count < 1 || count > 16 || first < 0 || first > seq->nsamples - count) {
     std::fprintf(stderr, "Error: %s: samples [%d, %d + %d) of a sequence of %d: a pass takes 1..16 "
                  "samples inside the sequence\n", who, first, first, count, seq->nsamples);
@@ -2468,8 +2635,67 @@ int rc_accum_pass_device(const rc_scene* s, int W, int H, const rc_options* opt,
   if (enter(kCurrentDevice, true, e)) return -1;
   hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
   const AccumPass pass{first, count, threshold, reset != 0};
-  if (enqueue_accum(*e.c, s, W, H, opt, seq, &pass, 1, d_acc, d_out, st)) return -1;
+  if (enqueue_accum(*e.c, s, W, H, opt, seq, &pass, 1, d_acc, d_out, st, win)) return -1;
   return finish_device(*e.c, opt, st, timing, kNoLog);
+}
+
+int rc_accum_pass_device(const rc_scene* s, int W, int H, const rc_options* opt,
+                         const rc_sample_seq* seq, int first, int count, int threshold, int reset,
+                         rc_accum_px* d_acc, uint8_t* d_out, void* stream, rc_timing* timing) {
+  return accum_pass("rc_accum_pass_device", s, nullptr, W, H, opt, seq, first, count, threshold,
+                    reset, d_acc, d_out, stream, timing);
+}
+
+int rc_accum_pass_window_device(const rc_scene* s, const rc_window* win, int W, int H,
+                                const rc_options* opt, const rc_sample_seq* seq, int first,
+                                int count, int threshold, int reset, rc_accum_px* d_acc,
+                                uint8_t* d_out, void* stream, rc_timing* timing) {
+  const char* who = "rc_accum_pass_window_device";
+  if (!win) {
+    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
+    return -1;
+  }
+  return accum_pass(who, s, win, W, H, opt, seq, first, count, threshold, reset, d_acc, d_out,
+                    stream, timing);
+}
+
+int rc_render_window_device(const rc_scene* s, const rc_window* win, int W, int H,
+                            const rc_options* opt, uint8_t* d_out, void* stream,
+                            rc_timing* timing) {
+  const char* who = "rc_render_window_device";
+  if (!s || !win || !opt || !d_out) {
+    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
+    return -1;
+  }
+  if (window_refused(who, opt, win, W, H)) return -1;
+  Entered e;
+  if (enter(kCurrentDevice, true, e)) return -1;
+  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
+  if (enqueue_window(*e.c, s, win, W, H, opt, d_out, st)) return -1;
+  return finish_device(*e.c, opt, st, timing, kNoLog);
+}
+
+int rc_render_window(const rc_scene* s, const rc_window* win, int W, int H, const rc_options* opt,
+                     uint8_t* pixmap, rc_timing* timing) {
+  const char* who = "rc_render_window";
+  if (!s || !win || !opt || !pixmap) {
+    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
+    return -1;
+  }
+  const auto t0 = HostClock::now();
+  if (window_refused(who, opt, win, W, H)) return -1;
+  if (timing) std::memset(timing, 0, sizeof *timing);
+  const rc_tuning tu = tune();
+  Entered e;
+  if (enter_host(opt, e)) return -1;
+  DevCtx* c = e.c;
+  const size_t bytes = (size_t)W * H * 3;
+  if (c->out.ensure(bytes)) {
+    std::fprintf(stderr, "Error: out of device memory for the image (%d x %d)\n", W, H);
+    return -1;
+  }
+  if (enqueue_window(*c, s, win, W, H, opt, (uint8_t*)c->out.p, c->stream)) return -1;
+  return finish_host(*c, opt, pixmap, bytes, tu, {false, false, kNoLog}, timing, t0);
 }
 
 int rc_accum_resolve_device(const rc_accum_px* d_acc, int W, int H, uint8_t* d_out, void* stream) {
@@ -3282,7 +3508,12 @@ void raycast(json_data_t* json_struct, PPMFormat photo_data) {
   int pat_t = 0;
   // RAYCAST_PATTERN (never together with a filter: that needs the RAYCAST_SSAA this refuses)
   const bool patterned = rc_pattern_env(&opt, &pat, &pat_t) == 1;
-  if (patterned ? rc_render_pattern(s, photo_data.width, photo_data.height, &opt, &pat, pat_t,
+  rc_window win;
+  // RAYCAST_WINDOW (never together with a pattern or the tent: rc_window_env ignores it then)
+  const bool windowed = rc_window_env(&opt, photo_data.width, photo_data.height, &win) == 1;
+  if (windowed ? rc_render_window(s, &win, photo_data.width, photo_data.height, &opt,
+                                  photo_data.pixmap, &t)
+      : patterned ? rc_render_pattern(s, photo_data.width, photo_data.height, &opt, &pat, pat_t,
                                     photo_data.pixmap, &t)
       : filtered ? rc_render_filtered(s, photo_data.width, photo_data.height, &opt, &filt,
                                       photo_data.pixmap, &t)

@@ -205,6 +205,35 @@ hipError_t launch_accum_resolve(const void* acc, int W, int H, uint8_t* out, hip
 // want > 0: that many; else from the CU count, at most the wave steps a W x H list can need
 int accum_list_blocks(int W, int H, int cus, int want);
 
+// Windows of a virtual image (rc_render_window*, rc_accum_pass_window_device; fast and cuda
+// modes): the W x H output is the rectangle at (x0, y0) of the full_w x full_h image, shot with
+// the camera of the s*full_w x s*full_h image (rc_window's fields).
+//   launch_window             the ssaa = s image of the window (s = 1, 2, 4 or 8), one lane per
+//                             subsample over the window's own subsample grid, nothing stored but
+//                             the W x H output;
+//   launch_accum_window       launch_accum with the window's origin (s = the sequence's g);
+//   launch_accum_list_window  launch_accum_list with it; list, acc and out are the window's own.
+// window_supported: s as above; the window inside the image, all sizes >= 1, the origin >= 0;
+// s*full_w and s*full_h within int; at most 65535 rows of tiles and 2^31 - 1 tiles in the window's
+// subsample grid.  The accumulation launchers add accum_supported(W, H, g, listed).  The launchers
+// return hipErrorInvalidValue for anything these refuse.
+struct Window {
+  int full_w, full_h, x0, y0;
+};
+int window_supported(const Window& w, int W, int H, int s);
+hipError_t launch_window(const LaunchScene& s, const Window& w, int W, int H, int ssaa, int maxrec,
+                         uint8_t* out, unsigned long long* zcount, hipStream_t stream,
+                         bool cuda_sem);
+hipError_t launch_accum_window(const LaunchScene& s, const Window& w, int W, int H, int g,
+                               int count, const uint8_t* px, const uint8_t* py, bool reset,
+                               int maxrec, void* acc, uint8_t* out, unsigned long long* zcount,
+                               unsigned* sat, hipStream_t stream, bool cuda_sem);
+hipError_t launch_accum_list_window(const LaunchScene& s, const Window& w, int W, int H, int g,
+                                    int count, const uint8_t* px, const uint8_t* py, int maxrec,
+                                    const uint32_t* list, const unsigned* nlist, void* acc,
+                                    uint8_t* out, unsigned long long* zcount, unsigned* sat,
+                                    int blocks, hipStream_t stream, bool cuda_sem);
+
 hipError_t launch_parity(const LaunchScene& s, int W, int H, int maxrec, uint8_t* out,
                          const ParityWork& w, unsigned long long* zcount, hipStream_t stream,
                          const hipEvent_t* ev);

@@ -4112,11 +4112,12 @@ __device__ __forceinline__ void accum_count_saturated(bool saturated, unsigned* 
 // not in a register across shoot) and the whole record once after them: one 8-byte load and one
 // 8-byte store a lane, adjacent lanes of a tile row adjacent in memory.  `reset`: the record is
 // not read at all and counts as zero.
+// (ox, oy): the window's origin in the virtual image, in pixels (k_accum: 0, 0; k_accum_win below).
 template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum(
-    Scene sc, Cam cam, int W, int H, int lg, int count, PatWords pat, int reset, int maxrec,
-    uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
-    unsigned* __restrict__ sat) {
+__device__ __forceinline__ void accum_dense(
+    Scene sc, Cam cam, int W, int H, int ox, int oy, int lg, int count, PatWords pat, int reset,
+    int maxrec, uint2* __restrict__ acc, uint8_t* __restrict__ out,
+    unsigned long long* __restrict__ zcount, unsigned* __restrict__ sat) {
   if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
   __shared__ StageBuf<kStage> stage;
   __shared__ TileBytes tb;
@@ -4138,8 +4139,9 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
       unsigned rg = 0u, b = 0u;
       for (int k = 0; k < count; ++k) {   // uniform
         unsigned srg, sb;
-        sample_shoot<kCuda>(sc, cam, (x << lg) + pat_entry(pat.x, (unsigned)k),
-                            (y << lg) + pat_entry(pat.y, (unsigned)k), maxrec, zcount, srg, sb);
+        sample_shoot<kCuda>(sc, cam, ((ox + x) << lg) + pat_entry(pat.x, (unsigned)k),
+                            ((oy + y) << lg) + pat_entry(pat.y, (unsigned)k), maxrec, zcount, srg,
+                            sb);
         rg += srg;
         b += sb;
       }
@@ -4163,15 +4165,24 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
     return y0 + q < H ? out + ((size_t)(y0 + q) * W + x0) * 3 : nullptr;
   }, nx * 3);
 }
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum(
+    Scene sc, Cam cam, int W, int H, int lg, int count, PatWords pat, int reset, int maxrec,
+    uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
+    unsigned* __restrict__ sat) {
+  accum_dense<kCuda, kStage>(sc, cam, W, H, 0, 0, lg, count, pat, reset, maxrec, acc, out, zcount,
+                             sat);
+}
 
 // Masked pass: over k_aa_mark's list like k_pattern_list, one lane per listed pixel (64 a wave
 // step); the list's length is read from device memory and the grid is a fixed number of
 // workgroups whose waves stride over the list.  A wave's trip count depends on the wave alone, so
 // every lane reaches the ballot.  A listed pixel is in the list once, so its record and its three
 // bytes have one writer.
+// (ox, oy): as accum_dense's.
 template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_list(
-    Scene sc, Cam cam, int W, int lg, int count, PatWords pat, int maxrec,
+__device__ __forceinline__ void accum_listed(
+    Scene sc, Cam cam, int W, int ox, int oy, int lg, int count, PatWords pat, int maxrec,
     const uint32_t* __restrict__ list, const unsigned* __restrict__ nlist,
     uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
     unsigned* __restrict__ sat) {
@@ -4193,7 +4204,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
       const unsigned p = list[e];
       saturated = (unsigned)((const uint16_t*)(acc + p))[3] + (unsigned)count > 256u;
       if (!saturated) {
-        const int xs = (int)((p % (unsigned)W) << lg), ys = (int)((p / (unsigned)W) << lg);
+        const int xs = (int)((p % (unsigned)W + (unsigned)ox) << lg);
+        const int ys = (int)((p / (unsigned)W + (unsigned)oy) << lg);
         unsigned rg = 0u, b = 0u;
         for (int k = 0; k < count; ++k) {   // uniform
           unsigned srg, sb;
@@ -4221,6 +4233,15 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
     }
     accum_count_saturated(saturated, sat);
   }
+}
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_list(
+    Scene sc, Cam cam, int W, int lg, int count, PatWords pat, int maxrec,
+    const uint32_t* __restrict__ list, const unsigned* __restrict__ nlist,
+    uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
+    unsigned* __restrict__ sat) {
+  accum_listed<kCuda, kStage>(sc, cam, W, 0, 0, lg, count, pat, maxrec, list, nlist, acc, out,
+                              zcount, sat);
 }
 
 // out = res(acc) for every pixel, nothing shot: 8 bytes in and 3 out a pixel, memory-bound.
@@ -4296,6 +4317,148 @@ hipError_t launch_accum_resolve(const void* acc, int W, int H, uint8_t* out, hip
   if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_accum_resolve, dim3((unsigned)blocks), dim3(256), 0, stream,
                      (const uint2*)acc, pixels, out);
+  return hipGetLastError();
+}
+
+// ------------------------------------- windows of a virtual image (fast, cuda) --
+// rc_render_window*, rc_accum_pass_window_device (include/raycast_hip.h, rc_window): the W x H
+// output is the rectangle at (x0, y0) of the full_w x full_h image, so pixel (x, y) of the window
+// is pixel (x0 + x, y0 + y) of that image and its subsamples are shot with the camera of the
+// s*full_w x s*full_h image (`cam`) at the coordinates s*(x0 + x) + i, s*(y0 + y) + j: what
+// k_render_ssaa, k_pattern and k_accum shoot for that pixel of the whole image.  Nothing of the
+// arithmetic changes, only where in the picture the rays start.  These kernels stand behind every
+// other kernel of the file, as section 16's did.
+//
+// k_window: k_render_ssaa's tiles over the window's own subsample grid (s = 1 << ls in 1, 2, 4, 8;
+// a workgroup owns 16 x 16 subsamples, a wave an 8 x 8 block of them), one lane per subsample.
+// Inside a wave's block the s x s subsamples of an output pixel are s*s adjacent lanes (lane l:
+// group l / (s*s), subsample l % (s*s) of it, row-major in both), so sample_reduce sums them and
+// the group's first lane stores the rounded mean.  The origin (ox, oy) = (s*x0, s*y0) is whole
+// pixels, so the groups stay aligned to the wave blocks whatever x0 and y0 are, and a group is
+// wholly inside the window or wholly outside it.  At s = 1 a lane is a pixel and stores its own
+// bytes.  The subsample image is never stored, in cuda mode either.
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_window(
+    Scene sc, Cam cam, int W, int H, int ls, int ox, int oy, int maxrec, uint8_t* __restrict__ out,
+    unsigned long long* __restrict__ zcount) {
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  stage_scene<kStage>(sc, stage);
+  int bx, by;
+  xcd_tile<0>(bx, by);
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const unsigned sub = lane & ((1u << (2 * ls)) - 1u);   // subsample within the group
+  const unsigned grp = lane >> (2 * ls);                  // group within the wave's 8 x 8 block
+  const int lgw = 3 - ls;                                 // log2 of the groups in a row of it
+  // unsigned: the last tile's columns may reach past 2^31 - 1 when s*W is close to it
+  const unsigned xs = (unsigned)bx * kTileW + (wave % (kTileW / 8)) * 8u +
+                      ((grp & ((1u << lgw) - 1u)) << ls) + (sub & ((1u << ls) - 1u));
+  const unsigned rs = (unsigned)by * kTileH + (wave / (kTileW / 8)) * 8u + ((grp >> lgw) << ls) +
+                      (sub >> ls);
+  // only xs and rs stay live across shoot, as in k_render_ssaa
+  const bool inside = (xs >> ls) < (unsigned)W && (rs >> ls) < (unsigned)H;
+  unsigned rg = 0u, b = 0u;
+  if (inside) sample_shoot<kCuda>(sc, cam, ox + (int)xs, oy + (int)rs, maxrec, zcount, rg, b);
+  sample_reduce(rg, b, 2 * ls);
+  if (inside && sub == 0u) {   // the group's first lane
+    uint8_t* q = out + ((size_t)(rs >> ls) * W + (xs >> ls)) * 3;
+    if (ls == 0) {   // one sample: its own bytes (sample_store's half is for two samples and more)
+      q[0] = (uint8_t)(rg & 0xffffu);
+      q[1] = (uint8_t)(rg >> 16);
+      q[2] = (uint8_t)b;
+    } else {
+      sample_store(q, rg, b, 2 * ls);
+    }
+  }
+}
+
+// The accumulation passes through a window: accum_dense's and accum_listed's bodies with the
+// window's origin; the records and the image are the window's own W x H.
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_win(
+    Scene sc, Cam cam, int W, int H, int ox, int oy, int lg, int count, PatWords pat, int reset,
+    int maxrec, uint2* __restrict__ acc, uint8_t* __restrict__ out,
+    unsigned long long* __restrict__ zcount, unsigned* __restrict__ sat) {
+  accum_dense<kCuda, kStage>(sc, cam, W, H, ox, oy, lg, count, pat, reset, maxrec, acc, out,
+                             zcount, sat);
+}
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_list_win(
+    Scene sc, Cam cam, int W, int ox, int oy, int lg, int count, PatWords pat, int maxrec,
+    const uint32_t* __restrict__ list, const unsigned* __restrict__ nlist,
+    uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
+    unsigned* __restrict__ sat) {
+  accum_listed<kCuda, kStage>(sc, cam, W, ox, oy, lg, count, pat, maxrec, list, nlist, acc, out,
+                              zcount, sat);
+}
+
+// the window lies inside the virtual image and s times that image's sides fit an int
+static bool window_inside(const Window& w, int W, int H, int s) {
+  return W >= 1 && H >= 1 && w.full_w >= 1 && w.full_h >= 1 && w.x0 >= 0 && w.y0 >= 0 &&
+         W <= w.full_w - w.x0 && H <= w.full_h - w.y0 && w.full_w <= 0x7fffffff / s &&
+         w.full_h <= 0x7fffffff / s;
+}
+
+int window_supported(const Window& w, int W, int H, int s) {
+  if ((s != 1 && ssaa_log2(s) < 0) || !window_inside(w, W, H, s)) return 0;
+  // k_render's tiles over the window's subsamples: grid.y, and xcd_tile's int tile index
+  const unsigned long long tx = ((unsigned long long)W * s + kTileW - 1) / kTileW;
+  const unsigned long long ty = ((unsigned long long)H * s + kTileH - 1) / kTileH;
+  return ty <= 65535ull && tx * ty <= 0x7fffffffull;
+}
+
+hipError_t launch_window(const LaunchScene& s, const Window& w, int W, int H, int ssaa, int maxrec,
+                         uint8_t* out, unsigned long long* zcount, hipStream_t stream,
+                         bool cuda_sem) {
+  if (!window_supported(w, W, H, ssaa)) return hipErrorInvalidValue;
+  const int ls = ssaa == 1 ? 0 : ssaa_log2(ssaa);
+  dim3 grid((unsigned)(((unsigned long long)W * ssaa + kTileW - 1) / kTileW),
+            (unsigned)(((unsigned long long)H * ssaa + kTileH - 1) / kTileH));
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, w.full_w * ssaa, w.full_h * ssaa);   // of the s*full_w x s*full_h image
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_window<cuda.value, st.value>), grid, dim3(kBlock), 0, stream, sc, cam, W,
+                       H, ls, w.x0 * ssaa, w.y0 * ssaa, maxrec, out, zcount);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_accum_window(const LaunchScene& s, const Window& w, int W, int H, int g,
+                               int count, const uint8_t* px, const uint8_t* py, bool reset,
+                               int maxrec, void* acc, uint8_t* out, unsigned long long* zcount,
+                               unsigned* sat, hipStream_t stream, bool cuda_sem) {
+  if (!accum_supported(W, H, g, false) || !window_inside(w, W, H, g) || count < 1 || count > 16)
+    return hipErrorInvalidValue;
+  const int lg = pattern_log2(g, 1, 3);
+  dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, w.full_w * g, w.full_h * g);   // of the g*full_w x g*full_h image
+  const PatWords pat = pattern_words(count, px, py);
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_accum_win<cuda.value, st.value>), grid, dim3(kBlock), 0, stream, sc, cam,
+                       W, H, w.x0, w.y0, lg, count, pat, reset ? 1 : 0, maxrec, (uint2*)acc, out,
+                       zcount, sat);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_accum_list_window(const LaunchScene& s, const Window& w, int W, int H, int g,
+                                    int count, const uint8_t* px, const uint8_t* py, int maxrec,
+                                    const uint32_t* list, const unsigned* nlist, void* acc,
+                                    uint8_t* out, unsigned long long* zcount, unsigned* sat,
+                                    int blocks, hipStream_t stream, bool cuda_sem) {
+  if (!accum_supported(W, H, g, true) || !window_inside(w, W, H, g) || count < 1 || count > 16 ||
+      blocks < 1 || blocks > 4096)
+    return hipErrorInvalidValue;
+  const int lg = pattern_log2(g, 1, 3);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, w.full_w * g, w.full_h * g);   // of the g*full_w x g*full_h image
+  const PatWords pat = pattern_words(count, px, py);
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_accum_list_win<cuda.value, st.value>), dim3((unsigned)blocks),
+                       dim3(kBlock), 0, stream, sc, cam, W, w.x0, w.y0, lg, count, pat, maxrec,
+                       list, nlist, (uint2*)acc, out, zcount, sat);
+  });
   return hipGetLastError();
 }
 

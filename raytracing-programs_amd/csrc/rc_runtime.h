@@ -161,7 +161,9 @@ struct Pipe {
 };
 
 // The sampling features whose frames leave phase spans behind (DevCtx::span_ev).
-enum SpanOwner { kSpanAdaptive, kSpanRates, kSpanFilter, kSpanPattern, kSpanAccum, kSpanOwners };
+enum SpanOwner {
+  kSpanAdaptive, kSpanRates, kSpanFilter, kSpanPattern, kSpanAccum, kSpanWindow, kSpanOwners
+};
 
 // The last list-refined frame of one feature on a device (adaptive supersampling, a pattern
 // frame with a threshold): what its stats getter reads.
@@ -237,7 +239,8 @@ struct DevCtx {
   // and its filter, [filt_end] behind the filter; pattern: [0] start, [1] end, and with a
   // threshold (pat_ev_listed) [2] [3] as adaptive; accumulation: [0] start and [1] end of the
   // call, [acc_ev_first] the start of its last pass and, when that pass ran over the edge list
-  // (acc_ev_listed), [3] behind the list.
+  // (acc_ev_listed), [3] behind the list; window (rc_render_window*): [0] start, [1] end (an
+  // accumulation pass through a window is an accumulation call and records as one).
   hipEvent_t* span_ev[kSpanOwners] = {};
   hipEvent_t filt_mid = nullptr;
   int filt_end = 1;
