@@ -25,7 +25,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -Wno-c11-extensions -Wno-unused-result
 CFLAGS   := -O3 -ffp-contract=off -fPIC -Wall -Wno-unused-result -Iinclude -I$(SRC)
 
-HIP_SRCS  := $(SRC)/rc_kernels.hip $(SRC)/rc_api.hip $(SRC)/rc_shard.hip $(SRC)/rc_filter.hip
+HIP_SRCS  := $(SRC)/rc_kernels.hip $(SRC)/rc_api.hip $(SRC)/rc_sampling.hip $(SRC)/rc_shard.hip $(SRC)/rc_filter.hip
 HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
 FRONT_SRC := $(SRC)/front/parse.c $(SRC)/front/objects.c $(SRC)/front/ppm.c
 
@@ -42,8 +42,11 @@ $(OBJ)/rc_scene.o: $(SRC)/rc_scene.c $(SRC)/rc_scene.h include/raycast_hip.h
 
 ROCM    ?= /opt/rocm
 HIPLIBS := -L$(ROCM)/lib -lrccl -Wl,-rpath,$(ROCM)/lib -lpthread
+# the objects every variant of the library shares with the product: they read no build-time
+# switch (RC_STAMPS, RC_DIAG and the kernels' -D options reach rc_kernels.hip and rc_api.hip only)
+PLAIN_OBJS := $(OBJ)/rc_sampling.o $(OBJ)/rc_shard.o $(OBJ)/rc_filter.o $(OBJ)/rc_scene.o
 
-$(LIB)/libraycast_hip.so: $(OBJ)/rc_kernels.o $(OBJ)/rc_api.o $(OBJ)/rc_shard.o $(OBJ)/rc_filter.o $(OBJ)/rc_scene.o
+$(LIB)/libraycast_hip.so: $(OBJ)/rc_kernels.o $(OBJ)/rc_api.o $(PLAIN_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ $(HIPLIBS)
 
 $(LIB)/libraycast_front.so: $(FRONT_SRC) include/raycast_hip.h
@@ -63,7 +66,7 @@ $(OBJ)/stamps_kernels.o: $(SRC)/rc_kernels.hip $(HIP_HDRS)
 $(OBJ)/stamps_api.o: $(SRC)/rc_api.hip $(HIP_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -DRC_STAMPS=1 -DRC_DIAG=1 -c $< -o $@
-$(LIB)/libraycast_hip_stamps.so: $(OBJ)/stamps_kernels.o $(OBJ)/stamps_api.o $(OBJ)/rc_shard.o $(OBJ)/rc_filter.o $(OBJ)/rc_scene.o
+$(LIB)/libraycast_hip_stamps.so: $(OBJ)/stamps_kernels.o $(OBJ)/stamps_api.o $(PLAIN_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ $(HIPLIBS)
 # coarse stamps: only per-step cycle counts (the evaluator itself is the product code)
 stamps2: $(LIB)/libraycast_hip_stamps2.so
@@ -73,7 +76,7 @@ $(OBJ)/stamps2_kernels.o: $(SRC)/rc_kernels.hip $(HIP_HDRS)
 $(OBJ)/stamps2_api.o: $(SRC)/rc_api.hip $(HIP_HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -DRC_STAMPS=2 -DRC_DIAG=1 -c $< -o $@
-$(LIB)/libraycast_hip_stamps2.so: $(OBJ)/stamps2_kernels.o $(OBJ)/stamps2_api.o $(OBJ)/rc_shard.o $(OBJ)/rc_filter.o $(OBJ)/rc_scene.o
+$(LIB)/libraycast_hip_stamps2.so: $(OBJ)/stamps2_kernels.o $(OBJ)/stamps2_api.o $(PLAIN_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ $(HIPLIBS)
 
 oracle:
@@ -98,7 +101,7 @@ $(OBJ)/pa5_kernels.o: $(SRC)/rc_kernels.hip $(HIP_HDRS)
 	$(HIPCC) $(HIPFLAGS) -DRC_PHASE_A_WAVES=5 -c $< -o $@
 $(OBJ)/pa6_kernels.o: $(SRC)/rc_kernels.hip $(HIP_HDRS)
 	$(HIPCC) $(HIPFLAGS) -DRC_PHASE_A_WAVES=6 -c $< -o $@
-$(LIB)/libraycast_hip_%.so: $(OBJ)/%_kernels.o $(OBJ)/rc_api.o $(OBJ)/rc_shard.o $(OBJ)/rc_filter.o $(OBJ)/rc_scene.o
+$(LIB)/libraycast_hip_%.so: $(OBJ)/%_kernels.o $(OBJ)/rc_api.o $(PLAIN_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ $(HIPLIBS)
 
 # ASan + UBSan builds of the host C (tests/test_sanitize.py; SURVEY.md §5: the CPU restatement

@@ -12,6 +12,7 @@ There is no CPU fallback: loading fails loudly if the shared libraries are missi
 render fails if no GPU is present.  Import name: ``raytracing_programs_amd`` (the directory
 name has a hyphen; ``__graft_entry__`` and tests load it by path).
 """
+import contextlib
 import ctypes
 import os
 import sys
@@ -652,6 +653,47 @@ def _timing_back(timing, t):
         timing.update({k: getattr(t, k) for k, _ in RcTiming._fields_})
 
 
+def _call(name, *args):
+    """The library's export `name` with `args`; a non-zero return raises."""
+    if getattr(hip_lib(), name)(*args) != 0:
+        raise RuntimeError(f"{name} failed (see stderr)")
+
+
+@contextlib.contextmanager
+def _timed(timing):
+    """A call's RcTiming record and the argument of a *_device entry (the record by reference,
+    or None when the caller wants no timing: the call then returns with its frame enqueued);
+    after the call the record goes into the caller's dict."""
+    t = RcTiming()
+    yield t, ctypes.byref(t) if timing is not None else None
+    _timing_back(timing, t)
+
+
+def _stream(stream_ptr):
+    """A stream argument: the caller's hipStream_t, or null for the context's own."""
+    return ctypes.c_void_p(stream_ptr or 0)
+
+
+def _host_ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _stats(name, cls, message, *lead):
+    """The fields of the stats struct `cls` that the getter `name` fills, as a dict."""
+    st = cls()
+    if getattr(hip_lib(), name)(*lead, ctypes.byref(st)) != 0:
+        raise RuntimeError(message)
+    return {k: getattr(st, k) for k, _ in cls._fields_}
+
+
+def _phase_ms(name, keys, message):
+    """The kernel spans that the getter `name` reads, in ms, under `keys`."""
+    ms = (ctypes.c_double * len(keys))()
+    if getattr(hip_lib(), name)(ms) != 0:
+        raise RuntimeError(message)
+    return dict(zip(keys, ms))
+
+
 def render(scene, width, height, depth=6, mode="parity", gpus=1, device=0, timing=None, out=None,
            ssaa=1, adaptive=0):
     """Render to a host array [H, W, 3] uint8 through rc_render (the raycast() path); `out`
@@ -659,15 +701,12 @@ def render(scene, width, height, depth=6, mode="parity", gpus=1, device=0, timin
     2, 4 or 8: the box filter of the ssaa*W x ssaa*H image (box_downsample), made on the device.
     adaptive = t in 1..255 (fast and cuda mode, with ssaa): only the pixels of the one-ray image
     whose 3 x 3 contrast reaches t are supersampled (adaptive_compose)."""
-    lib = hip_lib()
     out = _pixmap(out, width, height)
-    t = RcTiming()
     opt = options(depth, mode, gpus, device, ssaa, adaptive)
-    rc = lib.rc_render(scene.packed(), width, height, ctypes.byref(opt),
-                       out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
-    if rc != 0:
-        raise RuntimeError("rc_render failed (no GPU, or HIP error: see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (t, _):
+        if hip_lib().rc_render(scene.packed(), width, height, ctypes.byref(opt), _host_ptr(out),
+                               ctypes.byref(t)) != 0:
+            raise RuntimeError("rc_render failed (no GPU, or HIP error: see stderr)")
     return out
 
 
@@ -676,17 +715,11 @@ def render_device(scene, width, height, d_out_ptr, stream_ptr=None, depth=6, mod
     """Render rows row0, row0+row_step, ... into device memory at d_out_ptr (nrows*W*3 B); with
     ssaa > 1 the rows are those of the box-filtered W x H image.  adaptive > 0: whole images
     only."""
-    lib = hip_lib()
     nrows = height if nrows is None else nrows
     opt = options(depth, mode, ssaa=ssaa, adaptive=adaptive)
-    t = RcTiming()
-    rc = lib.rc_render_device(scene.packed(), width, height, row0, row_step, nrows,
-                              ctypes.byref(opt), ctypes.c_void_p(d_out_ptr),
-                              ctypes.c_void_p(stream_ptr or 0),
-                              ctypes.byref(t) if timing is not None else None)
-    if rc != 0:
-        raise RuntimeError("rc_render_device failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (_, t):
+        _call("rc_render_device", scene.packed(), width, height, row0, row_step, nrows,
+              ctypes.byref(opt), ctypes.c_void_p(d_out_ptr), _stream(stream_ptr), t)
 
 
 def frame_submit(scene, width, height, d_out_ptr, depth=6, mode="parity", ssaa=1, adaptive=0):
@@ -694,9 +727,8 @@ def frame_submit(scene, width, height, d_out_ptr, depth=6, mode="parity", ssaa=1
     flight (rc_frame_submit); returns at once.  Pair with frames_wait().  ssaa > 1 (and
     adaptive): fast and cuda mode only (parity frames in flight do not supersample)."""
     opt = options(depth, mode, ssaa=ssaa, adaptive=adaptive)
-    if hip_lib().rc_frame_submit(scene.packed(), width, height, ctypes.byref(opt),
-                                 ctypes.c_void_p(d_out_ptr)) != 0:
-        raise RuntimeError("rc_frame_submit failed (see stderr)")
+    _call("rc_frame_submit", scene.packed(), width, height, ctypes.byref(opt),
+          ctypes.c_void_p(d_out_ptr))
 
 
 def frames_wait(timing=None):
@@ -711,19 +743,15 @@ def frames_wait(timing=None):
 def adaptive_stats():
     """The last adaptive frame enqueued on the current device (rc_adaptive_stats_get, which
     waits for it): {"refined_pixels": pixels with contrast >= t, "rays": W*H + s*s*that}."""
-    st = RcAdaptiveStats()
-    if hip_lib().rc_adaptive_stats_get(ctypes.byref(st)) != 0:
-        raise RuntimeError("rc_adaptive_stats_get: no adaptive frame on this device")
-    return {k: getattr(st, k) for k, _ in RcAdaptiveStats._fields_}
+    return _stats("rc_adaptive_stats_get", RcAdaptiveStats,
+                  "rc_adaptive_stats_get: no adaptive frame on this device")
 
 
 def adaptive_phase_ms():
     """Kernel spans of the last timed adaptive frame (rc_adaptive_phase_ms), in ms:
     {"render", "mark", "refine"}."""
-    ms = (ctypes.c_double * 3)()
-    if hip_lib().rc_adaptive_phase_ms(ms) != 0:
-        raise RuntimeError("rc_adaptive_phase_ms: no timed adaptive frame on this device")
-    return {"render": ms[0], "mark": ms[1], "refine": ms[2]}
+    return _phase_ms("rc_adaptive_phase_ms", ("render", "mark", "refine"),
+                     "rc_adaptive_phase_ms: no timed adaptive frame on this device")
 
 
 def rates_compose(base, images, rates):
@@ -757,20 +785,15 @@ def render_rates(scene, width, height, rates, depth=6, mode="fast", out=None, ti
     values in RATE_VALUES, `out` the caller's C-contiguous [H, W, 3] uint8 pixmap, in and out (the
     default is zeros): a pixel of rate 0 keeps its bytes, one of rate s gets the ssaa = s image's
     pixel (rates_compose).  Fast and cuda mode."""
-    lib = hip_lib()
     rates = np.asarray(rates)
     if rates.dtype != np.uint8 or rates.shape != (height, width):
         raise ValueError(f"rates: uint8 {(height, width)}, got {rates.dtype} {rates.shape}")
     rates = np.ascontiguousarray(rates)
     out = _pixmap(out, width, height, np.zeros)
-    t = RcTiming()
     opt = options(depth, mode)
-    rc = lib.rc_render_rates(scene.packed(), width, height, ctypes.byref(opt),
-                             rates.ctypes.data_as(ctypes.c_void_p),
-                             out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
-    if rc != 0:
-        raise RuntimeError("rc_render_rates failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (t, _):
+        _call("rc_render_rates", scene.packed(), width, height, ctypes.byref(opt), _host_ptr(rates),
+              _host_ptr(out), ctypes.byref(t))
     return out
 
 
@@ -779,16 +802,10 @@ def render_rates_device(scene, width, height, d_rates_ptr, d_out_ptr, stream_ptr
     """rc_render_rates_device: the map (W*H bytes) and the image (W*H*3 bytes) are device memory;
     enqueued on the stream and asynchronous unless `timing` is given.  A map byte outside
     RATE_VALUES leaves its pixel alone and is counted in rate_stats()["invalid"]."""
-    lib = hip_lib()
     opt = options(depth, mode)
-    t = RcTiming()
-    rc = lib.rc_render_rates_device(scene.packed(), width, height, ctypes.byref(opt),
-                                    ctypes.c_void_p(d_rates_ptr), ctypes.c_void_p(d_out_ptr),
-                                    ctypes.c_void_p(stream_ptr),
-                                    ctypes.byref(t) if timing is not None else None)
-    if rc != 0:
-        raise RuntimeError("rc_render_rates_device failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (_, t):
+        _call("rc_render_rates_device", scene.packed(), width, height, ctypes.byref(opt),
+              ctypes.c_void_p(d_rates_ptr), ctypes.c_void_p(d_out_ptr), _stream(stream_ptr), t)
 
 
 def rate_stats():
@@ -804,10 +821,8 @@ def rate_stats():
 def rate_phase_ms():
     """Kernel spans of the last rate-map frame (rc_rate_phase_ms), in ms: {"render": the rate-1
     pass with the binning, "refine": the three lists}."""
-    ms = (ctypes.c_double * 2)()
-    if hip_lib().rc_rate_phase_ms(ms) != 0:
-        raise RuntimeError("rc_rate_phase_ms: no rate-map frame on this device")
-    return {"render": ms[0], "refine": ms[1]}
+    return _phase_ms("rc_rate_phase_ms", ("render", "refine"),
+                     "rc_rate_phase_ms: no rate-map frame on this device")
 
 
 def filter_box(s):
@@ -892,16 +907,12 @@ def render_filtered(scene, width, height, taps, ssaa, depth=6, mode="parity", de
                     timing=None, out=None):
     """rc_render_filtered: the ssaa*W x ssaa*H image of the mode through the tap vector `taps`
     (filter_downsample), into a host array [H, W, 3] uint8.  ssaa is 2, 4 or 8."""
-    lib = hip_lib()
     f = _rc_filter(taps, ssaa)
     out = _pixmap(out, width, height)
-    t = RcTiming()
     opt = options(depth, mode, 1, device, ssaa)
-    rc = lib.rc_render_filtered(scene.packed(), width, height, ctypes.byref(opt), ctypes.byref(f),
-                                out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
-    if rc != 0:
-        raise RuntimeError("rc_render_filtered failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (t, _):
+        _call("rc_render_filtered", scene.packed(), width, height, ctypes.byref(opt),
+              ctypes.byref(f), _host_ptr(out), ctypes.byref(t))
     return out
 
 
@@ -909,37 +920,26 @@ def render_filtered_device(scene, width, height, taps, ssaa, d_out_ptr, stream_p
                            mode="parity", timing=None):
     """rc_render_filtered_device: the image (W*H*3 bytes) is device memory; enqueued on the
     stream and asynchronous unless `timing` is given."""
-    lib = hip_lib()
     f = _rc_filter(taps, ssaa)
     opt = options(depth, mode, ssaa=ssaa)
-    t = RcTiming()
-    rc = lib.rc_render_filtered_device(scene.packed(), width, height, ctypes.byref(opt),
-                                       ctypes.byref(f), ctypes.c_void_p(d_out_ptr),
-                                       ctypes.c_void_p(stream_ptr or 0),
-                                       ctypes.byref(t) if timing is not None else None)
-    if rc != 0:
-        raise RuntimeError("rc_render_filtered_device failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (_, t):
+        _call("rc_render_filtered_device", scene.packed(), width, height, ctypes.byref(opt),
+              ctypes.byref(f), ctypes.c_void_p(d_out_ptr), _stream(stream_ptr), t)
 
 
 def filter_image_device(d_src_ptr, width, height, s, taps, d_dst_ptr, stream_ptr=None):
     """rc_filter_image_device: the filter pass alone, d_dst (W x H x 3 bytes) <- d_src (s*W x s*H
     x 3 bytes), device memory, on the stream; asynchronous."""
     f = _rc_filter(taps, s)
-    rc = hip_lib().rc_filter_image_device(ctypes.c_void_p(d_src_ptr), width, height, int(s),
-                                          ctypes.byref(f), ctypes.c_void_p(d_dst_ptr),
-                                          ctypes.c_void_p(stream_ptr or 0))
-    if rc != 0:
-        raise RuntimeError("rc_filter_image_device failed (see stderr)")
+    _call("rc_filter_image_device", ctypes.c_void_p(d_src_ptr), width, height, int(s),
+          ctypes.byref(f), ctypes.c_void_p(d_dst_ptr), _stream(stream_ptr))
 
 
 def filter_phase_ms():
     """Kernel spans of the last timed two-pass supersampled frame (rc_filter_phase_ms), in ms:
     {"render": the s*W x s*H image, "filter": the filter pass}."""
-    ms = (ctypes.c_double * 2)()
-    if hip_lib().rc_filter_phase_ms(ms) != 0:
-        raise RuntimeError("rc_filter_phase_ms: no timed two-pass frame on this device")
-    return {"render": ms[0], "filter": ms[1]}
+    return _phase_ms("rc_filter_phase_ms", ("render", "filter"),
+                     "rc_filter_phase_ms: no timed two-pass frame on this device")
 
 
 def filter_from_env(ssaa=1, adaptive=0):
@@ -1001,13 +1001,18 @@ def pattern_downsample(big, g, points):
     return ((total + n // 2) // n).astype(np.uint8)
 
 
-def _rc_pattern(p):
-    g, pts = pattern(p)
-    pat = RcPattern()
-    pat.grid, pat.nsamples = g, len(pts)
+def _lattice(struct, checked):
+    """The checked (g, points) in an RcPattern or an RcSampleSeq (the same four fields)."""
+    g, pts = checked
+    lat = struct()
+    lat.grid, lat.nsamples = g, len(pts)
     for k, (x, y) in enumerate(pts):
-        pat.x[k], pat.y[k] = x, y
-    return pat
+        lat.x[k], lat.y[k] = x, y
+    return lat
+
+
+def _rc_pattern(p):
+    return _lattice(RcPattern, pattern(p))
 
 
 def render_pattern(scene, width, height, pat, threshold=0, depth=6, mode="fast", device=0,
@@ -1016,17 +1021,12 @@ def render_pattern(scene, width, height, pat, threshold=0, depth=6, mode="fast",
     3 x 3 contrast reaches `threshold` (adaptive_compose) get the rounded mean of the pattern's
     samples of the g*W x g*H image (pattern_downsample).  `pat` is a built-in name or a
     (g, [(x, y), ...]) pair.  Fast and cuda mode."""
-    lib = hip_lib()
     p = _rc_pattern(pat)
     out = _pixmap(out, width, height)
-    t = RcTiming()
     opt = options(depth, mode, 1, device)
-    rc = lib.rc_render_pattern(scene.packed(), width, height, ctypes.byref(opt), ctypes.byref(p),
-                               int(threshold), out.ctypes.data_as(ctypes.c_void_p),
-                               ctypes.byref(t))
-    if rc != 0:
-        raise RuntimeError("rc_render_pattern failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (t, _):
+        _call("rc_render_pattern", scene.packed(), width, height, ctypes.byref(opt),
+              ctypes.byref(p), int(threshold), _host_ptr(out), ctypes.byref(t))
     return out
 
 
@@ -1034,36 +1034,26 @@ def render_pattern_device(scene, width, height, pat, d_out_ptr, threshold=0, str
                           depth=6, mode="fast", timing=None):
     """rc_render_pattern_device: the image (W*H*3 bytes) is device memory; enqueued on the stream
     and asynchronous unless `timing` is given."""
-    lib = hip_lib()
     p = _rc_pattern(pat)
     opt = options(depth, mode)
-    t = RcTiming()
-    rc = lib.rc_render_pattern_device(scene.packed(), width, height, ctypes.byref(opt),
-                                      ctypes.byref(p), int(threshold), ctypes.c_void_p(d_out_ptr),
-                                      ctypes.c_void_p(stream_ptr or 0),
-                                      ctypes.byref(t) if timing is not None else None)
-    if rc != 0:
-        raise RuntimeError("rc_render_pattern_device failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (_, t):
+        _call("rc_render_pattern_device", scene.packed(), width, height, ctypes.byref(opt),
+              ctypes.byref(p), int(threshold), ctypes.c_void_p(d_out_ptr), _stream(stream_ptr), t)
 
 
 def pattern_stats():
     """The last pattern frame enqueued on the current device (rc_pattern_stats_get, which waits
     for it): {"refined_pixels", "rays"}; threshold 0: W*H and n*W*H, else the listed pixels and
     W*H + n*listed."""
-    st = RcPatternStats()
-    if hip_lib().rc_pattern_stats_get(ctypes.byref(st)) != 0:
-        raise RuntimeError("rc_pattern_stats_get: no pattern frame on this device")
-    return {k: getattr(st, k) for k, _ in RcPatternStats._fields_}
+    return _stats("rc_pattern_stats_get", RcPatternStats,
+                  "rc_pattern_stats_get: no pattern frame on this device")
 
 
 def pattern_phase_ms():
     """Kernel spans of the last pattern frame (rc_pattern_phase_ms), in ms: {"render", "mark",
     "refine"}; threshold 0: "render" is the pattern kernel and the others are 0."""
-    ms = (ctypes.c_double * 3)()
-    if hip_lib().rc_pattern_phase_ms(ms) != 0:
-        raise RuntimeError("rc_pattern_phase_ms: no pattern frame on this device")
-    return {"render": ms[0], "mark": ms[1], "refine": ms[2]}
+    return _phase_ms("rc_pattern_phase_ms", ("render", "mark", "refine"),
+                     "rc_pattern_phase_ms: no pattern frame on this device")
 
 
 def pattern_from_env(mode="fast", ssaa=1, adaptive=0):
@@ -1182,12 +1172,7 @@ def accum_run(big, g, points, dense, t=0):
 
 
 def _rc_sample_seq(p):
-    g, pts = sample_seq(p)
-    seq = RcSampleSeq()
-    seq.grid, seq.nsamples = g, len(pts)
-    for k, (x, y) in enumerate(pts):
-        seq.x[k], seq.y[k] = x, y
-    return seq
+    return _lattice(RcSampleSeq, sample_seq(p))
 
 
 def accum_pass_device(scene, width, height, seq, first, count, d_acc_ptr, d_out_ptr, threshold=0,
@@ -1197,27 +1182,18 @@ def accum_pass_device(scene, width, height, seq, first, count, d_acc_ptr, d_out_
     [H, W, 4] uint16 array) and the means stored in the image (W*H*3 bytes), for every pixel
     (threshold 0) or the pixels of the image as it stands whose 3 x 3 contrast reaches
     `threshold` (accum_step).  Enqueued on the stream and asynchronous unless `timing` is given."""
-    lib = hip_lib()
     s = _rc_sample_seq(seq)
     opt = options(depth, mode)
-    t = RcTiming()
-    rc = lib.rc_accum_pass_device(scene.packed(), width, height, ctypes.byref(opt),
-                                  ctypes.byref(s), int(first), int(count), int(threshold),
-                                  1 if reset else 0, ctypes.c_void_p(d_acc_ptr),
-                                  ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(stream_ptr or 0),
-                                  ctypes.byref(t) if timing is not None else None)
-    if rc != 0:
-        raise RuntimeError("rc_accum_pass_device failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (_, t):
+        _call("rc_accum_pass_device", scene.packed(), width, height, ctypes.byref(opt),
+              ctypes.byref(s), int(first), int(count), int(threshold), 1 if reset else 0,
+              ctypes.c_void_p(d_acc_ptr), ctypes.c_void_p(d_out_ptr), _stream(stream_ptr), t)
 
 
 def accum_resolve_device(d_acc_ptr, width, height, d_out_ptr, stream_ptr=None):
     """rc_accum_resolve_device: the image of an accumulator (accum_resolve), nothing shot."""
-    rc = hip_lib().rc_accum_resolve_device(ctypes.c_void_p(d_acc_ptr), width, height,
-                                           ctypes.c_void_p(d_out_ptr),
-                                           ctypes.c_void_p(stream_ptr or 0))
-    if rc != 0:
-        raise RuntimeError("rc_accum_resolve_device failed (see stderr)")
+    _call("rc_accum_resolve_device", ctypes.c_void_p(d_acc_ptr), width, height,
+          ctypes.c_void_p(d_out_ptr), _stream(stream_ptr))
 
 
 def render_accum(scene, width, height, seq, dense=None, threshold=0, depth=6, mode="fast",
@@ -1225,17 +1201,13 @@ def render_accum(scene, width, height, seq, dense=None, threshold=0, depth=6, mo
     """rc_render_accum (accum_run): samples [0, dense) of `seq` for every pixel, then one
     single-sample pass with `threshold` for each of the others.  dense = None: the whole sequence.
     Fast and cuda mode."""
-    lib = hip_lib()
     s = _rc_sample_seq(seq)
     out = _pixmap(out, width, height)
-    t = RcTiming()
     opt = options(depth, mode, 1, device)
-    rc = lib.rc_render_accum(scene.packed(), width, height, ctypes.byref(opt), ctypes.byref(s),
-                             s.nsamples if dense is None else int(dense), int(threshold),
-                             out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
-    if rc != 0:
-        raise RuntimeError("rc_render_accum failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (t, _):
+        _call("rc_render_accum", scene.packed(), width, height, ctypes.byref(opt), ctypes.byref(s),
+              s.nsamples if dense is None else int(dense), int(threshold), _host_ptr(out),
+              ctypes.byref(t))
     return out
 
 
@@ -1243,19 +1215,15 @@ def accum_stats():
     """The last accumulation call enqueued on the current device (rc_accum_stats_get, which waits
     for it): {"passes", "active_pixels", "saturated", "rays"}; the pixel counts are the last
     pass's, the rays the whole call's."""
-    st = RcAccumStats()
-    if hip_lib().rc_accum_stats_get(ctypes.byref(st)) != 0:
-        raise RuntimeError("rc_accum_stats_get: no accumulation call on this device")
-    return {k: getattr(st, k) for k, _ in RcAccumStats._fields_}
+    return _stats("rc_accum_stats_get", RcAccumStats,
+                  "rc_accum_stats_get: no accumulation call on this device")
 
 
 def accum_phase_ms():
     """Kernel spans of the last pass of the last accumulation call (rc_accum_phase_ms), in ms:
     {"mark", "shoot"}; "mark" is 0 for a pass that takes every pixel."""
-    ms = (ctypes.c_double * 2)()
-    if hip_lib().rc_accum_phase_ms(ms) != 0:
-        raise RuntimeError("rc_accum_phase_ms: no accumulation call on this device")
-    return {"mark": ms[0], "shoot": ms[1]}
+    return _phase_ms("rc_accum_phase_ms", ("mark", "shoot"),
+                     "rc_accum_phase_ms: no accumulation call on this device")
 
 
 def _window(window, width, height, s=1):
@@ -1329,16 +1297,12 @@ def render_window(scene, window, width, height, ssaa=1, depth=6, mode="fast", de
                   timing=None, out=None):
     """rc_render_window: the W x H window at window = (full_w, full_h, x0, y0) of the full_w x
     full_h image of that mode with that ssaa (window_crop of it, s = 1).  Fast and cuda mode."""
-    lib = hip_lib()
     win = _rc_window(window)
     out = _pixmap(out, width, height)
-    t = RcTiming()
     opt = options(depth, mode, 1, device, ssaa)
-    rc = lib.rc_render_window(scene.packed(), ctypes.byref(win), width, height, ctypes.byref(opt),
-                              out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(t))
-    if rc != 0:
-        raise RuntimeError("rc_render_window failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (t, _):
+        _call("rc_render_window", scene.packed(), ctypes.byref(win), width, height,
+              ctypes.byref(opt), _host_ptr(out), ctypes.byref(t))
     return out
 
 
@@ -1346,17 +1310,11 @@ def render_window_device(scene, window, width, height, d_out_ptr, ssaa=1, stream
                          depth=6, mode="fast", timing=None):
     """rc_render_window_device: the window's image (W*H*3 bytes) is device memory; enqueued on the
     stream and asynchronous unless `timing` is given."""
-    lib = hip_lib()
     win = _rc_window(window)
     opt = options(depth, mode, ssaa=ssaa)
-    t = RcTiming()
-    rc = lib.rc_render_window_device(scene.packed(), ctypes.byref(win), width, height,
-                                     ctypes.byref(opt), ctypes.c_void_p(d_out_ptr),
-                                     ctypes.c_void_p(stream_ptr or 0),
-                                     ctypes.byref(t) if timing is not None else None)
-    if rc != 0:
-        raise RuntimeError("rc_render_window_device failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (_, t):
+        _call("rc_render_window_device", scene.packed(), ctypes.byref(win), width, height,
+              ctypes.byref(opt), ctypes.c_void_p(d_out_ptr), _stream(stream_ptr), t)
 
 
 def accum_pass_window_device(scene, window, width, height, seq, first, count, d_acc_ptr,
@@ -1365,20 +1323,14 @@ def accum_pass_window_device(scene, window, width, height, seq, first, count, d_
     """rc_accum_pass_window_device: accum_pass_device with the samples of the window at window =
     (full_w, full_h, x0, y0) of the virtual image (accum_step on window_crop of its g*full_w x
     g*full_h image, s = g); the accumulator and the image are the window's own W x H."""
-    lib = hip_lib()
     win = _rc_window(window)
     s = _rc_sample_seq(seq)
     opt = options(depth, mode)
-    t = RcTiming()
-    rc = lib.rc_accum_pass_window_device(scene.packed(), ctypes.byref(win), width, height,
-                                         ctypes.byref(opt), ctypes.byref(s), int(first),
-                                         int(count), int(threshold), 1 if reset else 0,
-                                         ctypes.c_void_p(d_acc_ptr), ctypes.c_void_p(d_out_ptr),
-                                         ctypes.c_void_p(stream_ptr or 0),
-                                         ctypes.byref(t) if timing is not None else None)
-    if rc != 0:
-        raise RuntimeError("rc_accum_pass_window_device failed (see stderr)")
-    _timing_back(timing, t)
+    with _timed(timing) as (_, t):
+        _call("rc_accum_pass_window_device", scene.packed(), ctypes.byref(win), width, height,
+              ctypes.byref(opt), ctypes.byref(s), int(first), int(count), int(threshold),
+              1 if reset else 0, ctypes.c_void_p(d_acc_ptr), ctypes.c_void_p(d_out_ptr),
+              _stream(stream_ptr), t)
 
 
 def window_from_env(width, height, mode="fast", ssaa=1, adaptive=0, gpus=1):
@@ -1494,10 +1446,7 @@ def profile_begin():
 
 def profile_end():
     """Close the window: per-phase kernel times (ms) averaged over the renders inside it."""
-    st = RcPhaseStats()
-    if hip_lib().rc_profile_end(ctypes.byref(st)) != 0:
-        raise RuntimeError("rc_profile_end failed")
-    return {k: getattr(st, k) for k, _ in RcPhaseStats._fields_}
+    return _stats("rc_profile_end", RcPhaseStats, "rc_profile_end failed")
 
 
 def encode_p3(img):
@@ -1559,18 +1508,12 @@ class Group:
         """Collective render; the root's image lands at d_image_ptr (W*H*3 B on rank 0's
         device)."""
         opt = options(depth, mode)
-        t = RcTiming()
-        rc = hip_lib().rc_render_sharded(self._h, scene.packed(), width, height, ctypes.byref(opt),
-                                         ctypes.c_void_p(d_image_ptr or 0), ctypes.byref(t))
-        if rc != 0:
-            raise RuntimeError("rc_render_sharded failed (see stderr)")
-        _timing_back(timing, t)
+        with _timed(timing) as (t, _):
+            _call("rc_render_sharded", self._h, scene.packed(), width, height, ctypes.byref(opt),
+                  ctypes.c_void_p(d_image_ptr or 0), ctypes.byref(t))
 
     def stats(self):
-        st = RcShardStats()
-        if hip_lib().rc_group_last_stats(self._h, ctypes.byref(st)) != 0:
-            raise RuntimeError("rc_group_last_stats failed")
-        return {k: getattr(st, k) for k, _ in RcShardStats._fields_}
+        return _stats("rc_group_last_stats", RcShardStats, "rc_group_last_stats failed", self._h)
 
     def rank_stats(self, rank):
         """One rank's own timeline of the last render (rc_group_rank_stats), or None when this

@@ -651,12 +651,7 @@ int copy_overlapped(DevCtx& c, uint8_t* host, const uint8_t* dev, size_t bytes,
 }
 
 // ------------------------------------------------------ the frame scaffold: entering --
-// A device call's context with its lock held (one render at a time per device, DevCtx::mu).
-struct Entered {
-  DevCtx* c = nullptr;
-  std::unique_lock<std::mutex> lk;
-};
-constexpr int kCurrentDevice = -1;
+// (declared and documented in rc_runtime.h: rc_sampling.hip's entry points use it too)
 
 // opt->device against the device count (*ndev, optional)
 int device_available(const rc_options* opt, int* ndev) {
@@ -670,11 +665,6 @@ int device_available(const rc_options* opt, int* ndev) {
   return 0;
 }
 
-// Enter a call on `device` (made current) or on the current one (kCurrentDevice).  The lock
-// covers the workspace from its (re)allocation on: a concurrent caller's ensure() could
-// otherwise free the buffer another caller is rendering into.  render: an earlier frame of this
-// workspace whose hand-off failed (rc_render_device on another stream) is reported by the next
-// render call, before its own frame is enqueued (once: the report consumes the counts).
 int enter(int device, bool render, Entered& e) {
   if (device == kCurrentDevice)
     HIP_TRY(hipGetDevice(&device));
@@ -689,12 +679,10 @@ int enter(int device, bool render, Entered& e) {
   return 0;
 }
 
-// a host-pixmap render entry: on opt->device
 int enter_host(const rc_options* opt, Entered& e) {
   return device_available(opt, nullptr) || enter(opt->device, true, e) ? -1 : 0;
 }
 
-// ms[i] = the span marks[i] -> marks[i + 1], once the last mark has completed
 int read_spans(std::initializer_list<hipEvent_t> marks, double* ms) {
   const hipEvent_t* m = marks.begin();
   HIP_TRY(hipEventSynchronize(m[marks.size() - 1]));
@@ -702,7 +690,6 @@ int read_spans(std::initializer_list<hipEvent_t> marks, double* ms) {
   return 0;
 }
 
-// the listed pixels of f's frame, from its counter block once its refinement has run
 int list_frame_refined(const ListFrame& f, int64_t* refined) {
   HIP_TRY(hipEventSynchronize(f.done));   // the frame's stream, up to its refinement
   unsigned n = 0;
@@ -774,609 +761,6 @@ int rc_set_tuning(const rc_tuning* t) {
 }
 
 double rc_last_kernel_ms(void) { return g_last_kernel_ms; }
-
-int rc_adaptive_stats_get(rc_adaptive_stats* out) {
-  Entered e;
-  if (!out || enter(kCurrentDevice, false, e) || !e.c->aa.valid) return -1;
-  const ListFrame& f = e.c->aa;
-  if (list_frame_refined(f, &out->refined_pixels)) return -1;
-  out->rays = (int64_t)f.pixels + (int64_t)f.rays * out->refined_pixels;
-  return 0;
-}
-
-int rc_adaptive_phase_ms(double ms[3]) {
-  Entered e;
-  if (!ms || enter(kCurrentDevice, false, e)) return -1;
-  hipEvent_t* ev = e.c->span_ev[kSpanAdaptive];
-  return ev ? read_spans({ev[0], ev[2], ev[3], ev[1]}, ms) : -1;
-}
-
-int rc_rate_stats_get(rc_rate_stats* out) {
-  Entered e;
-  if (!out || enter(kCurrentDevice, false, e) || !e.c->rate_valid) return -1;
-  HIP_TRY(hipEventSynchronize(e.c->rate_done));   // the frame's stream, up to its refinement
-  unsigned n[5] = {0, 0, 0, 0, 0};   // launch_rates_render's counter block
-  HIP_TRY(hipMemcpy(n, e.c->rate_count.p, sizeof n, hipMemcpyDeviceToHost));
-  out->pixels[0] = (int64_t)n[3];
-  out->pixels[1] = (int64_t)n[0];
-  out->pixels[2] = (int64_t)n[1];
-  out->pixels[3] = (int64_t)n[2];
-  out->invalid = (int64_t)n[4];
-  out->rays = out->pixels[0] + 4 * out->pixels[1] + 16 * out->pixels[2] + 64 * out->pixels[3];
-  return 0;
-}
-
-int rc_rate_phase_ms(double ms[2]) {
-  Entered e;
-  if (!ms || enter(kCurrentDevice, false, e)) return -1;
-  hipEvent_t* ev = e.c->span_ev[kSpanRates];
-  return ev ? read_spans({ev[0], ev[2], ev[1]}, ms) : -1;
-}
-
-int rc_filter_phase_ms(double ms[2]) {
-  Entered e;
-  if (!ms || enter(kCurrentDevice, false, e)) return -1;
-  hipEvent_t* ev = e.c->span_ev[kSpanFilter];
-  return ev ? read_spans({ev[0], e.c->filt_mid, ev[e.c->filt_end]}, ms) : -1;
-}
-
-// ---------------------------------------------------------- reconstruction filters --
-static bool filter_factor(int s) { return s == 2 || s == 4 || s == 8; }
-
-int rc_filter_box(int s, rc_filter* out) {
-  if (!out || !filter_factor(s)) return -1;
-  std::memset(out, 0, sizeof *out);
-  out->ntaps = s;
-  for (int i = 0; i < s; ++i) out->taps[i] = 1;
-  return 0;
-}
-
-int rc_filter_tent(int s, rc_filter* out) {
-  if (!out || !filter_factor(s)) return -1;
-  std::memset(out, 0, sizeof *out);
-  out->ntaps = 2 * s;
-  for (int i = 0; i < s; ++i) out->taps[i] = out->taps[2 * s - 1 - i] = (int16_t)(2 * i + 1);
-  return 0;
-}
-
-// The rules of include/raycast_hip.h (rc_filter).  The bound on the absolute sum is what keeps
-// the kernel's arithmetic in int32: a horizontal sum is at most 2048 * 255 < 2^19 in magnitude,
-// the full sum at most 2048^2 * 255, and with the rounding term S*S/2 <= 2^21 that stays below
-// 2^31, so the separable evaluation is exact.
-int rc_filter_check(const rc_filter* f, int s) {
-  if (!f) {
-    std::fprintf(stderr, "Error: rc_filter_check: a null filter\n");
-    return -1;
-  }
-  if (!filter_factor(s)) {
-    std::fprintf(stderr, "Error: rc_filter_check: factor %d is not 2, 4 or 8\n", s);
-    return -1;
-  }
-  const int n = f->ntaps;
-  if (n > RC_FILTER_MAX_TAPS) {
-    std::fprintf(stderr, "Error: rc_filter_check: %d taps, at most %d\n", n, RC_FILTER_MAX_TAPS);
-    return -1;
-  }
-  if (n < s || ((n - s) & 1)) {
-    std::fprintf(stderr, "Error: rc_filter_check: %d taps at factor %d: the count is s + 2h with "
-                 "a halo h >= 0, so it is at least s and differs from s by an even number\n", n, s);
-    return -1;
-  }
-  if ((n - s) / 2 > s) {
-    std::fprintf(stderr, "Error: rc_filter_check: %d taps at factor %d: the halo %d is wider than "
-                 "one output pixel (h <= s, at most %d taps)\n", n, s, (n - s) / 2, 3 * s);
-    return -1;
-  }
-  long long sum = 0, mag = 0;
-  for (int i = 0; i < n; ++i) {
-    sum += f->taps[i];
-    mag += f->taps[i] < 0 ? -(long long)f->taps[i] : f->taps[i];
-  }
-  if (sum <= 0) {
-    std::fprintf(stderr, "Error: rc_filter_check: the taps sum to %lld, the sum must be "
-                 "positive\n", sum);
-    return -1;
-  }
-  if (mag > 2048) {
-    std::fprintf(stderr, "Error: rc_filter_check: the taps' absolute values sum to %lld, at most "
-                 "2048 (the int32 bound)\n", mag);
-    return -1;
-  }
-  return 0;
-}
-
-int rc_filter_env(const rc_options* opt, rc_filter* out) {
-  const char* v = std::getenv("RAYCAST_FILTER");
-  if (!v || !opt || !out) return 0;
-  bool tent = false;
-  if (!std::strcmp(v, "tent")) tent = true;
-  else if (std::strcmp(v, "box"))
-    std::fprintf(stderr, "Warning: RAYCAST_FILTER '%s' is not box or tent, using box\n", v);
-  const int s = RC_SSAA_FACTOR(opt->ssaa);
-  if (!filter_factor(s)) {
-    std::fprintf(stderr, "Warning: RAYCAST_FILTER '%s' needs RAYCAST_SSAA 2, 4 or 8, ignored\n", v);
-    return 0;
-  }
-  if (RC_SSAA_THRESHOLD(opt->ssaa) > 0) {
-    std::fprintf(stderr, "Warning: RAYCAST_FILTER '%s' does not combine with "
-                 "RAYCAST_SSAA_ADAPTIVE (a refined pixel's footprint would reach its unrefined "
-                 "neighbours), ignored\n", v);
-    return 0;
-  }
-  return tent && rc_filter_tent(s, out) == 0 ? 1 : 0;
-}
-
-// What the filtered entry points refuse from their arguments alone; the factor, or -1.
-static int filtered_refused(const char* who, const rc_options* opt, int W, int H,
-                            const rc_filter* f) {
-  const int ss = ssaa_factor(opt, who);
-  if (ss < 0) return -1;   // ssaa_decode has said why
-  if (RC_SSAA_THRESHOLD(opt->ssaa) > 0) {
-    std::fprintf(stderr, "Error: %s: an adaptive threshold (ssaa %d): a refined pixel's filter "
-                 "footprint would reach its unrefined neighbours' subsamples; use a plain factor\n",
-                 who, opt->ssaa);
-    return -1;
-  }
-  if (ss < 2) {
-    std::fprintf(stderr, "Error: %s: ssaa %d: a filtered frame needs a factor of 2, 4 or 8\n", who,
-                 opt->ssaa);
-    return -1;
-  }
-  if (opt->num_gpus > 1) {
-    std::fprintf(stderr, "Error: %s: num_gpus %d: the row shards do not supersample\n", who,
-                 opt->num_gpus);
-    return -1;
-  }
-  if (rc_filter_check(f, ss)) return -1;
-  if (W <= 0 || H <= 0 || W > (1 << 28) / ss || H > (1 << 28) / ss) {
-    std::fprintf(stderr, "Error: %s: %d x %d at factor %d: both sides must be 1 .. 2^28 / s\n",
-                 who, W, H, ss);
-    return -1;
-  }
-  return ss;
-}
-
-// ------------------------------------------------------------ sparse sample patterns --
-int rc_pattern_stats_get(rc_pattern_stats* out) {
-  Entered e;
-  if (!out || enter(kCurrentDevice, false, e) || !e.c->pat.valid) return -1;
-  const ListFrame& f = e.c->pat;
-  const bool listed = e.c->pat_t > 0;
-  int64_t refined = (int64_t)f.pixels;   // without a threshold: known without the device
-  if (listed && list_frame_refined(f, &refined)) return -1;
-  out->refined_pixels = refined;
-  out->rays = (listed ? (int64_t)f.pixels : 0) + (int64_t)f.rays * refined;
-  return 0;
-}
-
-int rc_pattern_phase_ms(double ms[3]) {
-  Entered e;
-  if (!ms || enter(kCurrentDevice, false, e)) return -1;
-  hipEvent_t* ev = e.c->span_ev[kSpanPattern];
-  if (!ev) return -1;
-  if (e.c->pat_ev_listed) return read_spans({ev[0], ev[2], ev[3], ev[1]}, ms);
-  ms[1] = ms[2] = 0.0;
-  return read_spans({ev[0], ev[1]}, ms);
-}
-
-// (x, y) pairs, x to the right and y downwards (include/raycast_hip.h, rc_pattern)
-static const struct {
-  const char* name;
-  int grid, nsamples;
-  uint8_t xy[RC_PATTERN_MAX_SAMPLES][2];
-} kPatterns[] = {
-    {"diag2", 2, 2, {{0, 0}, {1, 1}}},
-    {"rgss4", 4, 4, {{1, 0}, {3, 1}, {0, 2}, {2, 3}}},
-    {"checker8", 4, 8, {{0, 0}, {2, 0}, {1, 1}, {3, 1}, {0, 2}, {2, 2}, {1, 3}, {3, 3}}},
-    {"queens8", 8, 8, {{3, 0}, {6, 1}, {2, 2}, {7, 3}, {1, 4}, {4, 5}, {0, 6}, {5, 7}}},
-};
-
-int rc_pattern_builtin(const char* name, rc_pattern* out) {
-  if (!name || !out) return -1;
-  for (const auto& p : kPatterns) {
-    if (std::strcmp(name, p.name)) continue;
-    std::memset(out, 0, sizeof *out);
-    out->grid = p.grid;
-    out->nsamples = p.nsamples;
-    for (int k = 0; k < p.nsamples; ++k) {
-      out->x[k] = p.xy[k][0];
-      out->y[k] = p.xy[k][1];
-    }
-    return 0;
-  }
-  return -1;
-}
-
-int rc_pattern_check(const rc_pattern* p) {
-  if (!p) {
-    std::fprintf(stderr, "Error: rc_pattern_check: a null pattern\n");
-    return -1;
-  }
-  const int g = p->grid, n = p->nsamples;
-  if (g != 2 && g != 4 && g != 8) {
-    std::fprintf(stderr, "Error: rc_pattern_check: grid %d is not 2, 4 or 8\n", g);
-    return -1;
-  }
-  if (n != 2 && n != 4 && n != 8 && n != 16) {
-    std::fprintf(stderr, "Error: rc_pattern_check: %d samples, not 2, 4, 8 or 16\n", n);
-    return -1;
-  }
-  if (n > g * g) {
-    std::fprintf(stderr, "Error: rc_pattern_check: %d samples on a %d x %d lattice of %d points\n",
-                 n, g, g, g * g);
-    return -1;
-  }
-  for (int k = 0; k < n; ++k) {
-    if (p->x[k] >= g || p->y[k] >= g) {
-      std::fprintf(stderr, "Error: rc_pattern_check: sample %d at (%d, %d) is off the %d x %d "
-                   "lattice\n", k, p->x[k], p->y[k], g, g);
-      return -1;
-    }
-    for (int j = 0; j < k; ++j)
-      if (p->x[j] == p->x[k] && p->y[j] == p->y[k]) {
-        std::fprintf(stderr, "Error: rc_pattern_check: samples %d and %d are both at (%d, %d)\n",
-                     j, k, p->x[k], p->y[k]);
-        return -1;
-      }
-  }
-  return 0;
-}
-
-int rc_pattern_env(const rc_options* opt, rc_pattern* out, int* threshold) {
-  const char* v = std::getenv("RAYCAST_PATTERN");
-  if (!v || !opt || !out || !threshold) return 0;
-  const char* colon = std::strchr(v, ':');
-  const std::string name = colon ? std::string(v, colon) : std::string(v);
-  rc_pattern pat;
-  if (rc_pattern_builtin(name.c_str(), &pat)) {
-    std::fprintf(stderr, "Warning: RAYCAST_PATTERN '%s': '%s' is not diag2, rgss4, checker8 or "
-                 "queens8, ignored\n", v, name.c_str());
-    return 0;
-  }
-  long t = 0;
-  if (colon) {
-    char* end = nullptr;
-    t = std::strtol(colon + 1, &end, 10);
-    if (colon[1] < '0' || colon[1] > '9' || *end != '\0' || t > 255) {
-      std::fprintf(stderr, "Warning: RAYCAST_PATTERN '%s': '%s' is not a threshold 0..255, "
-                   "ignored\n", v, colon + 1);
-      return 0;
-    }
-  }
-  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
-    std::fprintf(stderr, "Warning: RAYCAST_PATTERN '%s' is for fast and cuda mode (a parity image "
-                 "cannot be shot sparsely), ignored\n", v);
-    return 0;
-  }
-  if (RC_SSAA_FACTOR(opt->ssaa) > 1 || RC_SSAA_THRESHOLD(opt->ssaa) > 0) {
-    std::fprintf(stderr, "Warning: RAYCAST_PATTERN '%s' does not combine with RAYCAST_SSAA %d "
-                 "(the pattern carries its own grid), ignored\n", v, RC_SSAA_FACTOR(opt->ssaa));
-    return 0;
-  }
-  *out = pat;
-  *threshold = (int)t;
-  return 1;
-}
-
-// What the pattern entry points refuse from their arguments alone.
-static int pattern_refused(const char* who, const rc_options* opt, int W, int H,
-                           const rc_pattern* pat, int threshold) {
-  const int ss = ssaa_factor(opt, who);
-  if (ss < 0) return -1;   // ssaa_decode has said why (a threshold without a factor included)
-  if (ss > 1) {
-    std::fprintf(stderr, "Error: %s: ssaa %d in the options: the pattern carries the grid, leave "
-                 "ssaa at 0 or 1\n", who, opt->ssaa);
-    return -1;
-  }
-  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
-    std::fprintf(stderr, "Error: %s: a sample pattern is for fast and cuda mode: every pixel of a "
-                 "parity image depends on the scan-order carry of the whole image, so it cannot "
-                 "be shot sparsely; use plain ssaa\n", who);
-    return -1;
-  }
-  if (opt->num_gpus > 1) {
-    std::fprintf(stderr, "Error: %s: num_gpus %d: the row shards take no sample pattern\n", who,
-                 opt->num_gpus);
-    return -1;
-  }
-  if (rc_pattern_check(pat)) return -1;
-  if (threshold < 0 || threshold > 255) {
-    std::fprintf(stderr, "Error: %s: threshold %d is not 0..255\n", who, threshold);
-    return -1;
-  }
-  const int g = pat->grid;
-  if (W <= 0 || H <= 0 || W > (1 << 28) / g || H > (1 << 28) / g) {
-    std::fprintf(stderr, "Error: %s: %d x %d on a lattice of %d: both sides must be 1 .. 2^28 / "
-                 "g\n", who, W, H, g);
-    return -1;
-  }
-  if (threshold > 0 && (unsigned long long)W * (unsigned long long)H >= (1ull << 32)) {
-    std::fprintf(stderr, "Error: %s: %d x %d with a threshold is too large (32-bit pixel "
-                 "indices)\n", who, W, H);
-    return -1;
-  }
-  if (!rc::pattern_supported(W, H, g, pat->nsamples, threshold > 0)) {
-    std::fprintf(stderr, "Error: %s: %d x %d is too large for %d samples a pixel (at most 65535 "
-                 "rows of tiles)\n", who, W, H, pat->nsamples);
-    return -1;
-  }
-  return 0;
-}
-
-// ------------------------------------------------------- progressive supersampling --
-int rc_accum_stats_get(rc_accum_stats* out) {
-  Entered e;
-  if (!out || enter(kCurrentDevice, false, e) || !e.c->acc.valid) return -1;
-  const AccumFrame& f = e.c->acc;
-  HIP_TRY(hipEventSynchronize(f.done));   // the call's stream, up to its last pass
-  unsigned n[AccumFrame::kSlots][2] = {};   // per pass {listed, saturated}
-  HIP_TRY(hipMemcpy(n, f.count.p, (size_t)f.passes * sizeof n[0], hipMemcpyDeviceToHost));
-  out->passes = f.passes;
-  out->rays = 0;
-  for (int k = 0; k < f.passes; ++k) {
-    out->active_pixels = f.listed[k] ? (int64_t)n[k][0] : (int64_t)f.pixels;
-    out->saturated = (int64_t)n[k][1];
-    out->rays += (out->active_pixels - out->saturated) * f.samples[k];
-  }
-  return 0;
-}
-
-int rc_accum_phase_ms(double ms[2]) {
-  Entered e;
-  if (!ms || enter(kCurrentDevice, false, e)) return -1;
-  hipEvent_t* ev = e.c->span_ev[kSpanAccum];
-  if (!ev) return -1;
-  hipEvent_t first = ev[e.c->acc_ev_first];
-  if (e.c->acc_ev_listed) return read_spans({first, ev[3], ev[1]}, ms);
-  ms[0] = 0.0;
-  return read_spans({first, ev[1]}, ms + 1);
-}
-
-// hier<g>: point k is the bit-reversal r of k over 2 * lg bits; x takes r's even bits, y its odd
-// bits (include/raycast_hip.h, rc_sample_seq)
-static void hier_seq(int lg, rc_sample_seq* out) {
-  out->grid = 1 << lg;
-  out->nsamples = 1 << (2 * lg);
-  for (int k = 0; k < out->nsamples; ++k) {
-    int r = 0;
-    for (int b = 0; b < 2 * lg; ++b) r |= ((k >> b) & 1) << (2 * lg - 1 - b);
-    int x = 0, y = 0;
-    for (int i = 0; i < lg; ++i) {
-      x |= ((r >> (2 * i)) & 1) << i;
-      y |= ((r >> (2 * i + 1)) & 1) << i;
-    }
-    out->x[k] = (uint8_t)x;
-    out->y[k] = (uint8_t)y;
-  }
-}
-
-int rc_sample_seq_builtin(const char* name, rc_sample_seq* out) {
-  if (!name || !out) return -1;
-  std::memset(out, 0, sizeof *out);
-  for (int lg = 1; lg <= 3; ++lg) {
-    const char hier[] = {'h', 'i', 'e', 'r', (char)('0' + (1 << lg)), '\0'};
-    if (std::strcmp(name, hier)) continue;
-    hier_seq(lg, out);
-    return 0;
-  }
-  rc_pattern p;
-  if (rc_pattern_builtin(name, &p)) return -1;
-  out->grid = p.grid;
-  out->nsamples = p.nsamples;
-  std::memcpy(out->x, p.x, (size_t)p.nsamples);
-  std::memcpy(out->y, p.y, (size_t)p.nsamples);
-  return 0;
-}
-
-int rc_sample_seq_check(const rc_sample_seq* s) {
-  if (!s) {
-    std::fprintf(stderr, "Error: rc_sample_seq_check: a null sequence\n");
-    return -1;
-  }
-  const int g = s->grid, n = s->nsamples;
-  if (g != 2 && g != 4 && g != 8) {
-    std::fprintf(stderr, "Error: rc_sample_seq_check: grid %d is not 2, 4 or 8\n", g);
-    return -1;
-  }
-  const int most = g * g < RC_ACCUM_MAX_SAMPLES ? g * g : RC_ACCUM_MAX_SAMPLES;
-  if (n < 1 || n > most) {
-    std::fprintf(stderr, "Error: rc_sample_seq_check: %d samples, not 1..%d (a %d x %d lattice, at "
-                 "most %d)\n", n, most, g, g, RC_ACCUM_MAX_SAMPLES);
-    return -1;
-  }
-  for (int k = 0; k < n; ++k) {
-    if (s->x[k] >= g || s->y[k] >= g) {
-      std::fprintf(stderr, "Error: rc_sample_seq_check: sample %d at (%d, %d) is off the %d x %d "
-                   "lattice\n", k, s->x[k], s->y[k], g, g);
-      return -1;
-    }
-    for (int j = 0; j < k; ++j)
-      if (s->x[j] == s->x[k] && s->y[j] == s->y[k]) {
-        std::fprintf(stderr, "Error: rc_sample_seq_check: samples %d and %d are both at (%d, %d)\n",
-                     j, k, s->x[k], s->y[k]);
-        return -1;
-      }
-  }
-  return 0;
-}
-
-// What the accumulation entry points refuse from their arguments alone, whatever the passes:
-// `masked`: the call has a pass over the edge list, `dense`: one over every pixel.
-static int accum_refused(const char* who, const rc_options* opt, int W, int H,
-                         const rc_sample_seq* seq, int threshold, bool dense, bool masked) {
-  const int ss = ssaa_factor(opt, who);
-  if (ss < 0) return -1;   // ssaa_decode has said why (a threshold without a factor included)
-  if (ss > 1) {
-    std::fprintf(stderr, "Error: %s: ssaa %d in the options: the sample sequence carries the "
-                 "grid, leave ssaa at 0 or 1\n", who, opt->ssaa);
-    return -1;
-  }
-  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
-    std::fprintf(stderr, "Error: %s: accumulated samples are for fast and cuda mode: every pixel "
-                 "of a parity image depends on the scan-order carry of the whole image, so it "
-                 "cannot be shot sparsely; use plain ssaa\n", who);
-    return -1;
-  }
-  if (opt->num_gpus > 1) {
-    std::fprintf(stderr, "Error: %s: num_gpus %d: the row shards take no accumulator\n", who,
-                 opt->num_gpus);
-    return -1;
-  }
-  if (rc_sample_seq_check(seq)) return -1;
-  if (threshold < 0 || threshold > 255) {
-    std::fprintf(stderr, "Error: %s: threshold %d is not 0..255\n", who, threshold);
-    return -1;
-  }
-  const int g = seq->grid;
-  if (W <= 0 || H <= 0 || W > (1 << 28) / g || H > (1 << 28) / g) {
-    std::fprintf(stderr, "Error: %s: %d x %d on a lattice of %d: both sides must be 1 .. 2^28 / "
-                 "g\n", who, W, H, g);
-    return -1;
-  }
-  if (masked && (unsigned long long)W * (unsigned long long)H >= (1ull << 32)) {
-    std::fprintf(stderr, "Error: %s: %d x %d with a threshold is too large (32-bit pixel "
-                 "indices)\n", who, W, H);
-    return -1;
-  }
-  if ((dense && !rc::accum_supported(W, H, g, false)) ||
-      (masked && !rc::accum_supported(W, H, g, true))) {
-    std::fprintf(stderr, "Error: %s: %d x %d is too large for the kernels' grids (at most 65535 "
-                 "rows of tiles)\n", who, W, H);
-    return -1;
-  }
-  return 0;
-}
-
-// ------------------------------------------------------- windows of a virtual image --
-int rc_window_check(const rc_window* w, int W, int H, int s) {
-  const char* who = "rc_window_check";
-  if (!w) {
-    std::fprintf(stderr, "Error: %s: a null window\n", who);
-    return -1;
-  }
-  if (s == 0) s = 1;   // as rc_options.ssaa
-  if (s != 1 && s != 2 && s != 4 && s != 8) {
-    std::fprintf(stderr, "Error: %s: factor %d is not 0, 1, 2, 4 or 8\n", who, s);
-    return -1;
-  }
-  if (w->full_w < 1 || w->full_h < 1 || W < 1 || H < 1) {
-    std::fprintf(stderr, "Error: %s: a %d x %d window of a %d x %d image: every size must be at "
-                 "least 1\n", who, W, H, w->full_w, w->full_h);
-    return -1;
-  }
-  if (w->x0 < 0 || w->y0 < 0) {
-    std::fprintf(stderr, "Error: %s: origin (%d, %d): a window starts inside the image, at 0 or "
-                 "above\n", who, w->x0, w->y0);
-    return -1;
-  }
-  // W > full_w - x0 rather than x0 + W > full_w: no sum that could overflow
-  if (w->x0 > w->full_w || W > w->full_w - w->x0 || w->y0 > w->full_h || H > w->full_h - w->y0) {
-    std::fprintf(stderr, "Error: %s: a %d x %d window at (%d, %d) reaches outside the %d x %d "
-                 "image\n", who, W, H, w->x0, w->y0, w->full_w, w->full_h);
-    return -1;
-  }
-  if (w->full_w > 0x7fffffff / s || w->full_h > 0x7fffffff / s) {
-    std::fprintf(stderr, "Error: %s: %d times %d x %d: the subsample image's sides must stay "
-                 "within 2^31 - 1\n", who, s, w->full_w, w->full_h);
-    return -1;
-  }
-  if (!rc::window_supported(rc::Window{w->full_w, w->full_h, w->x0, w->y0}, W, H, s)) {
-    std::fprintf(stderr, "Error: %s: a %d x %d window at factor %d is too large for the kernel's "
-                 "grid (at most 65535 rows of 16-subsample tiles, 2^31 - 1 tiles)\n", who, W, H, s);
-    return -1;
-  }
-  return 0;
-}
-
-// one decimal field of RAYCAST_WINDOW: digits only, within int; *p moves behind it
-static bool window_field(const char** p, int* out) {
-  const char* q = *p;
-  long long v = 0;
-  if (*q < '0' || *q > '9') return false;
-  for (; *q >= '0' && *q <= '9'; ++q) {
-    v = v * 10 + (*q - '0');
-    if (v > 0x7fffffffll) return false;
-  }
-  *p = q;
-  *out = (int)v;
-  return true;
-}
-
-int rc_window_env(const rc_options* opt, int W, int H, rc_window* out) {
-  const char* v = std::getenv("RAYCAST_WINDOW");
-  if (!v || !opt || !out) return 0;
-  rc_window w;
-  const char* p = v;
-  int f[4] = {0, 0, 0, 0};
-  bool ok = window_field(&p, &f[0]);
-  const char seps[3] = {'x', '+', '+'};
-  for (int k = 0; ok && k < 3; ++k) ok = *p++ == seps[k] && window_field(&p, &f[k + 1]);
-  if (!ok || *p != '\0') {
-    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' is not FWxFH+X0+Y0 (four decimal numbers), "
-                 "ignored\n", v);
-    return 0;
-  }
-  w.full_w = f[0], w.full_h = f[1], w.x0 = f[2], w.y0 = f[3];
-  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
-    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' is for fast and cuda mode (a window of a "
-                 "parity image depends on the scan-order carry of every pixel before it), "
-                 "ignored\n", v);
-    return 0;
-  }
-  if (RC_SSAA_THRESHOLD(opt->ssaa) > 0) {
-    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' does not combine with "
-                 "RAYCAST_SSAA_ADAPTIVE, ignored\n", v);
-    return 0;
-  }
-  const char* pat = std::getenv("RAYCAST_PATTERN");
-  if (pat && pat[0]) {
-    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' does not combine with RAYCAST_PATTERN, "
-                 "ignored\n", v);
-    return 0;
-  }
-  const char* filt = std::getenv("RAYCAST_FILTER");
-  if (filt && !std::strcmp(filt, "tent")) {
-    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' does not combine with RAYCAST_FILTER=tent, "
-                 "ignored\n", v);
-    return 0;
-  }
-  if (opt->num_gpus > 1) {
-    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' does not combine with RAYCAST_GPUS %d (the "
-                 "row shards take no window), ignored\n", v, opt->num_gpus);
-    return 0;
-  }
-  if (rc_window_check(&w, W, H, RC_SSAA_FACTOR(opt->ssaa))) {
-    std::fprintf(stderr, "Warning: RAYCAST_WINDOW '%s' does not hold a %d x %d window, ignored\n",
-                 v, W, H);
-    return 0;
-  }
-  *out = w;
-  return 1;
-}
-
-// What the window render entry points refuse from their arguments alone.
-static int window_refused(const char* who, const rc_options* opt, const rc_window* win, int W,
-                          int H) {
-  const int ss = ssaa_factor(opt, who);
-  if (ss < 0) return -1;   // ssaa_decode has said why
-  if (ssaa_threshold(opt, who) > 0) {
-    std::fprintf(stderr, "Error: %s: ssaa %d carries an adaptive threshold: adaptive refinement of "
-                 "a window is an accumulation pass with a threshold "
-                 "(rc_accum_pass_window_device)\n", who, opt->ssaa);
-    return -1;
-  }
-  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
-    std::fprintf(stderr, "Error: %s: windows are for fast and cuda mode: a window of a parity "
-                 "image depends on the scan-order carry of every pixel before it\n", who);
-    return -1;
-  }
-  if (opt->num_gpus > 1) {
-    std::fprintf(stderr, "Error: %s: num_gpus %d: the row shards take no window\n", who,
-                 opt->num_gpus);
-    return -1;
-  }
-  return rc_window_check(win, W, H, ss);
-}
 
 void rc_default_options(rc_options* opt, int use_env) {
   opt->max_recursion = 7;   // C/raycast.c:14
@@ -1663,10 +1047,7 @@ int ensure_parity(DevCtx& c, FrameBufs& b, int W, int H, rc::ParityWork& w, int 
   return 0;
 }
 
-// The pending phase C (Pipe::cdefer) of the last submitted frame: on its lane's phase C
-// stream, or with `whole` on the device stream over every CU — the window's last frame, whose
-// phase C otherwise ran alone on the pixel partition after the last resolver (0.8 ms of a
-// 20-frame window's drain at quadric 4096^2 against ~0.47 ms on every CU).
+// (rc_runtime.h)
 int flush_phase_c(DevCtx& c, bool whole) {
   Pipe& p = c.pipe;
   if (!p.cdefer) return 0;
@@ -1691,31 +1072,7 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
                       bool timed, uint32_t* patch, hipEvent_t** evset,
                       const rc_filter* filt = nullptr);
 
-// The workspace bracket of a frame on `stream` through the device's one-frame workspace c.fb:
-// after the previous frame that used it, whatever its stream.  prepare() is what the frame
-// allocates before it waits for the workspace (a failure there leaves the stream untouched),
-// body() enqueues the frame.
-template <class Prepare, class Body>
-int ws_frame(DevCtx& c, hipStream_t stream, Prepare prepare, Body body) {
-  // a frame in flight's held-back phase C goes out first, so that a device synchronisation
-  // after this call completes it (rc_frames_wait stays the frames' completion point)
-  if (flush_phase_c(c, false) || prepare()) return -1;
-  if (c.ws_valid && c.ws_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, c.ws_ev, 0));
-  const int rc = body();
-  // recorded even after a failed enqueue: whatever was enqueued stays ordered
-  HIP_TRY(hipEventRecord(c.ws_ev, stream));
-  c.ws_stream = stream;
-  c.ws_valid = true;
-  return rc;
-}
-
-// The event set of the frame being enqueued: set 0, or inside an rc_profile_begin/end window
-// the next set of the pool.  The ownership rule of the sets' spans (DevCtx::span_ev) is here and
-// nowhere else: a frame that records the set anew (`records`) takes it from every feature that
-// still points at it, so no rc_*_phase_ms reads another frame's spans; `owner` (or kSpanOwners
-// for none) loses its own spans whatever set they were in, until the frame's enqueue has
-// succeeded and stores the set in span_ev[owner].  Under profiling consecutive frames record
-// different sets, so several owners can stay valid at once.
+// (rc_runtime.h: the one place that picks an event set and invalidates spans)
 hipEvent_t* claim_event_set(DevCtx& c, int owner, bool parity, bool records) {
   hipEvent_t* ev = c.ev[0];
   if (c.prof_active) {
@@ -1780,7 +1137,7 @@ static int adaptive_refused(const rc_options* opt, const char* who, int ss, int 
 // context's buffer, then its box filter into d_out.  The frame's events, counts and hand-off
 // log are those of the large image; its last event is moved behind the box filter.  With filt
 // (whole images: the halo needs the neighbouring rows) the separable filter of rc_filter.hip
-// takes the box filter's place.  A timed frame also records filt_mid between the two passes
+// takes the box filter's place.  A timed frame also records filt.mid between the two passes
 // (rc_filter_phase_ms).
 int enqueue_render_two_pass(DevCtx& c, const rc_scene* s, int W, int H, int ss, int row0,
                             int row_step, int nrows, const rc_options* opt, uint8_t* d_out,
@@ -1797,7 +1154,7 @@ int enqueue_render_two_pass(DevCtx& c, const rc_scene* s, int W, int H, int ss, 
                  "%d): the filter's halo needs the neighbouring rows\n", row0, nrows, H);
     return -1;
   }
-  if (timed && !c.filt_mid) HIP_TRY(hipEventCreate(&c.filt_mid));
+  if (timed && !c.filt.mid) HIP_TRY(hipEventCreate(&c.filt.mid));
   const int sw = W * ss, sh = H * ss;
   if (c.ssaa.ensure((size_t)sw * 3 * (size_t)nrows * ss)) {
     std::fprintf(stderr, "Error: out of device memory for the supersampled image (%dx%d)\n", sw,
@@ -1811,7 +1168,7 @@ int enqueue_render_two_pass(DevCtx& c, const rc_scene* s, int W, int H, int ss, 
                         timed, nullptr, &ev))
     return -1;
   if (evset) *evset = ev;
-  if (timed) HIP_TRY(hipEventRecord(c.filt_mid, stream));
+  if (timed) HIP_TRY(hipEventRecord(c.filt.mid, stream));
   if (filt)
     HIP_TRY(rc::launch_filter_down((const uint8_t*)c.ssaa.p, W, H, ss, filt->taps, filt->ntaps,
                                    d_out, stream));
@@ -1821,7 +1178,7 @@ int enqueue_render_two_pass(DevCtx& c, const rc_scene* s, int W, int H, int ss, 
   if (timed) {
     HIP_TRY(hipEventRecord(ev[parity ? 4 : 1], stream));
     c.span_ev[kSpanFilter] = ev;
-    c.filt_end = parity ? 4 : 1;
+    c.filt.end = parity ? 4 : 1;
   }
   return 0;
 }
@@ -1918,247 +1275,6 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
   w.inject = take_inject();
   HIP_TRY(rc::launch_parity(ls, W, H, maxrec, d_out, w, zc, stream, timed ? ev + 1 : nullptr));
   return c.lone_log.enqueue(w.team, stream);
-}
-
-// Rate-map supersampling's refusals that do not depend on the entry point (rc_render_rates*).
-static int rates_refused(const rc_options* opt, const char* who, int W, int H) {
-  const int ss = ssaa_factor(opt, who);
-  if (ss < 0) return -1;   // ssaa_decode has said why (a threshold without a factor included)
-  if (ss > 1) {
-    std::fprintf(stderr, "Error: %s: ssaa %d in the options: the rate map carries the factor "
-                 "per pixel, leave ssaa at 0 or 1\n", who, opt->ssaa);
-    return -1;
-  }
-  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) {
-    std::fprintf(stderr, "Error: %s: a rate map is for fast and cuda mode: every pixel of a "
-                 "parity image depends on the scan-order carry of the whole image, so it cannot "
-                 "be shot sparsely\n", who);
-    return -1;
-  }
-  if (opt->num_gpus > 1) {
-    std::fprintf(stderr, "Error: %s: num_gpus %d: the row shards take no rate map\n", who,
-                 opt->num_gpus);
-    return -1;
-  }
-  if (!rc::rates_supported(W, H)) {
-    std::fprintf(stderr, "Error: %s: %d x %d is too large for a rate map (32-bit pixel indices "
-                 "at 8 subsamples a side, at most 65535 rows of tiles)\n", who, W, H);
-    return -1;
-  }
-  return 0;
-}
-
-// One rate-map frame on `stream` through the device's one-frame workspace (the caller holds
-// c.mu and has passed rates_refused): the rate-1 pixels with the binning, then the three lists'
-// refinements, with no host wait in between.  The host does not know which lists are empty, so
-// all three are launched.
-static int enqueue_rates(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
-                         const uint8_t* d_rates, uint8_t* d_out, hipStream_t stream) {
-  auto prepare = [&]() -> int {
-    const size_t entries = (size_t)W * H;
-    if (c.aa_list.ensure(entries * sizeof(uint32_t)) ||
-        c.rate_list.ensure(entries * sizeof(uint32_t)) || c.rate_count.ensure(32)) {
-      std::fprintf(stderr, "Error: out of device memory for the rate lists (%d x %d)\n", W, H);
-      return -1;
-    }
-    if (!c.rate_done) HIP_TRY(hipEventCreateWithFlags(&c.rate_done, hipEventDisableTiming));
-    return 0;
-  };
-  return ws_frame(c, stream, prepare, [&]() -> int {
-    rc::LaunchScene ls;
-    if (upload_scene(c.fb, stream, s, ls)) return -1;
-    unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
-    unsigned* cnt = (unsigned*)c.rate_count.p;
-    uint32_t* list4 = (uint32_t*)c.aa_list.p;
-    uint32_t* list28 = (uint32_t*)c.rate_list.p;
-    HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
-    HIP_TRY(hipMemsetAsync(cnt, 0, 32, stream));
-    const int maxrec = opt->max_recursion;
-    const bool cuda = opt->mode == RC_MODE_CUDA;
-    hipEvent_t* ev = claim_event_set(c, kSpanRates, false, true);
-    // The lists follow the map's row-major order, so over a uniform region entry k is pixel
-    // k + const and a wave's static stride (workgroups * 4 waves * pixels per step) that is a
-    // multiple of W keeps the wave in one column of the image: the waves whose column crosses
-    // the expensive shapes finish last.  An odd number of workgroups makes the stride drift
-    // through the columns (measured: DESIGN.md section 12).  An explicit adaptive_blocks holds.
-    const int want = tune().adaptive_blocks;
-    auto blocks = [&](int ss) {
-      const int b = rc::aa_refine_blocks(W, H, ss, c.cus, want);
-      return want <= 0 && b > 2 && (b & 1) == 0 ? b - 1 : b;
-    };
-    HIP_TRY(hipEventRecord(ev[0], stream));
-    HIP_TRY(rc::launch_rates_render(ls, W, H, maxrec, d_rates, d_out, list4, list28, cnt, zc,
-                                    stream, cuda));
-    HIP_TRY(hipEventRecord(ev[2], stream));
-    HIP_TRY(rc::launch_aa_refine(ls, W, H, 2, maxrec, list28, cnt, d_out, zc,
-                                 blocks(2), stream, cuda));
-    HIP_TRY(rc::launch_aa_refine(ls, W, H, 4, maxrec, list4, cnt + 1, d_out, zc,
-                                 blocks(4), stream, cuda));
-    HIP_TRY(rc::launch_rates_refine8(ls, W, H, maxrec, list28, cnt + 2, d_out, zc,
-                                     blocks(8), stream, cuda));
-    HIP_TRY(hipEventRecord(c.rate_done, stream));
-    HIP_TRY(hipEventRecord(ev[1], stream));
-    c.rate_valid = true;
-    c.span_ev[kSpanRates] = ev;
-    return 0;
-  });
-}
-
-// One pattern frame on `stream` through the device's one-frame workspace (the caller holds c.mu
-// and has passed pattern_refused).  at = 0: the dense kernel.  at > 0: the one-ray image by the
-// plain kernel, the adaptive path's edge list (launch_aa_mark into aa_list), then the pattern
-// kernel over the list: three launches with no host wait in between.
-static int enqueue_pattern(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
-                           const rc_pattern* pat, int at, uint8_t* d_out, hipStream_t stream) {
-  auto prepare = [&]() -> int {
-    if (at > 0 && (c.pat.count.ensure(8) || c.aa_list.ensure((size_t)W * H * sizeof(uint32_t)))) {
-      std::fprintf(stderr, "Error: out of device memory for the edge list (%d x %d)\n", W, H);
-      return -1;
-    }
-    if (at > 0 && !c.pat.done)
-      HIP_TRY(hipEventCreateWithFlags(&c.pat.done, hipEventDisableTiming));
-    return 0;
-  };
-  return ws_frame(c, stream, prepare, [&]() -> int {
-    rc::LaunchScene ls;
-    if (upload_scene(c.fb, stream, s, ls)) return -1;
-    unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
-    unsigned* cnt = (unsigned*)c.pat.count.p;
-    uint32_t* list = (uint32_t*)c.aa_list.p;
-    HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
-    if (at > 0) HIP_TRY(hipMemsetAsync(cnt, 0, 8, stream));
-    const int maxrec = opt->max_recursion, g = pat->grid, n = pat->nsamples;
-    const bool cuda = opt->mode == RC_MODE_CUDA;
-    hipEvent_t* ev = claim_event_set(c, kSpanPattern, false, true);
-    HIP_TRY(hipEventRecord(ev[0], stream));
-    if (at == 0) {
-      HIP_TRY(rc::launch_pattern(ls, W, H, g, n, pat->x, pat->y, maxrec, d_out, zc, stream, cuda));
-    } else {
-      HIP_TRY(rc::launch_render(ls, W, H, 0, 1, H, maxrec, d_out, zc, stream, cuda));
-      HIP_TRY(hipEventRecord(ev[2], stream));
-      HIP_TRY(rc::launch_aa_mark(d_out, W, H, at, list, cnt, stream));
-      HIP_TRY(hipEventRecord(ev[3], stream));
-      HIP_TRY(rc::launch_pattern_list(
-          ls, W, H, g, n, pat->x, pat->y, maxrec, list, cnt, d_out, zc,
-          rc::pattern_list_blocks(W, H, n, c.cus, tune().adaptive_blocks), stream, cuda));
-    }
-    HIP_TRY(hipEventRecord(ev[1], stream));
-    // behind the span's end, and only where rc_pattern_stats_get has a count to wait for
-    if (at > 0) HIP_TRY(hipEventRecord(c.pat.done, stream));
-    c.pat.valid = true;
-    c.pat.rays = n;
-    c.pat_t = at;
-    c.pat.pixels = (long long)W * H;
-    c.span_ev[kSpanPattern] = ev;
-    c.pat_ev_listed = at > 0;
-    return 0;
-  });
-}
-
-// One pass of an accumulation call: samples [first, first + count) of the sequence, over every
-// pixel (at = 0) or over the pixels whose contrast in `out` reaches at; reset: the records count
-// as zero and are not read.
-struct AccumPass {
-  int first, count, at;
-  bool reset;
-};
-
-// The passes of one accumulation call on `stream` through the device's one-frame workspace (the
-// caller holds c.mu and has passed accum_refused and the range checks; at most
-// AccumFrame::kSlots passes).  A pass over every pixel is one launch; a masked pass is the
-// adaptive path's edge list (launch_aa_mark over d_out into aa_list) and the list kernel.
-// Nothing waits for the host: pass k counts into slot k of the call's counter block.
-// win (or null): the samples are those of this window of a virtual image (it has passed
-// rc_window_check at the sequence's g); the edge list, the records and the image stay the
-// window's own W x H.
-static int enqueue_accum(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
-                         const rc_sample_seq* seq, const AccumPass* passes, int npasses,
-                         rc_accum_px* d_acc, uint8_t* d_out, hipStream_t stream,
-                         const rc_window* win = nullptr) {
-  bool masked = false;
-  for (int k = 0; k < npasses; ++k) masked = masked || passes[k].at > 0;
-  auto prepare = [&]() -> int {
-    if (c.acc.count.ensure(AccumFrame::kSlots * 8) ||
-        (masked && c.aa_list.ensure((size_t)W * H * sizeof(uint32_t)))) {
-      std::fprintf(stderr, "Error: out of device memory for the edge list (%d x %d)\n", W, H);
-      return -1;
-    }
-    if (!c.acc.done) HIP_TRY(hipEventCreateWithFlags(&c.acc.done, hipEventDisableTiming));
-    return 0;
-  };
-  return ws_frame(c, stream, prepare, [&]() -> int {
-    rc::LaunchScene ls;
-    if (upload_scene(c.fb, stream, s, ls)) return -1;
-    unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
-    unsigned* cnt = (unsigned*)c.acc.count.p;
-    uint32_t* list = (uint32_t*)c.aa_list.p;
-    c.acc.valid = false;   // the block is this call's from here on
-    HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
-    HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)npasses * 8, stream));
-    const int maxrec = opt->max_recursion, g = seq->grid;
-    const bool cuda = opt->mode == RC_MODE_CUDA;
-    const rc::Window vw = win ? rc::Window{win->full_w, win->full_h, win->x0, win->y0}
-                              : rc::Window{W, H, 0, 0};
-    hipEvent_t* ev = claim_event_set(c, kSpanAccum, false, true);
-    HIP_TRY(hipEventRecord(ev[0], stream));
-    for (int k = 0; k < npasses; ++k) {
-      const AccumPass& p = passes[k];
-      const bool last = k + 1 == npasses;
-      if (last && k > 0) HIP_TRY(hipEventRecord(ev[2], stream));
-      const uint8_t* px = seq->x + p.first;
-      const uint8_t* py = seq->y + p.first;
-      unsigned* slot = cnt + 2 * k;
-      if (p.at == 0) {
-        if (win)
-          HIP_TRY(rc::launch_accum_window(ls, vw, W, H, g, p.count, px, py, p.reset, maxrec, d_acc,
-                                          d_out, zc, slot + 1, stream, cuda));
-        else
-          HIP_TRY(rc::launch_accum(ls, W, H, g, p.count, px, py, p.reset, maxrec, d_acc, d_out, zc,
-                                   slot + 1, stream, cuda));
-      } else {
-        HIP_TRY(rc::launch_aa_mark(d_out, W, H, p.at, list, slot, stream));
-        if (last) HIP_TRY(hipEventRecord(ev[3], stream));
-        const int blocks = rc::accum_list_blocks(W, H, c.cus, tune().adaptive_blocks);
-        if (win)
-          HIP_TRY(rc::launch_accum_list_window(ls, vw, W, H, g, p.count, px, py, maxrec, list, slot,
-                                               d_acc, d_out, zc, slot + 1, blocks, stream, cuda));
-        else
-          HIP_TRY(rc::launch_accum_list(ls, W, H, g, p.count, px, py, maxrec, list, slot, d_acc,
-                                        d_out, zc, slot + 1, blocks, stream, cuda));
-      }
-      c.acc.samples[k] = (uint8_t)p.count;
-      c.acc.listed[k] = p.at > 0;
-    }
-    HIP_TRY(hipEventRecord(ev[1], stream));
-    HIP_TRY(hipEventRecord(c.acc.done, stream));
-    c.acc.valid = true;
-    c.acc.passes = npasses;
-    c.acc.pixels = (long long)W * H;
-    c.span_ev[kSpanAccum] = ev;
-    c.acc_ev_first = npasses > 1 ? 2 : 0;
-    c.acc_ev_listed = passes[npasses - 1].at > 0;
-    return 0;
-  });
-}
-
-// One window frame on `stream` through the device's one-frame workspace (the caller holds c.mu
-// and has passed window_refused): one launch of k_window at the options' factor.
-static int enqueue_window(DevCtx& c, const rc_scene* s, const rc_window* win, int W, int H,
-                          const rc_options* opt, uint8_t* d_out, hipStream_t stream) {
-  return ws_frame(c, stream, [] { return 0; }, [&]() -> int {
-    rc::LaunchScene ls;
-    if (upload_scene(c.fb, stream, s, ls)) return -1;
-    unsigned long long* zc = (unsigned long long*)c.fb.zcount.p;
-    HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
-    hipEvent_t* ev = claim_event_set(c, kSpanWindow, false, true);
-    HIP_TRY(hipEventRecord(ev[0], stream));
-    HIP_TRY(rc::launch_window(ls, rc::Window{win->full_w, win->full_h, win->x0, win->y0}, W, H,
-                              ssaa_factor(opt, "rc_render_window"), opt->max_recursion, d_out, zc,
-                              stream, opt->mode == RC_MODE_CUDA));
-    HIP_TRY(hipEventRecord(ev[1], stream));
-    c.span_ev[kSpanWindow] = ev;
-    return 0;
-  });
 }
 
 // After a synchronised parity render: the resolver's and phase C's bounded spins set
@@ -2410,7 +1526,7 @@ void fill_device_timing(DevCtx& c, const rc_options* opt, rc_timing* t,
 }
 
 // ------------------------------------------------------- the frame scaffold: tails --
-constexpr long long kNoLog = -1;   // `own` of a frame that logs no hand-off entry
+// (finish_device, HostTail and finish_host are declared and documented in rc_runtime.h)
 
 // After the frame's stream has been synchronised: its own latched hand-off words (ring entry
 // `own`).  Its own failure is reported by this call and consumed; another stream's frame that
@@ -2424,9 +1540,6 @@ int own_frame_failed(DevCtx& c, long long own, const rc_options* opt) {
   return -1;
 }
 
-// The tail of a device-resident call: without a timing record it returns with its frame
-// enqueued; with one it waits for the frame.  own (or kNoLog): the frame's entry in lone_log,
-// for the calls whose frame may be a parity frame.
 int finish_device(DevCtx& c, const rc_options* opt, hipStream_t st, rc_timing* timing,
                   long long own) {
   if (!timing) return 0;
@@ -2459,8 +1572,6 @@ int enqueue_tail_counts(DevCtx& c, bool parity) {
   return 0;
 }
 
-using HostClock = std::chrono::steady_clock;
-
 // the host-side pair of rc_timing: the copy since td, the call since t0
 void stamp_host_ms(rc_timing* t, HostClock::time_point td, HostClock::time_point t0) {
   if (!t) return;
@@ -2468,15 +1579,6 @@ void stamp_host_ms(rc_timing* t, HostClock::time_point td, HostClock::time_point
   t->total_ms = std::chrono::duration<double, std::milli>(HostClock::now() - t0).count();
 }
 
-// The tail of a host-pixmap call whose frame is enqueued on c.stream with its image in c.out:
-// the copy into the caller's pixmap, the wait, the timing record (t0: the call's entry).
-// What the entry points do differently is explicit: tail_counts (the frame's counts through
-// pin_tail rather than two copies after the frame), prefault (the pixmap is faulted in while the
-// GPU renders), own (or kNoLog: the frame's hand-off entry is verified).
-struct HostTail {
-  bool tail_counts, prefault;
-  long long own;
-};
 int finish_host(DevCtx& c, const rc_options* opt, uint8_t* pixmap, size_t bytes,
                 const rc_tuning& tu, const HostTail& how, rc_timing* timing,
                 HostClock::time_point t0) {
@@ -2513,322 +1615,6 @@ int rc_render_device(const rc_scene* s, int W, int H, int row0, int row_step, in
   const int rc = enqueue_render(*c, s, W, H, row0, row_step, nrows, opt, d_out, st, true);
   c->stream = saved;
   return rc ? -1 : finish_device(*c, opt, st, timing, own);
-}
-
-int rc_render_rates_device(const rc_scene* s, int W, int H, const rc_options* opt,
-                           const uint8_t* d_rates, uint8_t* d_out, void* stream,
-                           rc_timing* timing) {
-  if (!s || !opt || !d_rates || !d_out) {
-    std::fprintf(stderr, "Error: rc_render_rates_device: a null pointer\n");
-    return -1;
-  }
-  if (W <= 0 || H <= 0) return -1;
-  if (rates_refused(opt, "rc_render_rates_device", W, H)) return -1;
-  Entered e;
-  if (enter(kCurrentDevice, true, e)) return -1;
-  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
-  if (enqueue_rates(*e.c, s, W, H, opt, d_rates, d_out, st)) return -1;
-  return finish_device(*e.c, opt, st, timing, kNoLog);
-}
-
-int rc_render_rates(const rc_scene* s, int W, int H, const rc_options* opt, const uint8_t* rates,
-                    uint8_t* pixmap, rc_timing* timing) {
-  if (!s || !opt || !rates || !pixmap) {
-    std::fprintf(stderr, "Error: rc_render_rates: a null pointer\n");
-    return -1;
-  }
-  if (W <= 0 || H <= 0) return -1;
-  const auto t0 = HostClock::now();
-  if (rates_refused(opt, "rc_render_rates", W, H)) return -1;
-  const size_t pixels = (size_t)W * H;
-  for (size_t i = 0; i < pixels; ++i) {
-    const unsigned r = rates[i];
-    if (r > 8u || !((0x117u >> r) & 1u)) {   // bits 0, 1, 2, 4, 8
-      std::fprintf(stderr, "Error: rc_render_rates: rate %u at pixel (%zu, %zu) is not 0, 1, 2, "
-                   "4 or 8\n", r, i % (size_t)W, i / (size_t)W);
-      return -1;
-    }
-  }
-  if (timing) std::memset(timing, 0, sizeof *timing);
-  const rc_tuning tu = tune();
-  Entered e;
-  if (enter_host(opt, e)) return -1;
-  DevCtx* c = e.c;
-  if (c->out.ensure(pixels * 3) || c->rate_map.ensure(pixels)) {
-    std::fprintf(stderr, "Error: out of device memory for the image and its rate map (%d x %d)\n",
-                 W, H);
-    return -1;
-  }
-  uint8_t* d_out = (uint8_t*)c->out.p;
-  uint8_t* d_rates = (uint8_t*)c->rate_map.p;
-  // the pixmap goes in as well as out: the bytes of rate-0 pixels come back as they were
-  HIP_TRY(hipMemcpyAsync(d_rates, rates, pixels, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_out, pixmap, pixels * 3, hipMemcpyHostToDevice, c->stream));
-  if (enqueue_rates(*c, s, W, H, opt, d_rates, d_out, c->stream)) return -1;
-  return finish_host(*c, opt, pixmap, pixels * 3, tu, {false, false, kNoLog}, timing, t0);
-}
-
-int rc_render_pattern_device(const rc_scene* s, int W, int H, const rc_options* opt,
-                             const rc_pattern* pat, int threshold, uint8_t* d_out, void* stream,
-                             rc_timing* timing) {
-  if (!s || !opt || !pat || !d_out) {
-    std::fprintf(stderr, "Error: rc_render_pattern_device: a null pointer\n");
-    return -1;
-  }
-  if (pattern_refused("rc_render_pattern_device", opt, W, H, pat, threshold)) return -1;
-  Entered e;
-  if (enter(kCurrentDevice, true, e)) return -1;
-  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
-  if (enqueue_pattern(*e.c, s, W, H, opt, pat, threshold, d_out, st)) return -1;
-  return finish_device(*e.c, opt, st, timing, kNoLog);
-}
-
-int rc_render_pattern(const rc_scene* s, int W, int H, const rc_options* opt,
-                      const rc_pattern* pat, int threshold, uint8_t* pixmap, rc_timing* timing) {
-  if (!s || !opt || !pat || !pixmap) {
-    std::fprintf(stderr, "Error: rc_render_pattern: a null pointer\n");
-    return -1;
-  }
-  const auto t0 = HostClock::now();
-  if (pattern_refused("rc_render_pattern", opt, W, H, pat, threshold)) return -1;
-  if (timing) std::memset(timing, 0, sizeof *timing);
-  const rc_tuning tu = tune();
-  Entered e;
-  if (enter_host(opt, e)) return -1;
-  DevCtx* c = e.c;
-  const size_t bytes = (size_t)W * H * 3;
-  if (c->out.ensure(bytes)) {
-    std::fprintf(stderr, "Error: out of device memory for the image (%d x %d)\n", W, H);
-    return -1;
-  }
-  if (enqueue_pattern(*c, s, W, H, opt, pat, threshold, (uint8_t*)c->out.p, c->stream)) return -1;
-  return finish_host(*c, opt, pixmap, bytes, tu, {false, false, kNoLog}, timing, t0);
-}
-
-// rc_accum_pass_device and rc_accum_pass_window_device (win: null for the former)
-static int accum_pass(const char* who, const rc_scene* s, const rc_window* win, int W, int H,
-                      const rc_options* opt, const rc_sample_seq* seq, int first, int count,
-                      int threshold, int reset, rc_accum_px* d_acc, uint8_t* d_out, void* stream,
-                      rc_timing* timing) {
-  if (!s || !opt || !seq || !d_acc || !d_out) {
-    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
-    return -1;
-  }
-  if ((uintptr_t)d_acc & 7u) {
-    std::fprintf(stderr, "Error: %s: the accumulator is not 8-byte aligned\n", who);
-    return -1;
-  }
-  if (accum_refused(who, opt, W, H, seq, threshold, threshold == 0, threshold > 0)) return -1;
-  if (win && rc_window_check(win, W, H, seq->grid)) return -1;
-  if (count < 1 || count > 16 || first < 0 || first > seq->nsamples - count) {
-    std::fprintf(stderr, "Error: %s: samples [%d, %d + %d) of a sequence of %d: a pass takes 1..16 "
-                 "samples inside the sequence\n", who, first, first, count, seq->nsamples);
-    return -1;
-  }
-  if (reset && threshold > 0) {
-    std::fprintf(stderr, "Error: %s: reset with threshold %d: a reset pass takes every pixel "
-                 "(there is no image yet to find edges in), leave the threshold at 0\n", who,
-                 threshold);
-    return -1;
-  }
-  Entered e;
-  if (enter(kCurrentDevice, true, e)) return -1;
-  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
-  const AccumPass pass{first, count, threshold, reset != 0};
-  if (enqueue_accum(*e.c, s, W, H, opt, seq, &pass, 1, d_acc, d_out, st, win)) return -1;
-  return finish_device(*e.c, opt, st, timing, kNoLog);
-}
-
-int rc_accum_pass_device(const rc_scene* s, int W, int H, const rc_options* opt,
-                         const rc_sample_seq* seq, int first, int count, int threshold, int reset,
-                         rc_accum_px* d_acc, uint8_t* d_out, void* stream, rc_timing* timing) {
-  return accum_pass("rc_accum_pass_device", s, nullptr, W, H, opt, seq, first, count, threshold,
-                    reset, d_acc, d_out, stream, timing);
-}
-
-int rc_accum_pass_window_device(const rc_scene* s, const rc_window* win, int W, int H,
-                                const rc_options* opt, const rc_sample_seq* seq, int first,
-                                int count, int threshold, int reset, rc_accum_px* d_acc,
-                                uint8_t* d_out, void* stream, rc_timing* timing) {
-  const char* who = "rc_accum_pass_window_device";
-  if (!win) {
-    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
-    return -1;
-  }
-  return accum_pass(who, s, win, W, H, opt, seq, first, count, threshold, reset, d_acc, d_out,
-                    stream, timing);
-}
-
-int rc_render_window_device(const rc_scene* s, const rc_window* win, int W, int H,
-                            const rc_options* opt, uint8_t* d_out, void* stream,
-                            rc_timing* timing) {
-  const char* who = "rc_render_window_device";
-  if (!s || !win || !opt || !d_out) {
-    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
-    return -1;
-  }
-  if (window_refused(who, opt, win, W, H)) return -1;
-  Entered e;
-  if (enter(kCurrentDevice, true, e)) return -1;
-  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
-  if (enqueue_window(*e.c, s, win, W, H, opt, d_out, st)) return -1;
-  return finish_device(*e.c, opt, st, timing, kNoLog);
-}
-
-int rc_render_window(const rc_scene* s, const rc_window* win, int W, int H, const rc_options* opt,
-                     uint8_t* pixmap, rc_timing* timing) {
-  const char* who = "rc_render_window";
-  if (!s || !win || !opt || !pixmap) {
-    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
-    return -1;
-  }
-  const auto t0 = HostClock::now();
-  if (window_refused(who, opt, win, W, H)) return -1;
-  if (timing) std::memset(timing, 0, sizeof *timing);
-  const rc_tuning tu = tune();
-  Entered e;
-  if (enter_host(opt, e)) return -1;
-  DevCtx* c = e.c;
-  const size_t bytes = (size_t)W * H * 3;
-  if (c->out.ensure(bytes)) {
-    std::fprintf(stderr, "Error: out of device memory for the image (%d x %d)\n", W, H);
-    return -1;
-  }
-  if (enqueue_window(*c, s, win, W, H, opt, (uint8_t*)c->out.p, c->stream)) return -1;
-  return finish_host(*c, opt, pixmap, bytes, tu, {false, false, kNoLog}, timing, t0);
-}
-
-int rc_accum_resolve_device(const rc_accum_px* d_acc, int W, int H, uint8_t* d_out, void* stream) {
-  const char* who = "rc_accum_resolve_device";
-  if (!d_acc || !d_out) {
-    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
-    return -1;
-  }
-  if ((uintptr_t)d_acc & 7u) {
-    std::fprintf(stderr, "Error: %s: the accumulator is not 8-byte aligned\n", who);
-    return -1;
-  }
-  if (W <= 0 || H <= 0 || ((unsigned long long)W * (unsigned long long)H + 255) / 256 > 0x7fffffffull) {
-    std::fprintf(stderr, "Error: %s: %d x %d: both sides must be at least 1 and the image at most "
-                 "2^39 - 256 pixels (one grid)\n", who, W, H);
-    return -1;
-  }
-  Entered e;
-  if (enter(kCurrentDevice, false, e)) return -1;
-  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
-  HIP_TRY(rc::launch_accum_resolve(d_acc, W, H, d_out, st));
-  return 0;
-}
-
-int rc_render_accum(const rc_scene* s, int W, int H, const rc_options* opt,
-                    const rc_sample_seq* seq, int dense, int threshold, uint8_t* pixmap,
-                    rc_timing* timing) {
-  const char* who = "rc_render_accum";
-  if (!s || !opt || !seq || !pixmap) {
-    std::fprintf(stderr, "Error: %s: a null pointer\n", who);
-    return -1;
-  }
-  const auto t0 = HostClock::now();
-  // which kernels run is known once the sequence and dense have been checked; the limits of both
-  // are tested here, a call that needs only one of them being a sub-case of no interest
-  if (accum_refused(who, opt, W, H, seq, threshold, true, threshold > 0)) return -1;
-  if (dense < 1 || dense > seq->nsamples) {
-    std::fprintf(stderr, "Error: %s: dense %d is not 1..%d (the sequence's length)\n", who, dense,
-                 seq->nsamples);
-    return -1;
-  }
-  // samples [0, dense) for every pixel in chunks of at most 16, the first chunk resetting the
-  // accumulator; then one single-sample pass for each of the others
-  AccumPass passes[AccumFrame::kSlots];
-  int np = 0;
-  for (int k = 0; k < dense; k += 16)
-    passes[np++] = {k, dense - k < 16 ? dense - k : 16, 0, k == 0};
-  for (int k = dense; k < seq->nsamples; ++k) passes[np++] = {k, 1, threshold, false};
-  if (timing) std::memset(timing, 0, sizeof *timing);
-  const rc_tuning tu = tune();
-  Entered e;
-  if (enter_host(opt, e)) return -1;
-  DevCtx* c = e.c;
-  const size_t pixels = (size_t)W * H;
-  if (c->out.ensure(pixels * 3) || c->accum_px.ensure(pixels * sizeof(rc_accum_px))) {
-    std::fprintf(stderr, "Error: out of device memory for the image and its accumulator "
-                 "(%d x %d)\n", W, H);
-    return -1;
-  }
-  if (enqueue_accum(*c, s, W, H, opt, seq, passes, np, (rc_accum_px*)c->accum_px.p,
-                    (uint8_t*)c->out.p, c->stream))
-    return -1;
-  return finish_host(*c, opt, pixmap, pixels * 3, tu, {false, false, kNoLog}, timing, t0);
-}
-
-int rc_render_filtered_device(const rc_scene* s, int W, int H, const rc_options* opt,
-                              const rc_filter* f, uint8_t* d_out, void* stream,
-                              rc_timing* timing) {
-  if (!s || !opt || !f || !d_out) {
-    std::fprintf(stderr, "Error: rc_render_filtered_device: a null pointer\n");
-    return -1;
-  }
-  if (filtered_refused("rc_render_filtered_device", opt, W, H, f) < 0) return -1;
-  Entered e;
-  if (enter(kCurrentDevice, true, e)) return -1;
-  DevCtx* c = e.c;
-  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-  const long long own = c->lone_log.head;
-  hipStream_t saved = c->stream;   // the scene upload and events follow the caller's stream
-  c->stream = st;
-  const int rc = enqueue_render(*c, s, W, H, 0, 1, H, opt, d_out, st, true, nullptr, nullptr, f);
-  c->stream = saved;
-  return rc ? -1 : finish_device(*c, opt, st, timing, own);
-}
-
-int rc_render_filtered(const rc_scene* s, int W, int H, const rc_options* opt, const rc_filter* f,
-                       uint8_t* pixmap, rc_timing* timing) {
-  if (!s || !opt || !f || !pixmap) {
-    std::fprintf(stderr, "Error: rc_render_filtered: a null pointer\n");
-    return -1;
-  }
-  const auto t0 = HostClock::now();
-  if (filtered_refused("rc_render_filtered", opt, W, H, f) < 0) return -1;
-  if (timing) std::memset(timing, 0, sizeof *timing);
-  const rc_tuning tu = tune();
-  Entered e;
-  if (enter_host(opt, e)) return -1;
-  DevCtx* c = e.c;
-  const size_t bytes = (size_t)W * H * 3;
-  if (c->out.ensure(bytes)) return -1;
-  const long long own = c->lone_log.head;
-  if (enqueue_render(*c, s, W, H, 0, 1, H, opt, (uint8_t*)c->out.p, c->stream, true, nullptr,
-                     nullptr, f))
-    return -1;
-  return finish_host(*c, opt, pixmap, bytes, tu, {true, true, own}, timing, t0);
-}
-
-int rc_filter_image_device(const uint8_t* d_src, int W, int H, int s, const rc_filter* f,
-                           uint8_t* d_dst, void* stream) {
-  if (!d_src || !d_dst || !f) {
-    std::fprintf(stderr, "Error: rc_filter_image_device: a null pointer\n");
-    return -1;
-  }
-  if (rc_filter_check(f, s)) return -1;
-  if (W <= 0 || H <= 0 || W > (1 << 28) / s || H > (1 << 28) / s) {
-    std::fprintf(stderr, "Error: rc_filter_image_device: %d x %d at factor %d: both sides must "
-                 "be 1 .. 2^28 / s\n", W, H, s);
-    return -1;
-  }
-  const uintptr_t a = (uintptr_t)d_src, b = (uintptr_t)d_dst;
-  const size_t nb = (size_t)W * H * 3, na = nb * (size_t)s * s;
-  if (a < b + nb && b < a + na) {
-    std::fprintf(stderr, "Error: rc_filter_image_device: the source and the destination "
-                 "overlap: every output pixel reads its neighbours' subsamples\n");
-    return -1;
-  }
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  DevCtx* c;
-  if (ctx_get(dev, &c)) return -1;
-  HIP_TRY(rc::launch_filter_down(d_src, W, H, s, f->taps, f->ntaps, d_dst,
-                                 stream ? (hipStream_t)stream : c->stream));
-  return 0;
 }
 
 // ------------------------------------------------------------ pipelined frames --

@@ -1,11 +1,14 @@
 // rc_runtime.h — internal host-runtime state of libraycast_hip.so shared by rc_api.hip (one
-// device: rc_render, frames in flight) and rc_shard.hip (row shards over several devices).
+// device: rc_render, frames in flight), rc_sampling.hip (the sampling features' entry points)
+// and rc_shard.hip (row shards over several devices).
 // Not part of the C-ABI (include/raycast_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 #include <mutex>
 
 #include "raycast_hip.h"
@@ -165,8 +168,13 @@ enum SpanOwner {
   kSpanAdaptive, kSpanRates, kSpanFilter, kSpanPattern, kSpanAccum, kSpanWindow, kSpanOwners
 };
 
+// The sampling features' frame records.  Each documents the events its rc_*_phase_ms reads out
+// of the event set it owns (DevCtx::span_ev), an accumulation pass through a window being an
+// accumulation call that records as one.
+//
 // The last list-refined frame of one feature on a device (adaptive supersampling, a pattern
-// frame with a threshold): what its stats getter reads.
+// frame with a threshold): what its stats getter reads.  Adaptive spans: [0] start, [2] one-ray
+// image, [3] list, [1] refinement.
 struct ListFrame {
   DevBuf count;                // 8-byte counter block (word 0: entries), zeroed on the frame's
                                // stream before the list is made
@@ -176,10 +184,40 @@ struct ListFrame {
   int rays = 0;                // rays per refined pixel
 };
 
+// Sparse sample patterns (rc_render_pattern*): the edge list of a frame with a threshold lives in
+// DevCtx::aa_list; the record keeps a counter block of its own so that rc_pattern_stats_get
+// outlives a later adaptive frame.  Without a threshold (threshold = 0) every pixel is refined
+// and neither the counter nor `done` is used.  Spans: [0] start, [1] end, and with a threshold
+// (ev_listed) [2] [3] as adaptive.
+struct PatternFrame : ListFrame {
+  int threshold = 0;
+  bool ev_listed = false;
+};
+
+// Rate-map supersampling (rc_render_rates*): the rate-4 list lives in DevCtx::aa_list; `list`
+// holds the rate-2 list (upwards from its start) and the rate-8 list (downwards from its end),
+// W*H entries; `count` is the counter block (five words, launch_rates_render), zeroed on the
+// frame's stream; `map` is rc_render_rates' device copy of the host map.  Spans: [0] start, [2]
+// the rate-1 pass, [1] the refinement.
+struct RateFrame {
+  DevBuf list, count, map;
+  hipEvent_t done = nullptr;   // behind the last rate-map frame's refinement
+  bool valid = false;          // a rate-map frame has been enqueued on this device
+};
+
+// A timed two-pass supersampled frame (enqueue_render_two_pass).  Spans: [0] start, `mid`
+// between the s*W x s*H image and its filter, [end] behind the filter.
+struct FilterFrame {
+  hipEvent_t mid = nullptr;
+  int end = 1;
+};
+
 // The last accumulation call of a device (rc_accum_pass_device: one pass; rc_render_accum: all
 // of its passes): what rc_accum_stats_get reads.  Pass k owns slot k of the counter block, two
 // words {pixels listed by the edge list, saturated pixels}, so no pass waits for the host; the
-// block is the call's own, so the counts outlive the other sampling features' frames.
+// block is the call's own, so the counts outlive the other sampling features' frames.  Spans:
+// [0] start and [1] end of the call, [ev_first] the start of its last pass and, when that pass
+// ran over the edge list (ev_listed), [3] behind the list.
 struct AccumFrame {
   static constexpr int kSlots = 128;   // >= 4 dense chunks + 63 single-sample passes
   DevBuf count;                // kSlots * 8 bytes, zeroed on the call's stream before its passes
@@ -189,6 +227,8 @@ struct AccumFrame {
   int passes = 0;
   uint8_t samples[kSlots] = {};   // per pass: its sample count
   bool listed[kSlots] = {};       // per pass: it ran over the edge list (threshold > 0)
+  int ev_first = 0;
+  bool ev_listed = false;
 };
 
 struct DevCtx {
@@ -202,9 +242,8 @@ struct DevCtx {
   hipStream_t stream = nullptr;
   // event sets: [0] start, then per phase ends (fast: [1] = render; parity: [1] phase A,
   // [2] compaction, [3] resolver, [4] phase C; adaptive supersampling: [2] the one-ray image,
-  // [3] the edge list, [1] the refinement; rate maps: [2] the rate-1 pass, [1] the
-  // refinement; sample patterns: [1] the frame, with a threshold [2] [3] as adaptive
-  // supersampling).  Set 0 serves plain calls; inside an
+  // [3] the edge list, [1] the refinement; the other sampling features: at their records
+  // above).  Set 0 serves plain calls; inside an
   // rc_profile_begin/end window every call takes the next set of the pool.
   static constexpr int kEvSets = 64;
   hipEvent_t ev[kEvSets][5] = {};
@@ -215,38 +254,18 @@ struct DevCtx {
   // record is `aa`
   DevBuf aa_list;
   ListFrame aa;
-  // rate-map supersampling (rc_render_rates*): the rate-4 list lives in aa_list; rate_list holds
-  // the rate-2 list (upwards from its start) and the rate-8 list (downwards from its end), W*H
-  // entries; rate_count is the counter block (five words, launch_rates_render), zeroed on the
-  // frame's stream; rate_map is rc_render_rates' device copy of the host map
-  DevBuf rate_list, rate_count, rate_map;
-  hipEvent_t rate_done = nullptr;    // behind the last rate-map frame's refinement
-  bool rate_valid = false;           // a rate-map frame has been enqueued on this device
-  // sparse sample patterns (rc_render_pattern*): the edge list of a frame with a threshold lives
-  // in aa_list; its record `pat` keeps a counter block of its own so that rc_pattern_stats_get
-  // outlives a later adaptive frame.  Without a threshold (pat_t = 0) every pixel is refined and
-  // neither the counter nor pat.done is used.
-  ListFrame pat;
-  int pat_t = 0;
+  RateFrame rates;     // rate-map supersampling
+  PatternFrame pat;    // sparse sample patterns
+  FilterFrame filt;    // two-pass supersampling's timed frames
   // progressive supersampling: rc_render_accum's accumulator (rc_accum_pass_device's is the
   // caller's); a masked pass's edge list lives in aa_list; `acc` is the last call's record
   DevBuf accum_px;
   AccumFrame acc;
   // The event set whose spans each sampling feature's rc_*_phase_ms may still read, null once
-  // another frame has recorded that set anew (claim_event_set).  adaptive: [0] start, [2]
-  // one-ray image, [3] list, [1] refinement; rates: [0] start, [2] the rate-1 pass, [1] the
-  // refinement; filter (a timed two-pass frame): [0] start, filt_mid between the s*W x s*H image
-  // and its filter, [filt_end] behind the filter; pattern: [0] start, [1] end, and with a
-  // threshold (pat_ev_listed) [2] [3] as adaptive; accumulation: [0] start and [1] end of the
-  // call, [acc_ev_first] the start of its last pass and, when that pass ran over the edge list
-  // (acc_ev_listed), [3] behind the list; window (rc_render_window*): [0] start, [1] end (an
-  // accumulation pass through a window is an accumulation call and records as one).
+  // another frame has recorded that set anew (claim_event_set).  Which events of the set a
+  // feature reads is documented at its record above; window (rc_render_window*): [0] start,
+  // [1] end.
   hipEvent_t* span_ev[kSpanOwners] = {};
-  hipEvent_t filt_mid = nullptr;
-  int filt_end = 1;
-  bool pat_ev_listed = false;
-  int acc_ev_first = 0;
-  bool acc_ev_listed = false;
   uint8_t* stage[2] = {nullptr, nullptr};   // pinned bounce buffers of copy_to_host
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   FrameBufs fb;        // scene, counter and parity workspace of the plain path
@@ -324,6 +343,84 @@ int ssaa_threshold(const rc_options* opt, const char* who);
 int check_spin_error(FrameBufs& b, const rc_options* opt);
 void fill_device_timing(DevCtx& c, const rc_options* opt, rc_timing* t,
                         const uint8_t* tail = nullptr);
+
+// ------------------------------------------- the frame scaffold (rc_api.hip) --
+// A device call's context with its lock held (one render at a time per device, DevCtx::mu).
+struct Entered {
+  DevCtx* c = nullptr;
+  std::unique_lock<std::mutex> lk;
+};
+constexpr int kCurrentDevice = -1;
+
+// Enter a call on `device` (made current) or on the current one (kCurrentDevice).  The lock
+// covers the workspace from its (re)allocation on: a concurrent caller's ensure() could
+// otherwise free the buffer another caller is rendering into.  render: an earlier frame of this
+// workspace whose hand-off failed (rc_render_device on another stream) is reported by the next
+// render call, before its own frame is enqueued (once: the report consumes the counts).
+int enter(int device, bool render, Entered& e);
+// a host-pixmap render entry: on opt->device
+int enter_host(const rc_options* opt, Entered& e);
+// ms[i] = the span marks[i] -> marks[i + 1], once the last mark has completed
+int read_spans(std::initializer_list<hipEvent_t> marks, double* ms);
+// the listed pixels of f's frame, from its counter block once its refinement has run
+int list_frame_refined(const ListFrame& f, int64_t* refined);
+
+// The pending phase C (Pipe::cdefer) of the last submitted frame: on its lane's phase C
+// stream, or with `whole` on the device stream over every CU — the window's last frame, whose
+// phase C otherwise ran alone on the pixel partition after the last resolver (0.8 ms of a
+// 20-frame window's drain at quadric 4096^2 against ~0.47 ms on every CU).
+int flush_phase_c(DevCtx& c, bool whole);
+
+// The workspace bracket of a frame on `stream` through the device's one-frame workspace c.fb:
+// after the previous frame that used it, whatever its stream.  prepare() is what the frame
+// allocates before it waits for the workspace (a failure there leaves the stream untouched),
+// body() enqueues the frame.
+template <class Prepare, class Body>
+int ws_frame(DevCtx& c, hipStream_t stream, Prepare prepare, Body body) {
+  // a frame in flight's held-back phase C goes out first, so that a device synchronisation
+  // after this call completes it (rc_frames_wait stays the frames' completion point)
+  if (flush_phase_c(c, false) || prepare()) return -1;
+  if (c.ws_valid && c.ws_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, c.ws_ev, 0));
+  const int rc = body();
+  // recorded even after a failed enqueue: whatever was enqueued stays ordered
+  HIP_TRY(hipEventRecord(c.ws_ev, stream));
+  c.ws_stream = stream;
+  c.ws_valid = true;
+  return rc;
+}
+
+// The event set of the frame being enqueued: set 0, or inside an rc_profile_begin/end window
+// the next set of the pool.  The ownership rule of the sets' spans (DevCtx::span_ev) is here and
+// nowhere else: a frame that records the set anew (`records`) takes it from every feature that
+// still points at it, so no rc_*_phase_ms reads another frame's spans; `owner` (or kSpanOwners
+// for none) loses its own spans whatever set they were in, until the frame's enqueue has
+// succeeded and stores the set in span_ev[owner].  Under profiling consecutive frames record
+// different sets, so several owners can stay valid at once.
+hipEvent_t* claim_event_set(DevCtx& c, int owner, bool parity, bool records);
+
+constexpr long long kNoLog = -1;   // `own` of a frame that logs no hand-off entry
+
+// The tail of a device-resident call: without a timing record it returns with its frame
+// enqueued; with one it waits for the frame.  own (or kNoLog): the frame's entry in lone_log,
+// for the calls whose frame may be a parity frame.
+int finish_device(DevCtx& c, const rc_options* opt, hipStream_t st, rc_timing* timing,
+                  long long own);
+
+using HostClock = std::chrono::steady_clock;
+
+// The tail of a host-pixmap call whose frame is enqueued on c.stream with its image in c.out:
+// the copy into the caller's pixmap, the wait, the timing record (t0: the call's entry).
+// What the entry points do differently is explicit: tail_counts (the frame's counts through
+// pin_tail rather than two copies after the frame), prefault (the pixmap is faulted in while the
+// GPU renders), own (or kNoLog: the frame's hand-off entry is verified).
+struct HostTail {
+  bool tail_counts, prefault;
+  long long own;
+};
+int finish_host(DevCtx& c, const rc_options* opt, uint8_t* pixmap, size_t bytes,
+                const rc_tuning& tu, const HostTail& how, rc_timing* timing,
+                HostClock::time_point t0);
+
 // rc_shard.hip: rc_render's multi-GPU path (a cached in-process group over devices
 // first..first+n-1, or n ranks sharing device `first` with device copies between them when
 // `share`); *d_image = the root's de-interleaved image.  The caller holds no lock.

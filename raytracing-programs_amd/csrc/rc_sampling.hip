@@ -1,0 +1,1051 @@
+// rc_sampling.hip — the sampling features of libraycast_hip.so's C-ABI (include/raycast_hip.h):
+// rate maps, reconstruction filters, sparse sample patterns, progressive accumulation and windows
+// of a virtual image, with adaptive supersampling's getters.  Host code only: the kernels are
+// rc_kernels.hip's and rc_filter.hip's, the device context and the frame scaffold (enter,
+// ws_frame, claim_event_set, finish_device, finish_host) are rc_api.hip's, through rc_runtime.h.
+//
+// A feature is one Refusal description, one enqueue body between SampleFrame::begin and ::end,
+// one record in DevCtx and two entry points that are their null checks, `refused` and one call
+// of device_entry or host_entry.  Nothing here reads a build-time
+// diagnostic switch, so one object serves every variant of the library.
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "raycast_hip.h"
+#include "rc_kernels.h"
+#include "rc_runtime.h"
+#include "rc_scene.h"
+
+using namespace rcrt;
+
+// ---------------------------------------------------------------------- refusals --
+// What a feature's entry points refuse from their arguments alone, before the first HIP call.
+// The clauses are tested in the order of the fields; a null message switches its clause off.
+// Every message is a whole format string that starts with the entry point's name.
+struct Refusal {
+  const char* adaptive;   // (who, opt->ssaa): no adaptive threshold in the options
+  int factor_min;         // 1: the options' factor must be off (the feature carries its own grid);
+  const char* factor;     // 2: it must be 2, 4 or 8; (who, opt->ssaa)
+  const char* mode;       // (who): fast and cuda mode only
+  const char* shards;     // (who, opt->num_gpus): one GPU only
+  // check(ss): the feature's own check of its argument, which prints its own message
+  // then: the threshold in 0..255
+  const char* side;       // (who, W, H, g): both sides in 1 .. 2^28 / g
+  // then: with `masked`, W * H below 2^32; then supported(ss): the kernels' grid limits
+};
+
+static int no_check(int) { return 0; }
+
+// a refusal's message on stderr; -1
+__attribute__((format(printf, 1, 2))) static int say(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  std::vfprintf(stderr, fmt, ap);
+  va_end(ap);
+  return -1;
+}
+
+// an environment reader's warning on stderr; 0: the variable is ignored
+__attribute__((format(printf, 1, 2))) static int warn(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  std::vfprintf(stderr, fmt, ap);
+  va_end(ap);
+  return 0;
+}
+
+// g: the lattice the side limit is taken at (0: the options' factor); threshold and masked: of
+// the features that take an edge threshold as an argument (0 and false elsewhere).
+template <class Check, class Supported>
+static int refused(const Refusal& d, const char* who, const rc_options* opt, int W, int H, int g,
+                   int threshold, bool masked, Check check, Supported supported) {
+  const int ss = ssaa_factor(opt, who);
+  if (ss < 0) return -1;   // ssaa_decode has said why (a threshold without a factor included)
+  if (d.adaptive && RC_SSAA_THRESHOLD(opt->ssaa) > 0) return say(d.adaptive, who, opt->ssaa);
+  if (d.factor && (d.factor_min == 1 ? ss > 1 : ss < d.factor_min))
+    return say(d.factor, who, opt->ssaa);
+  if (d.mode && opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) return say(d.mode, who);
+  if (opt->num_gpus > 1) return say(d.shards, who, opt->num_gpus);
+  if (check(ss)) return -1;
+  if (threshold < 0 || threshold > 255)
+    return say("Error: %s: threshold %d is not 0..255\n", who, threshold);
+  if (g == 0) g = ss;
+  if (d.side && (W <= 0 || H <= 0 || W > (1 << 28) / g || H > (1 << 28) / g))
+    return say(d.side, who, W, H, g);
+  if (masked && (unsigned long long)W * (unsigned long long)H >= (1ull << 32))
+    return say("Error: %s: %d x %d with a threshold is too large (32-bit pixel indices)\n", who, W,
+               H);
+  return supported(ss) ? -1 : 0;
+}
+
+static const char kLatticeSide[] =
+    "Error: %s: %d x %d on a lattice of %d: both sides must be 1 .. 2^28 / g\n";
+
+static const Refusal kFilteredRefusal = {
+    "Error: %s: an adaptive threshold (ssaa %d): a refined pixel's filter footprint would reach "
+    "its unrefined neighbours' subsamples; use a plain factor\n",
+    2, "Error: %s: ssaa %d: a filtered frame needs a factor of 2, 4 or 8\n",
+    nullptr,
+    "Error: %s: num_gpus %d: the row shards do not supersample\n",
+    "Error: %s: %d x %d at factor %d: both sides must be 1 .. 2^28 / s\n"};
+
+static const Refusal kPatternRefusal = {
+    nullptr,
+    1, "Error: %s: ssaa %d in the options: the pattern carries the grid, leave ssaa at 0 or 1\n",
+    "Error: %s: a sample pattern is for fast and cuda mode: every pixel of a parity image depends "
+    "on the scan-order carry of the whole image, so it cannot be shot sparsely; use plain ssaa\n",
+    "Error: %s: num_gpus %d: the row shards take no sample pattern\n",
+    kLatticeSide};
+
+static const Refusal kAccumRefusal = {
+    nullptr,
+    1, "Error: %s: ssaa %d in the options: the sample sequence carries the grid, leave ssaa at 0 "
+    "or 1\n",
+    "Error: %s: accumulated samples are for fast and cuda mode: every pixel of a parity image "
+    "depends on the scan-order carry of the whole image, so it cannot be shot sparsely; use plain "
+    "ssaa\n",
+    "Error: %s: num_gpus %d: the row shards take no accumulator\n",
+    kLatticeSide};
+
+static const Refusal kWindowRefusal = {
+    "Error: %s: ssaa %d carries an adaptive threshold: adaptive refinement of a window is an "
+    "accumulation pass with a threshold (rc_accum_pass_window_device)\n",
+    0, nullptr,
+    "Error: %s: windows are for fast and cuda mode: a window of a parity image depends on the "
+    "scan-order carry of every pixel before it\n",
+    "Error: %s: num_gpus %d: the row shards take no window\n",
+    nullptr};   // rc_window_check tests the sizes
+
+static const Refusal kRatesRefusal = {
+    nullptr,
+    1, "Error: %s: ssaa %d in the options: the rate map carries the factor per pixel, leave ssaa "
+    "at 0 or 1\n",
+    "Error: %s: a rate map is for fast and cuda mode: every pixel of a parity image depends on "
+    "the scan-order carry of the whole image, so it cannot be shot sparsely\n",
+    "Error: %s: num_gpus %d: the row shards take no rate map\n",
+    nullptr};   // rc::rates_supported tests the sizes
+
+// One argument order (who, opt, W, H, the feature's own) and one return: -1 refused, 0 passed.
+// A caller that needs the factor afterwards takes it from ssaa_factor.
+static int filtered_refused(const char* who, const rc_options* opt, int W, int H,
+                            const rc_filter* f) {
+  return refused(kFilteredRefusal, who, opt, W, H, 0, 0, false,
+                 [&](int ss) { return rc_filter_check(f, ss); }, no_check);
+}
+
+static int pattern_refused(const char* who, const rc_options* opt, int W, int H,
+                           const rc_pattern* pat, int threshold) {
+  const bool masked = threshold > 0;
+  return refused(kPatternRefusal, who, opt, W, H, pat->grid, threshold, masked,
+                 [&](int) { return rc_pattern_check(pat); }, [&](int) {
+                   if (rc::pattern_supported(W, H, pat->grid, pat->nsamples, masked)) return 0;
+                   return say("Error: %s: %d x %d is too large for %d samples a pixel (at most "
+                              "65535 rows of tiles)\n", who, W, H, pat->nsamples);
+                 });
+}
+
+// whatever the passes: `masked`: the call has a pass over the edge list, `dense`: one over every
+// pixel
+static int accum_refused(const char* who, const rc_options* opt, int W, int H,
+                         const rc_sample_seq* seq, int threshold, bool dense, bool masked) {
+  return refused(kAccumRefusal, who, opt, W, H, seq->grid, threshold, masked,
+                 [&](int) { return rc_sample_seq_check(seq); }, [&](int) {
+                   if ((!dense || rc::accum_supported(W, H, seq->grid, false)) &&
+                       (!masked || rc::accum_supported(W, H, seq->grid, true)))
+                     return 0;
+                   return say("Error: %s: %d x %d is too large for the kernels' grids (at most "
+                              "65535 rows of tiles)\n", who, W, H);
+                 });
+}
+
+static int window_refused(const char* who, const rc_options* opt, int W, int H,
+                          const rc_window* win) {
+  return refused(kWindowRefusal, who, opt, W, H, 0, 0, false,
+                 [&](int ss) { return rc_window_check(win, W, H, ss); }, no_check);
+}
+
+static int rates_refused(const char* who, const rc_options* opt, int W, int H) {
+  return refused(kRatesRefusal, who, opt, W, H, 0, 0, false, [&](int) {
+    if (rc::rates_supported(W, H)) return 0;
+    return say("Error: %s: %d x %d is too large for a rate map (32-bit pixel indices at 8 "
+               "subsamples a side, at most 65535 rows of tiles)\n", who, W, H);
+  }, no_check);
+}
+
+// ------------------------------------------- sample lattices: patterns and sequences --
+// (x, y) pairs, x to the right and y downwards (include/raycast_hip.h, rc_pattern)
+static const struct {
+  const char* name;
+  int grid, nsamples;
+  uint8_t xy[RC_PATTERN_MAX_SAMPLES][2];
+} kPatterns[] = {
+    {"diag2", 2, 2, {{0, 0}, {1, 1}}},
+    {"rgss4", 4, 4, {{1, 0}, {3, 1}, {0, 2}, {2, 3}}},
+    {"checker8", 4, 8, {{0, 0}, {2, 0}, {1, 1}, {3, 1}, {0, 2}, {2, 2}, {1, 3}, {3, 3}}},
+    {"queens8", 8, 8, {{3, 0}, {6, 1}, {2, 2}, {7, 3}, {1, 4}, {4, 5}, {0, 6}, {5, 7}}},
+};
+
+// The built-in pattern `name` into an rc_pattern or an rc_sample_seq (the same four fields);
+// -1 and `out` as it was: no such pattern.
+template <class Lattice>
+static int builtin_pattern(const char* name, Lattice* out) {
+  for (const auto& p : kPatterns) {
+    if (std::strcmp(name, p.name)) continue;
+    std::memset(out, 0, sizeof *out);
+    out->grid = p.grid;
+    out->nsamples = p.nsamples;
+    for (int k = 0; k < p.nsamples; ++k) {
+      out->x[k] = p.xy[k][0];
+      out->y[k] = p.xy[k][1];
+    }
+    return 0;
+  }
+  return -1;
+}
+
+// The rules an rc_pattern and an rc_sample_seq share: the lattice g is 2, 4 or 8, the count n
+// passes the type's own rule (count_refused(g, n) says why not), every point lies on the lattice
+// and no two coincide.
+template <class Rule>
+static int lattice_check(const char* who, int g, int n, const uint8_t* x, const uint8_t* y,
+                         Rule count_refused) {
+  if (g != 2 && g != 4 && g != 8) return say("Error: %s: grid %d is not 2, 4 or 8\n", who, g);
+  if (count_refused(g, n)) return -1;
+  for (int k = 0; k < n; ++k) {
+    if (x[k] >= g || y[k] >= g)
+      return say("Error: %s: sample %d at (%d, %d) is off the %d x %d lattice\n", who, k, x[k],
+                 y[k], g, g);
+    for (int j = 0; j < k; ++j)
+      if (x[j] == x[k] && y[j] == y[k])
+        return say("Error: %s: samples %d and %d are both at (%d, %d)\n", who, j, k, x[k], y[k]);
+  }
+  return 0;
+}
+
+extern "C" {
+
+// ------------------------ getters: adaptive supersampling, rate maps, two-pass frames --
+int rc_adaptive_stats_get(rc_adaptive_stats* out) {
+  Entered e;
+  if (!out || enter(kCurrentDevice, false, e) || !e.c->aa.valid) return -1;
+  const ListFrame& f = e.c->aa;
+  if (list_frame_refined(f, &out->refined_pixels)) return -1;
+  out->rays = (int64_t)f.pixels + (int64_t)f.rays * out->refined_pixels;
+  return 0;
+}
+
+int rc_adaptive_phase_ms(double ms[3]) {
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanAdaptive];
+  return ev ? read_spans({ev[0], ev[2], ev[3], ev[1]}, ms) : -1;
+}
+
+int rc_rate_stats_get(rc_rate_stats* out) {
+  Entered e;
+  if (!out || enter(kCurrentDevice, false, e) || !e.c->rates.valid) return -1;
+  HIP_TRY(hipEventSynchronize(e.c->rates.done));   // the frame's stream, up to its refinement
+  unsigned n[5] = {0, 0, 0, 0, 0};   // launch_rates_render's counter block
+  HIP_TRY(hipMemcpy(n, e.c->rates.count.p, sizeof n, hipMemcpyDeviceToHost));
+  out->pixels[0] = (int64_t)n[3];
+  out->pixels[1] = (int64_t)n[0];
+  out->pixels[2] = (int64_t)n[1];
+  out->pixels[3] = (int64_t)n[2];
+  out->invalid = (int64_t)n[4];
+  out->rays = out->pixels[0] + 4 * out->pixels[1] + 16 * out->pixels[2] + 64 * out->pixels[3];
+  return 0;
+}
+
+int rc_rate_phase_ms(double ms[2]) {
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanRates];
+  return ev ? read_spans({ev[0], ev[2], ev[1]}, ms) : -1;
+}
+
+int rc_filter_phase_ms(double ms[2]) {
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanFilter];
+  return ev ? read_spans({ev[0], e.c->filt.mid, ev[e.c->filt.end]}, ms) : -1;
+}
+
+// ---------------------------------------------------------- reconstruction filters --
+static bool filter_factor(int s) { return s == 2 || s == 4 || s == 8; }
+
+int rc_filter_box(int s, rc_filter* out) {
+  if (!out || !filter_factor(s)) return -1;
+  std::memset(out, 0, sizeof *out);
+  out->ntaps = s;
+  for (int i = 0; i < s; ++i) out->taps[i] = 1;
+  return 0;
+}
+
+int rc_filter_tent(int s, rc_filter* out) {
+  if (!out || !filter_factor(s)) return -1;
+  std::memset(out, 0, sizeof *out);
+  out->ntaps = 2 * s;
+  for (int i = 0; i < s; ++i) out->taps[i] = out->taps[2 * s - 1 - i] = (int16_t)(2 * i + 1);
+  return 0;
+}
+
+// The rules of include/raycast_hip.h (rc_filter).  The bound on the absolute sum is what keeps
+// the kernel's arithmetic in int32: a horizontal sum is at most 2048 * 255 < 2^19 in magnitude,
+// the full sum at most 2048^2 * 255, and with the rounding term S*S/2 <= 2^21 that stays below
+// 2^31, so the separable evaluation is exact.
+int rc_filter_check(const rc_filter* f, int s) {
+  const char* who = "rc_filter_check";
+  if (!f) return say("Error: %s: a null filter\n", who);
+  if (!filter_factor(s)) return say("Error: %s: factor %d is not 2, 4 or 8\n", who, s);
+  const int n = f->ntaps;
+  if (n > RC_FILTER_MAX_TAPS)
+    return say("Error: %s: %d taps, at most %d\n", who, n, RC_FILTER_MAX_TAPS);
+  if (n < s || ((n - s) & 1))
+    return say("Error: %s: %d taps at factor %d: the count is s + 2h with a halo h >= 0, so it is "
+               "at least s and differs from s by an even number\n", who, n, s);
+  if ((n - s) / 2 > s)
+    return say("Error: %s: %d taps at factor %d: the halo %d is wider than one output pixel "
+               "(h <= s, at most %d taps)\n", who, n, s, (n - s) / 2, 3 * s);
+  long long sum = 0, mag = 0;
+  for (int i = 0; i < n; ++i) {
+    sum += f->taps[i];
+    mag += f->taps[i] < 0 ? -(long long)f->taps[i] : f->taps[i];
+  }
+  if (sum <= 0)
+    return say("Error: %s: the taps sum to %lld, the sum must be positive\n", who, sum);
+  if (mag > 2048)
+    return say("Error: %s: the taps' absolute values sum to %lld, at most 2048 (the int32 "
+               "bound)\n", who, mag);
+  return 0;
+}
+
+int rc_filter_env(const rc_options* opt, rc_filter* out) {
+  const char* v = std::getenv("RAYCAST_FILTER");
+  if (!v || !opt || !out) return 0;
+  bool tent = false;
+  if (!std::strcmp(v, "tent")) tent = true;
+  else if (std::strcmp(v, "box"))
+    std::fprintf(stderr, "Warning: RAYCAST_FILTER '%s' is not box or tent, using box\n", v);
+  const int s = RC_SSAA_FACTOR(opt->ssaa);
+  if (!filter_factor(s))
+    return warn("Warning: RAYCAST_FILTER '%s' needs RAYCAST_SSAA 2, 4 or 8, ignored\n", v);
+  if (RC_SSAA_THRESHOLD(opt->ssaa) > 0)
+    return warn("Warning: RAYCAST_FILTER '%s' does not combine with RAYCAST_SSAA_ADAPTIVE (a "
+                "refined pixel's footprint would reach its unrefined neighbours), ignored\n", v);
+  return tent && rc_filter_tent(s, out) == 0 ? 1 : 0;
+}
+
+// ------------------------------------------------------------ sparse sample patterns --
+int rc_pattern_stats_get(rc_pattern_stats* out) {
+  Entered e;
+  if (!out || enter(kCurrentDevice, false, e) || !e.c->pat.valid) return -1;
+  const PatternFrame& f = e.c->pat;
+  const bool listed = f.threshold > 0;
+  int64_t refined = (int64_t)f.pixels;   // without a threshold: known without the device
+  if (listed && list_frame_refined(f, &refined)) return -1;
+  out->refined_pixels = refined;
+  out->rays = (listed ? (int64_t)f.pixels : 0) + (int64_t)f.rays * refined;
+  return 0;
+}
+
+int rc_pattern_phase_ms(double ms[3]) {
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanPattern];
+  if (!ev) return -1;
+  if (e.c->pat.ev_listed) return read_spans({ev[0], ev[2], ev[3], ev[1]}, ms);
+  ms[1] = ms[2] = 0.0;
+  return read_spans({ev[0], ev[1]}, ms);
+}
+
+int rc_pattern_builtin(const char* name, rc_pattern* out) {
+  return name && out ? builtin_pattern(name, out) : -1;
+}
+
+int rc_pattern_check(const rc_pattern* p) {
+  const char* who = "rc_pattern_check";
+  if (!p) return say("Error: %s: a null pattern\n", who);
+  return lattice_check(who, p->grid, p->nsamples, p->x, p->y, [&](int g, int n) {
+    if (n != 2 && n != 4 && n != 8 && n != 16)
+      return say("Error: %s: %d samples, not 2, 4, 8 or 16\n", who, n);
+    if (n > g * g)
+      return say("Error: %s: %d samples on a %d x %d lattice of %d points\n", who, n, g, g, g * g);
+    return 0;
+  });
+}
+
+int rc_pattern_env(const rc_options* opt, rc_pattern* out, int* threshold) {
+  const char* v = std::getenv("RAYCAST_PATTERN");
+  if (!v || !opt || !out || !threshold) return 0;
+  const char* colon = std::strchr(v, ':');
+  const std::string name = colon ? std::string(v, colon) : std::string(v);
+  rc_pattern pat;
+  if (rc_pattern_builtin(name.c_str(), &pat))
+    return warn("Warning: RAYCAST_PATTERN '%s': '%s' is not diag2, rgss4, checker8 or queens8, "
+                "ignored\n", v, name.c_str());
+  long t = 0;
+  if (colon) {
+    char* end = nullptr;
+    t = std::strtol(colon + 1, &end, 10);
+    if (colon[1] < '0' || colon[1] > '9' || *end != '\0' || t > 255)
+      return warn("Warning: RAYCAST_PATTERN '%s': '%s' is not a threshold 0..255, ignored\n", v,
+                  colon + 1);
+  }
+  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA)
+    return warn("Warning: RAYCAST_PATTERN '%s' is for fast and cuda mode (a parity image cannot be "
+                "shot sparsely), ignored\n", v);
+  if (RC_SSAA_FACTOR(opt->ssaa) > 1 || RC_SSAA_THRESHOLD(opt->ssaa) > 0)
+    return warn("Warning: RAYCAST_PATTERN '%s' does not combine with RAYCAST_SSAA %d (the pattern "
+                "carries its own grid), ignored\n", v, RC_SSAA_FACTOR(opt->ssaa));
+  *out = pat;
+  *threshold = (int)t;
+  return 1;
+}
+
+// ------------------------------------------------------- progressive supersampling --
+int rc_accum_stats_get(rc_accum_stats* out) {
+  Entered e;
+  if (!out || enter(kCurrentDevice, false, e) || !e.c->acc.valid) return -1;
+  const AccumFrame& f = e.c->acc;
+  HIP_TRY(hipEventSynchronize(f.done));   // the call's stream, up to its last pass
+  unsigned n[AccumFrame::kSlots][2] = {};   // per pass {listed, saturated}
+  HIP_TRY(hipMemcpy(n, f.count.p, (size_t)f.passes * sizeof n[0], hipMemcpyDeviceToHost));
+  out->passes = f.passes;
+  out->rays = 0;
+  for (int k = 0; k < f.passes; ++k) {
+    out->active_pixels = f.listed[k] ? (int64_t)n[k][0] : (int64_t)f.pixels;
+    out->saturated = (int64_t)n[k][1];
+    out->rays += (out->active_pixels - out->saturated) * f.samples[k];
+  }
+  return 0;
+}
+
+int rc_accum_phase_ms(double ms[2]) {
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanAccum];
+  if (!ev) return -1;
+  hipEvent_t first = ev[e.c->acc.ev_first];
+  if (e.c->acc.ev_listed) return read_spans({first, ev[3], ev[1]}, ms);
+  ms[0] = 0.0;
+  return read_spans({first, ev[1]}, ms + 1);
+}
+
+// hier<g>: point k is the bit-reversal r of k over 2 * lg bits; x takes r's even bits, y its odd
+// bits (include/raycast_hip.h, rc_sample_seq)
+static void hier_seq(int lg, rc_sample_seq* out) {
+  out->grid = 1 << lg;
+  out->nsamples = 1 << (2 * lg);
+  for (int k = 0; k < out->nsamples; ++k) {
+    int r = 0;
+    for (int b = 0; b < 2 * lg; ++b) r |= ((k >> b) & 1) << (2 * lg - 1 - b);
+    int x = 0, y = 0;
+    for (int i = 0; i < lg; ++i) {
+      x |= ((r >> (2 * i)) & 1) << i;
+      y |= ((r >> (2 * i + 1)) & 1) << i;
+    }
+    out->x[k] = (uint8_t)x;
+    out->y[k] = (uint8_t)y;
+  }
+}
+
+int rc_sample_seq_builtin(const char* name, rc_sample_seq* out) {
+  if (!name || !out) return -1;
+  std::memset(out, 0, sizeof *out);
+  for (int lg = 1; lg <= 3; ++lg) {
+    const char hier[] = {'h', 'i', 'e', 'r', (char)('0' + (1 << lg)), '\0'};
+    if (std::strcmp(name, hier)) continue;
+    hier_seq(lg, out);
+    return 0;
+  }
+  return builtin_pattern(name, out);
+}
+
+int rc_sample_seq_check(const rc_sample_seq* s) {
+  const char* who = "rc_sample_seq_check";
+  if (!s) return say("Error: %s: a null sequence\n", who);
+  return lattice_check(who, s->grid, s->nsamples, s->x, s->y, [&](int g, int n) {
+    const int most = g * g < RC_ACCUM_MAX_SAMPLES ? g * g : RC_ACCUM_MAX_SAMPLES;
+    if (n >= 1 && n <= most) return 0;
+    return say("Error: %s: %d samples, not 1..%d (a %d x %d lattice, at most %d)\n", who, n, most,
+               g, g, RC_ACCUM_MAX_SAMPLES);
+  });
+}
+
+// ------------------------------------------------------- windows of a virtual image --
+int rc_window_check(const rc_window* w, int W, int H, int s) {
+  const char* who = "rc_window_check";
+  if (!w) return say("Error: %s: a null window\n", who);
+  if (s == 0) s = 1;   // as rc_options.ssaa
+  if (s != 1 && s != 2 && s != 4 && s != 8)
+    return say("Error: %s: factor %d is not 0, 1, 2, 4 or 8\n", who, s);
+  if (w->full_w < 1 || w->full_h < 1 || W < 1 || H < 1)
+    return say("Error: %s: a %d x %d window of a %d x %d image: every size must be at least 1\n",
+               who, W, H, w->full_w, w->full_h);
+  if (w->x0 < 0 || w->y0 < 0)
+    return say("Error: %s: origin (%d, %d): a window starts inside the image, at 0 or above\n",
+               who, w->x0, w->y0);
+  // W > full_w - x0 rather than x0 + W > full_w: no sum that could overflow
+  if (w->x0 > w->full_w || W > w->full_w - w->x0 || w->y0 > w->full_h || H > w->full_h - w->y0)
+    return say("Error: %s: a %d x %d window at (%d, %d) reaches outside the %d x %d image\n", who,
+               W, H, w->x0, w->y0, w->full_w, w->full_h);
+  if (w->full_w > 0x7fffffff / s || w->full_h > 0x7fffffff / s)
+    return say("Error: %s: %d times %d x %d: the subsample image's sides must stay within 2^31 - "
+               "1\n", who, s, w->full_w, w->full_h);
+  if (!rc::window_supported(rc::Window{w->full_w, w->full_h, w->x0, w->y0}, W, H, s))
+    return say("Error: %s: a %d x %d window at factor %d is too large for the kernel's grid (at "
+               "most 65535 rows of 16-subsample tiles, 2^31 - 1 tiles)\n", who, W, H, s);
+  return 0;
+}
+
+// one decimal field of RAYCAST_WINDOW: digits only, within int; *p moves behind it
+static bool window_field(const char** p, int* out) {
+  const char* q = *p;
+  long long v = 0;
+  if (*q < '0' || *q > '9') return false;
+  for (; *q >= '0' && *q <= '9'; ++q) {
+    v = v * 10 + (*q - '0');
+    if (v > 0x7fffffffll) return false;
+  }
+  *p = q;
+  *out = (int)v;
+  return true;
+}
+
+int rc_window_env(const rc_options* opt, int W, int H, rc_window* out) {
+  const char* v = std::getenv("RAYCAST_WINDOW");
+  if (!v || !opt || !out) return 0;
+  rc_window w;
+  const char* p = v;
+  int f[4] = {0, 0, 0, 0};
+  bool ok = window_field(&p, &f[0]);
+  const char seps[3] = {'x', '+', '+'};
+  for (int k = 0; ok && k < 3; ++k) ok = *p++ == seps[k] && window_field(&p, &f[k + 1]);
+  if (!ok || *p != '\0')
+    return warn("Warning: RAYCAST_WINDOW '%s' is not FWxFH+X0+Y0 (four decimal numbers), "
+                "ignored\n", v);
+  w.full_w = f[0], w.full_h = f[1], w.x0 = f[2], w.y0 = f[3];
+  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA)
+    return warn("Warning: RAYCAST_WINDOW '%s' is for fast and cuda mode (a window of a parity "
+                "image depends on the scan-order carry of every pixel before it), ignored\n", v);
+  if (RC_SSAA_THRESHOLD(opt->ssaa) > 0)
+    return warn("Warning: RAYCAST_WINDOW '%s' does not combine with RAYCAST_SSAA_ADAPTIVE, "
+                "ignored\n", v);
+  const char* pat = std::getenv("RAYCAST_PATTERN");
+  if (pat && pat[0])
+    return warn("Warning: RAYCAST_WINDOW '%s' does not combine with RAYCAST_PATTERN, ignored\n",
+                v);
+  const char* filt = std::getenv("RAYCAST_FILTER");
+  if (filt && !std::strcmp(filt, "tent"))
+    return warn("Warning: RAYCAST_WINDOW '%s' does not combine with RAYCAST_FILTER=tent, "
+                "ignored\n", v);
+  if (opt->num_gpus > 1)
+    return warn("Warning: RAYCAST_WINDOW '%s' does not combine with RAYCAST_GPUS %d (the row "
+                "shards take no window), ignored\n", v, opt->num_gpus);
+  if (rc_window_check(&w, W, H, RC_SSAA_FACTOR(opt->ssaa)))
+    return warn("Warning: RAYCAST_WINDOW '%s' does not hold a %d x %d window, ignored\n", v, W, H);
+  *out = w;
+  return 1;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ enqueue bodies --
+// The first and the last lines of a sampling frame's body inside ws_frame.  begin: the scene, the
+// zero-normalize counter and the feature's own counters (bytes of *counters, 0: none) zeroed on
+// the stream, then the event set is claimed for `owner` and ev[0] recorded.  end: ev[1] recorded
+// and the set stored as the owner's.  What a feature records around ev[1] (RateFrame::done before
+// it, the pattern's and the accumulation's `done` behind it) and its record's flags stay in its
+// body, the flags behind end().
+struct SampleFrame {
+  DevCtx& c;
+  hipStream_t stream;
+  SpanOwner owner;
+  rc::LaunchScene ls;
+  unsigned long long* zc = nullptr;
+  hipEvent_t* ev = nullptr;
+
+  int begin(const rc_scene* s, const DevBuf* counters, size_t bytes) {
+    if (upload_scene(c.fb, stream, s, ls)) return -1;
+    zc = (unsigned long long*)c.fb.zcount.p;
+    HIP_TRY(hipMemsetAsync(zc, 0, sizeof(unsigned long long), stream));
+    if (bytes) HIP_TRY(hipMemsetAsync(counters->p, 0, bytes, stream));
+    ev = claim_event_set(c, owner, false, true);
+    HIP_TRY(hipEventRecord(ev[0], stream));
+    return 0;
+  }
+  int end() {
+    HIP_TRY(hipEventRecord(ev[1], stream));
+    c.span_ev[owner] = ev;
+    return 0;
+  }
+};
+
+// a record's `done` event, created on first use
+static int ensure_done(hipEvent_t& done) {
+  if (!done) HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+  return 0;
+}
+
+// One rate-map frame on `stream` through the device's one-frame workspace (the caller holds
+// c.mu and has passed rates_refused): the rate-1 pixels with the binning, then the three lists'
+// refinements, with no host wait in between.  The host does not know which lists are empty, so
+// all three are launched.
+static int enqueue_rates(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
+                         const uint8_t* d_rates, uint8_t* d_out, hipStream_t stream) {
+  RateFrame& r = c.rates;
+  auto prepare = [&]() -> int {
+    const size_t entries = (size_t)W * H;
+    if (c.aa_list.ensure(entries * sizeof(uint32_t)) ||
+        r.list.ensure(entries * sizeof(uint32_t)) || r.count.ensure(32)) {
+      std::fprintf(stderr, "Error: out of device memory for the rate lists (%d x %d)\n", W, H);
+      return -1;
+    }
+    return ensure_done(r.done);
+  };
+  return ws_frame(c, stream, prepare, [&]() -> int {
+    SampleFrame f{c, stream, kSpanRates};
+    if (f.begin(s, &r.count, 32)) return -1;
+    unsigned* cnt = (unsigned*)r.count.p;
+    uint32_t* list4 = (uint32_t*)c.aa_list.p;
+    uint32_t* list28 = (uint32_t*)r.list.p;
+    const int maxrec = opt->max_recursion;
+    const bool cuda = opt->mode == RC_MODE_CUDA;
+    // The lists follow the map's row-major order, so over a uniform region entry k is pixel
+    // k + const and a wave's static stride (workgroups * 4 waves * pixels per step) that is a
+    // multiple of W keeps the wave in one column of the image: the waves whose column crosses
+    // the expensive shapes finish last.  An odd number of workgroups makes the stride drift
+    // through the columns (measured: DESIGN.md section 12).  An explicit adaptive_blocks holds.
+    const int want = tune().adaptive_blocks;
+    auto blocks = [&](int ss) {
+      const int b = rc::aa_refine_blocks(W, H, ss, c.cus, want);
+      return want <= 0 && b > 2 && (b & 1) == 0 ? b - 1 : b;
+    };
+    HIP_TRY(rc::launch_rates_render(f.ls, W, H, maxrec, d_rates, d_out, list4, list28, cnt, f.zc,
+                                    stream, cuda));
+    HIP_TRY(hipEventRecord(f.ev[2], stream));
+    HIP_TRY(rc::launch_aa_refine(f.ls, W, H, 2, maxrec, list28, cnt, d_out, f.zc, blocks(2),
+                                 stream, cuda));
+    HIP_TRY(rc::launch_aa_refine(f.ls, W, H, 4, maxrec, list4, cnt + 1, d_out, f.zc, blocks(4),
+                                 stream, cuda));
+    HIP_TRY(rc::launch_rates_refine8(f.ls, W, H, maxrec, list28, cnt + 2, d_out, f.zc, blocks(8),
+                                     stream, cuda));
+    HIP_TRY(hipEventRecord(r.done, stream));
+    if (f.end()) return -1;
+    r.valid = true;
+    return 0;
+  });
+}
+
+// One pattern frame on `stream` through the device's one-frame workspace (the caller holds c.mu
+// and has passed pattern_refused).  at = 0: the dense kernel.  at > 0: the one-ray image by the
+// plain kernel, the adaptive path's edge list (launch_aa_mark into aa_list), then the pattern
+// kernel over the list: three launches with no host wait in between.
+static int enqueue_pattern(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
+                           const rc_pattern* pat, int at, uint8_t* d_out, hipStream_t stream) {
+  PatternFrame& p = c.pat;
+  auto prepare = [&]() -> int {
+    if (at == 0) return 0;
+    if (p.count.ensure(8) || c.aa_list.ensure((size_t)W * H * sizeof(uint32_t))) {
+      std::fprintf(stderr, "Error: out of device memory for the edge list (%d x %d)\n", W, H);
+      return -1;
+    }
+    return ensure_done(p.done);
+  };
+  return ws_frame(c, stream, prepare, [&]() -> int {
+    SampleFrame f{c, stream, kSpanPattern};
+    if (f.begin(s, &p.count, at > 0 ? 8 : 0)) return -1;
+    unsigned* cnt = (unsigned*)p.count.p;
+    uint32_t* list = (uint32_t*)c.aa_list.p;
+    const int maxrec = opt->max_recursion, g = pat->grid, n = pat->nsamples;
+    const bool cuda = opt->mode == RC_MODE_CUDA;
+    if (at == 0) {
+      HIP_TRY(rc::launch_pattern(f.ls, W, H, g, n, pat->x, pat->y, maxrec, d_out, f.zc, stream,
+                                 cuda));
+    } else {
+      HIP_TRY(rc::launch_render(f.ls, W, H, 0, 1, H, maxrec, d_out, f.zc, stream, cuda));
+      HIP_TRY(hipEventRecord(f.ev[2], stream));
+      HIP_TRY(rc::launch_aa_mark(d_out, W, H, at, list, cnt, stream));
+      HIP_TRY(hipEventRecord(f.ev[3], stream));
+      HIP_TRY(rc::launch_pattern_list(
+          f.ls, W, H, g, n, pat->x, pat->y, maxrec, list, cnt, d_out, f.zc,
+          rc::pattern_list_blocks(W, H, n, c.cus, tune().adaptive_blocks), stream, cuda));
+    }
+    if (f.end()) return -1;
+    // behind the span's end, and only where rc_pattern_stats_get has a count to wait for
+    if (at > 0) HIP_TRY(hipEventRecord(p.done, stream));
+    p.valid = true;
+    p.rays = n;
+    p.threshold = at;
+    p.pixels = (long long)W * H;
+    p.ev_listed = at > 0;
+    return 0;
+  });
+}
+
+// One pass of an accumulation call: samples [first, first + count) of the sequence, over every
+// pixel (at = 0) or over the pixels whose contrast in `out` reaches at; reset: the records count
+// as zero and are not read.
+struct AccumPass {
+  int first, count, at;
+  bool reset;
+};
+
+// The passes of one accumulation call on `stream` through the device's one-frame workspace (the
+// caller holds c.mu and has passed accum_refused and the range checks; at most
+// AccumFrame::kSlots passes).  A pass over every pixel is one launch; a masked pass is the
+// adaptive path's edge list (launch_aa_mark over d_out into aa_list) and the list kernel.
+// Nothing waits for the host: pass k counts into slot k of the call's counter block.
+// win (or null): the samples are those of this window of a virtual image (it has passed
+// rc_window_check at the sequence's g); the edge list, the records and the image stay the
+// window's own W x H.
+static int enqueue_accum(DevCtx& c, const rc_scene* s, int W, int H, const rc_options* opt,
+                         const rc_sample_seq* seq, const AccumPass* passes, int npasses,
+                         rc_accum_px* d_acc, uint8_t* d_out, hipStream_t stream,
+                         const rc_window* win = nullptr) {
+  AccumFrame& a = c.acc;
+  bool masked = false;
+  for (int k = 0; k < npasses; ++k) masked = masked || passes[k].at > 0;
+  auto prepare = [&]() -> int {
+    if (a.count.ensure(AccumFrame::kSlots * 8) ||
+        (masked && c.aa_list.ensure((size_t)W * H * sizeof(uint32_t)))) {
+      std::fprintf(stderr, "Error: out of device memory for the edge list (%d x %d)\n", W, H);
+      return -1;
+    }
+    return ensure_done(a.done);
+  };
+  return ws_frame(c, stream, prepare, [&]() -> int {
+    a.valid = false;   // the block is this call's from here on
+    SampleFrame f{c, stream, kSpanAccum};
+    if (f.begin(s, &a.count, (size_t)npasses * 8)) return -1;
+    unsigned* cnt = (unsigned*)a.count.p;
+    uint32_t* list = (uint32_t*)c.aa_list.p;
+    const int maxrec = opt->max_recursion, g = seq->grid;
+    const bool cuda = opt->mode == RC_MODE_CUDA;
+    const rc::Window vw = win ? rc::Window{win->full_w, win->full_h, win->x0, win->y0}
+                              : rc::Window{W, H, 0, 0};
+    for (int k = 0; k < npasses; ++k) {
+      const AccumPass& p = passes[k];
+      const bool last = k + 1 == npasses;
+      if (last && k > 0) HIP_TRY(hipEventRecord(f.ev[2], stream));
+      const uint8_t* px = seq->x + p.first;
+      const uint8_t* py = seq->y + p.first;
+      unsigned* slot = cnt + 2 * k;
+      if (p.at == 0) {
+        if (win)
+          HIP_TRY(rc::launch_accum_window(f.ls, vw, W, H, g, p.count, px, py, p.reset, maxrec,
+                                          d_acc, d_out, f.zc, slot + 1, stream, cuda));
+        else
+          HIP_TRY(rc::launch_accum(f.ls, W, H, g, p.count, px, py, p.reset, maxrec, d_acc, d_out,
+                                   f.zc, slot + 1, stream, cuda));
+      } else {
+        HIP_TRY(rc::launch_aa_mark(d_out, W, H, p.at, list, slot, stream));
+        if (last) HIP_TRY(hipEventRecord(f.ev[3], stream));
+        const int blocks = rc::accum_list_blocks(W, H, c.cus, tune().adaptive_blocks);
+        if (win)
+          HIP_TRY(rc::launch_accum_list_window(f.ls, vw, W, H, g, p.count, px, py, maxrec, list,
+                                               slot, d_acc, d_out, f.zc, slot + 1, blocks, stream,
+                                               cuda));
+        else
+          HIP_TRY(rc::launch_accum_list(f.ls, W, H, g, p.count, px, py, maxrec, list, slot, d_acc,
+                                        d_out, f.zc, slot + 1, blocks, stream, cuda));
+      }
+      a.samples[k] = (uint8_t)p.count;
+      a.listed[k] = p.at > 0;
+    }
+    if (f.end()) return -1;
+    HIP_TRY(hipEventRecord(a.done, stream));
+    a.valid = true;
+    a.passes = npasses;
+    a.pixels = (long long)W * H;
+    a.ev_first = npasses > 1 ? 2 : 0;
+    a.ev_listed = passes[npasses - 1].at > 0;
+    return 0;
+  });
+}
+
+// One window frame on `stream` through the device's one-frame workspace (the caller holds c.mu
+// and has passed window_refused): one launch of k_window at the options' factor.
+static int enqueue_window(DevCtx& c, const rc_scene* s, const rc_window* win, int W, int H,
+                          const rc_options* opt, uint8_t* d_out, hipStream_t stream) {
+  return ws_frame(c, stream, [] { return 0; }, [&]() -> int {
+    SampleFrame f{c, stream, kSpanWindow};
+    if (f.begin(s, nullptr, 0)) return -1;
+    HIP_TRY(rc::launch_window(f.ls, rc::Window{win->full_w, win->full_h, win->x0, win->y0}, W, H,
+                              ssaa_factor(opt, "rc_render_window"), opt->max_recursion, d_out,
+                              f.zc, stream, opt->mode == RC_MODE_CUDA));
+    return f.end();
+  });
+}
+
+// -------------------------------------------------------------- the two entry shapes --
+// A *_device entry behind its null checks and its refusal: on the current device, on the
+// caller's stream or the context's, enqueue(c, st), then finish_device.  plain: the frame goes
+// through the plain path (enqueue_render: rc_render_filtered_device), whose scene upload and
+// events live on c.stream, so c.stream is the caller's stream for the enqueue, and whose frame
+// may be a parity frame that logs a hand-off entry.
+template <class Enqueue>
+static int device_entry(const rc_options* opt, void* stream, rc_timing* timing, bool plain,
+                        Enqueue enqueue) {
+  Entered e;
+  if (enter(kCurrentDevice, true, e)) return -1;
+  DevCtx& c = *e.c;
+  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+  const long long own = plain ? c.lone_log.head : kNoLog;
+  hipStream_t saved = c.stream;
+  if (plain) c.stream = st;
+  const int rc = enqueue(c, st);
+  c.stream = saved;
+  return rc ? -1 : finish_device(c, opt, st, timing, own);
+}
+
+// A host-pixmap entry behind its null checks and its refusal (t0: taken before the refusal, so
+// that total_ms covers the whole call): the timing zeroed, one tuning snapshot, opt->device
+// entered, c.out for the W x H image and ensure_more(c) for what the feature adds, enqueue(c) on
+// c.stream, then finish_host.  oom (W, H): the message when either allocation fails, null: the
+// entry returns silently (rc_render_filtered, like rc_render).  plain: as device_entry; such a
+// frame also gets rc_render's tail (the counts through pin_tail, the pixmap prefaulted).
+template <class Ensure, class Enqueue>
+static int host_entry(const rc_options* opt, int W, int H, uint8_t* pixmap, rc_timing* timing,
+                      HostClock::time_point t0, const char* oom, bool plain, Ensure ensure_more,
+                      Enqueue enqueue) {
+  if (timing) std::memset(timing, 0, sizeof *timing);
+  const rc_tuning tu = tune();
+  Entered e;
+  if (enter_host(opt, e)) return -1;
+  DevCtx& c = *e.c;
+  const size_t bytes = (size_t)W * H * 3;
+  if (c.out.ensure(bytes) || ensure_more(c)) return oom ? say(oom, W, H) : -1;
+  const long long own = plain ? c.lone_log.head : kNoLog;
+  if (enqueue(c)) return -1;
+  return finish_host(c, opt, pixmap, bytes, tu, {plain, plain, own}, timing, t0);
+}
+
+static int nothing_more(DevCtx&) { return 0; }
+static const char kImageOom[] = "Error: out of device memory for the image (%d x %d)\n";
+
+extern "C" {
+
+// rc_render_rates*: W <= 0 or H <= 0 returns silently, before the refusal.
+int rc_render_rates_device(const rc_scene* s, int W, int H, const rc_options* opt,
+                           const uint8_t* d_rates, uint8_t* d_out, void* stream,
+                           rc_timing* timing) {
+  const char* who = "rc_render_rates_device";
+  if (!s || !opt || !d_rates || !d_out) return say("Error: %s: a null pointer\n", who);
+  if (W <= 0 || H <= 0) return -1;
+  if (rates_refused(who, opt, W, H)) return -1;
+  return device_entry(opt, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_rates(c, s, W, H, opt, d_rates, d_out, st);
+  });
+}
+
+int rc_render_rates(const rc_scene* s, int W, int H, const rc_options* opt, const uint8_t* rates,
+                    uint8_t* pixmap, rc_timing* timing) {
+  const char* who = "rc_render_rates";
+  if (!s || !opt || !rates || !pixmap) return say("Error: %s: a null pointer\n", who);
+  if (W <= 0 || H <= 0) return -1;
+  const auto t0 = HostClock::now();
+  if (rates_refused(who, opt, W, H)) return -1;
+  const size_t pixels = (size_t)W * H;
+  for (size_t i = 0; i < pixels; ++i) {
+    const unsigned r = rates[i];
+    if (r > 8u || !((0x117u >> r) & 1u))   // bits 0, 1, 2, 4, 8
+      return say("Error: %s: rate %u at pixel (%zu, %zu) is not 0, 1, 2, 4 or 8\n", who, r,
+                 i % (size_t)W, i / (size_t)W);
+  }
+  return host_entry(
+      opt, W, H, pixmap, timing, t0,
+      "Error: out of device memory for the image and its rate map (%d x %d)\n", false,
+      [&](DevCtx& c) { return c.rates.map.ensure(pixels); },
+      [&](DevCtx& c) -> int {
+        uint8_t* d_out = (uint8_t*)c.out.p;
+        uint8_t* d_rates = (uint8_t*)c.rates.map.p;
+        // the pixmap goes in as well as out: the bytes of rate-0 pixels come back as they were
+        HIP_TRY(hipMemcpyAsync(d_rates, rates, pixels, hipMemcpyHostToDevice, c.stream));
+        HIP_TRY(hipMemcpyAsync(d_out, pixmap, pixels * 3, hipMemcpyHostToDevice, c.stream));
+        return enqueue_rates(c, s, W, H, opt, d_rates, d_out, c.stream);
+      });
+}
+
+int rc_render_pattern_device(const rc_scene* s, int W, int H, const rc_options* opt,
+                             const rc_pattern* pat, int threshold, uint8_t* d_out, void* stream,
+                             rc_timing* timing) {
+  const char* who = "rc_render_pattern_device";
+  if (!s || !opt || !pat || !d_out) return say("Error: %s: a null pointer\n", who);
+  if (pattern_refused(who, opt, W, H, pat, threshold)) return -1;
+  return device_entry(opt, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_pattern(c, s, W, H, opt, pat, threshold, d_out, st);
+  });
+}
+
+int rc_render_pattern(const rc_scene* s, int W, int H, const rc_options* opt,
+                      const rc_pattern* pat, int threshold, uint8_t* pixmap, rc_timing* timing) {
+  const char* who = "rc_render_pattern";
+  if (!s || !opt || !pat || !pixmap) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  if (pattern_refused(who, opt, W, H, pat, threshold)) return -1;
+  return host_entry(opt, W, H, pixmap, timing, t0, kImageOom, false, nothing_more, [&](DevCtx& c) {
+    return enqueue_pattern(c, s, W, H, opt, pat, threshold, (uint8_t*)c.out.p, c.stream);
+  });
+}
+
+// rc_accum_pass_device and rc_accum_pass_window_device (win: null for the former)
+static int accum_pass(const char* who, const rc_scene* s, const rc_window* win, int W, int H,
+                      const rc_options* opt, const rc_sample_seq* seq, int first, int count,
+                      int threshold, int reset, rc_accum_px* d_acc, uint8_t* d_out, void* stream,
+                      rc_timing* timing) {
+  if (!s || !opt || !seq || !d_acc || !d_out) return say("Error: %s: a null pointer\n", who);
+  if ((uintptr_t)d_acc & 7u)
+    return say("Error: %s: the accumulator is not 8-byte aligned\n", who);
+  if (accum_refused(who, opt, W, H, seq, threshold, threshold == 0, threshold > 0)) return -1;
+  if (win && rc_window_check(win, W, H, seq->grid)) return -1;
+  if (count < 1 || count > 16 || first < 0 || first > seq->nsamples - count)
+    return say("Error: %s: samples [%d, %d + %d) of a sequence of %d: a pass takes 1..16 samples "
+               "inside the sequence\n", who, first, first, count, seq->nsamples);
+  if (reset && threshold > 0)
+    return say("Error: %s: reset with threshold %d: a reset pass takes every pixel (there is no "
+               "image yet to find edges in), leave the threshold at 0\n", who, threshold);
+  const AccumPass pass{first, count, threshold, reset != 0};
+  return device_entry(opt, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_accum(c, s, W, H, opt, seq, &pass, 1, d_acc, d_out, st, win);
+  });
+}
+
+int rc_accum_pass_device(const rc_scene* s, int W, int H, const rc_options* opt,
+                         const rc_sample_seq* seq, int first, int count, int threshold, int reset,
+                         rc_accum_px* d_acc, uint8_t* d_out, void* stream, rc_timing* timing) {
+  return accum_pass("rc_accum_pass_device", s, nullptr, W, H, opt, seq, first, count, threshold,
+                    reset, d_acc, d_out, stream, timing);
+}
+
+int rc_accum_pass_window_device(const rc_scene* s, const rc_window* win, int W, int H,
+                                const rc_options* opt, const rc_sample_seq* seq, int first,
+                                int count, int threshold, int reset, rc_accum_px* d_acc,
+                                uint8_t* d_out, void* stream, rc_timing* timing) {
+  const char* who = "rc_accum_pass_window_device";
+  if (!win) return say("Error: %s: a null pointer\n", who);
+  return accum_pass(who, s, win, W, H, opt, seq, first, count, threshold, reset, d_acc, d_out,
+                    stream, timing);
+}
+
+int rc_render_window_device(const rc_scene* s, const rc_window* win, int W, int H,
+                            const rc_options* opt, uint8_t* d_out, void* stream,
+                            rc_timing* timing) {
+  const char* who = "rc_render_window_device";
+  if (!s || !win || !opt || !d_out) return say("Error: %s: a null pointer\n", who);
+  if (window_refused(who, opt, W, H, win)) return -1;
+  return device_entry(opt, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_window(c, s, win, W, H, opt, d_out, st);
+  });
+}
+
+int rc_render_window(const rc_scene* s, const rc_window* win, int W, int H, const rc_options* opt,
+                     uint8_t* pixmap, rc_timing* timing) {
+  const char* who = "rc_render_window";
+  if (!s || !win || !opt || !pixmap) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  if (window_refused(who, opt, W, H, win)) return -1;
+  return host_entry(opt, W, H, pixmap, timing, t0, kImageOom, false, nothing_more, [&](DevCtx& c) {
+    return enqueue_window(c, s, win, W, H, opt, (uint8_t*)c.out.p, c.stream);
+  });
+}
+
+// No frame of the workspace: the resolve of an accumulator alone, on the current device.
+int rc_accum_resolve_device(const rc_accum_px* d_acc, int W, int H, uint8_t* d_out, void* stream) {
+  const char* who = "rc_accum_resolve_device";
+  if (!d_acc || !d_out) return say("Error: %s: a null pointer\n", who);
+  if ((uintptr_t)d_acc & 7u)
+    return say("Error: %s: the accumulator is not 8-byte aligned\n", who);
+  if (W <= 0 || H <= 0 ||
+      ((unsigned long long)W * (unsigned long long)H + 255) / 256 > 0x7fffffffull)
+    return say("Error: %s: %d x %d: both sides must be at least 1 and the image at most 2^39 - 256 "
+               "pixels (one grid)\n", who, W, H);
+  Entered e;
+  if (enter(kCurrentDevice, false, e)) return -1;
+  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
+  HIP_TRY(rc::launch_accum_resolve(d_acc, W, H, d_out, st));
+  return 0;
+}
+
+int rc_render_accum(const rc_scene* s, int W, int H, const rc_options* opt,
+                    const rc_sample_seq* seq, int dense, int threshold, uint8_t* pixmap,
+                    rc_timing* timing) {
+  const char* who = "rc_render_accum";
+  if (!s || !opt || !seq || !pixmap) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  // which kernels run is known once the sequence and dense have been checked; the limits of both
+  // are tested here, a call that needs only one of them being a sub-case of no interest
+  if (accum_refused(who, opt, W, H, seq, threshold, true, threshold > 0)) return -1;
+  if (dense < 1 || dense > seq->nsamples)
+    return say("Error: %s: dense %d is not 1..%d (the sequence's length)\n", who, dense,
+               seq->nsamples);
+  // samples [0, dense) for every pixel in chunks of at most 16, the first chunk resetting the
+  // accumulator; then one single-sample pass for each of the others
+  AccumPass passes[AccumFrame::kSlots];
+  int np = 0;
+  for (int k = 0; k < dense; k += 16)
+    passes[np++] = {k, dense - k < 16 ? dense - k : 16, 0, k == 0};
+  for (int k = dense; k < seq->nsamples; ++k) passes[np++] = {k, 1, threshold, false};
+  return host_entry(
+      opt, W, H, pixmap, timing, t0,
+      "Error: out of device memory for the image and its accumulator (%d x %d)\n", false,
+      [&](DevCtx& c) { return c.accum_px.ensure((size_t)W * H * sizeof(rc_accum_px)); },
+      [&](DevCtx& c) {
+        return enqueue_accum(c, s, W, H, opt, seq, passes, np, (rc_accum_px*)c.accum_px.p,
+                             (uint8_t*)c.out.p, c.stream);
+      });
+}
+
+int rc_render_filtered_device(const rc_scene* s, int W, int H, const rc_options* opt,
+                              const rc_filter* f, uint8_t* d_out, void* stream,
+                              rc_timing* timing) {
+  const char* who = "rc_render_filtered_device";
+  if (!s || !opt || !f || !d_out) return say("Error: %s: a null pointer\n", who);
+  if (filtered_refused(who, opt, W, H, f)) return -1;
+  return device_entry(opt, stream, timing, true, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_render(c, s, W, H, 0, 1, H, opt, d_out, st, true, nullptr, nullptr, f);
+  });
+}
+
+int rc_render_filtered(const rc_scene* s, int W, int H, const rc_options* opt, const rc_filter* f,
+                       uint8_t* pixmap, rc_timing* timing) {
+  const char* who = "rc_render_filtered";
+  if (!s || !opt || !f || !pixmap) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  if (filtered_refused(who, opt, W, H, f)) return -1;
+  return host_entry(opt, W, H, pixmap, timing, t0, nullptr, true, nothing_more, [&](DevCtx& c) {
+    return enqueue_render(c, s, W, H, 0, 1, H, opt, (uint8_t*)c.out.p, c.stream, true, nullptr,
+                          nullptr, f);
+  });
+}
+
+// No frame of the workspace either: the filter pass alone, on the current device.
+int rc_filter_image_device(const uint8_t* d_src, int W, int H, int s, const rc_filter* f,
+                           uint8_t* d_dst, void* stream) {
+  const char* who = "rc_filter_image_device";
+  if (!d_src || !d_dst || !f) return say("Error: %s: a null pointer\n", who);
+  if (rc_filter_check(f, s)) return -1;
+  if (W <= 0 || H <= 0 || W > (1 << 28) / s || H > (1 << 28) / s)
+    return say("Error: %s: %d x %d at factor %d: both sides must be 1 .. 2^28 / s\n", who, W, H, s);
+  const uintptr_t a = (uintptr_t)d_src, b = (uintptr_t)d_dst;
+  const size_t nb = (size_t)W * H * 3, na = nb * (size_t)s * s;
+  if (a < b + nb && b < a + na)
+    return say("Error: %s: the source and the destination overlap: every output pixel reads its "
+               "neighbours' subsamples\n", who);
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  HIP_TRY(rc::launch_filter_down(d_src, W, H, s, f->taps, f->ntaps, d_dst,
+                                 stream ? (hipStream_t)stream : c->stream));
+  return 0;
+}
+
+}  // extern "C"
+

@@ -10,7 +10,7 @@ O=raytracing-programs_amd/lib/obj
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off \
   -fno-gpu-flush-denormals-to-zero -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude \
   -Iraytracing-programs_amd/csrc -w "$@" -c raytracing-programs_amd/csrc/rc_kernels.hip -o $O/var_$name.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $O/var_$name.o $O/rc_api.o $O/rc_shard.o \
-  $O/rc_scene.o -o raytracing-programs_amd/lib/libraycast_hip_$name.so -L/opt/rocm/lib -lrccl \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $O/var_$name.o $O/rc_api.o $O/rc_sampling.o \
+  $O/rc_shard.o $O/rc_filter.o $O/rc_scene.o -o raytracing-programs_amd/lib/libraycast_hip_$name.so -L/opt/rocm/lib -lrccl \
   -Wl,-rpath,/opt/rocm/lib -lpthread
 echo built libraycast_hip_$name.so
