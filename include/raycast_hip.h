@@ -557,7 +557,8 @@ typedef struct rc_accum_stats {
 } rc_accum_stats;
 _Static_assert(sizeof(rc_accum_stats) == 32, "rc_accum_stats layout (ctypes binding)");
 /* The last accumulation call enqueued on the current device: waits for it, then reads its device
- * counters (one slot a pass, so the passes never wait for the host).  -1 if there was none. */
+ * counters (one slot a pass, so the passes never wait for the host).  -1 if there was none.  A
+ * call without a pass (rc_accum_scroll_device with nothing exposed) gives four zeros. */
 int rc_accum_stats_get(rc_accum_stats *out);
 /* The kernel spans (ms, HIP events) of the last pass of the last accumulation call on the current
  * device: ms[0] the edge list (0 for a pass that takes every pixel), ms[1] the samples.  Returns
@@ -642,6 +643,60 @@ int rc_accum_pass_window_device(const rc_scene *scene, const rc_window *win, int
                                 const rc_options *opt, const rc_sample_seq *seq, int first,
                                 int count, int threshold, int reset, rc_accum_px *d_acc,
                                 uint8_t *d_out, void *stream, rc_timing *timing);
+
+/* Scrolling an accumulated view: a pan that keeps the overlap and shoots only the exposed strips
+ * (rc_accum_scroll_device; fast and cuda mode).  `win` is the NEW window and (dx, dy) is the new
+ * origin minus the old one, in whole pixels of the virtual image; either sign and any magnitude
+ * (all arithmetic on them is done in 64 bits).  Source and destination are two states (records
+ * and image) of the same W x H: a viewer keeps two and swaps them.
+ * For every destination pixel (x, y) let (sx, sy) = (x + dx, y + dy).
+ * Kept:     0 <= sx < W and 0 <= sy < H.  acc_dst[y][x] = acc_src[sy][sx] and
+ *           out_dst[y][x] = out_src[sy][sx], verbatim, whatever the record holds: any n, 0 too, a
+ *           state left by masked passes too.
+ * Exposed:  every other pixel gets exactly what a reset pass followed by t = 0 passes over
+ *           seq[0..count) would give window pixel (x, y) of `win`:
+ *             sum[c] = sum over k < count of B_g[g*(y0 + y) + y[k]][g*(x0 + x) + x[k]][c],
+ *             n = count, out = res(sum, n),
+ *           B_g the mode's g*full_w x g*full_h image: the accumulation contract through a window,
+ *           word for word.  1 <= count <= seq->nsamples (up to 64); the library shoots it in
+ *           chunks of at most 16, the first one resetting, as rc_render_accum does for its dense
+ *           part.
+ * Every destination pixel is stored to exactly once per array; the source is not written.
+ * |dx| >= W or |dy| >= H: nothing is kept, the call is a reset pass of the whole window into the
+ * destination.  dx = dy = 0: nothing is exposed, the call is a copy.
+ * So when the source was built through the old window by a reset pass and t = 0 passes covering
+ * seq[0..count), the destination equals, record for record and byte for byte, the state built
+ * from scratch through `win` (window independence, above).  With any other history the kept
+ * records are simply moved.  The old window is not an argument and is not checked: only kept
+ * pixels come from it, and they lie inside `win` as well.
+ * E = W*H - max(0, W - |dx|) * max(0, H - |dy|) pixels are exposed.
+ * On the device: the move is one memory-bound kernel over the kept rectangle (one 8-byte record
+ * and three bytes a pixel, nothing shot); the exposed set is the complement of that rectangle, at
+ * most four rectangles whose sizes the host knows, so the sample kernel needs no list: a fixed
+ * number of workgroups strides over [0, E), one lane an exposed pixel, and a strip three pixels
+ * wide fills whole waves.  On the current device and the caller's stream (NULL: the library's
+ * stream, as rc_accum_pass_device); asynchronous unless timing is requested; nothing waits for
+ * the host, so a source written on that stream just before the call is honoured.
+ * rc_options: mode fast or cuda; ssaa 0 or 1; max_recursion as everywhere.  rc_timing.kernel_ms
+ * covers the move and the samples, zero_normalize counts the exposed pixels' rays only.
+ * Stats and spans are the accumulation family's: rc_accum_stats_get gives passes = the number of
+ * chunks, active_pixels = E, saturated = 0 and rays = E * count (all four 0 when E = 0);
+ * rc_accum_phase_ms gives ms[0] = the move and ms[1] = all the sample chunks.
+ * Refused, each with one message and -1, from the arguments alone (before any device work), in
+ * this order: a null pointer; an accumulator (either one) that is not 8-byte aligned; every
+ * refusal of rc_accum_pass_window_device with t = 0, on W and H (the options, the sequence, the
+ * sides, the kernels' grids, then rc_window_check at the sequence's g); W * H >= 2^32; count
+ * outside 1..nsamples; the byte ranges of d_acc_src and d_acc_dst overlapping (equal pointers
+ * included); those of d_out_src and d_out_dst overlapping.
+ * Out of scope: no host-pixmap form and no RAYCAST_* variable (state across calls has no meaning
+ * for the one-call drop-in); no threshold (follow with rc_accum_pass_window_device, t > 0, on the
+ * new window); no in-place form; no reuse across a zoom. */
+int rc_accum_scroll_device(const rc_scene *scene, const rc_window *win, int width, int height,
+                           const rc_options *opt, const rc_sample_seq *seq, int count,
+                           int dx, int dy,
+                           const rc_accum_px *d_acc_src, const uint8_t *d_out_src,
+                           rc_accum_px *d_acc_dst, uint8_t *d_out_dst,
+                           void *stream, rc_timing *timing);
 
 /* Frames in flight (an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out

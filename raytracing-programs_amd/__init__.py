@@ -430,6 +430,12 @@ def _hip_lib_locked():
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.POINTER(RcTiming)]
+    lib.rc_accum_scroll_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcWindow), ctypes.c_int,
+                                           ctypes.c_int, ctypes.POINTER(RcOptions),
+                                           ctypes.POINTER(RcSampleSeq), ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.POINTER(RcTiming)]
     _hip = lib
     return lib
 
@@ -1221,7 +1227,8 @@ def accum_stats():
 
 def accum_phase_ms():
     """Kernel spans of the last pass of the last accumulation call (rc_accum_phase_ms), in ms:
-    {"mark", "shoot"}; "mark" is 0 for a pass that takes every pixel."""
+    {"mark", "shoot"}; "mark" is 0 for a pass that takes every pixel.  After accum_scroll_device
+    "mark" is the move of the kept rectangle and "shoot" all the sample chunks."""
     return _phase_ms("rc_accum_phase_ms", ("mark", "shoot"),
                      "rc_accum_phase_ms: no accumulation call on this device")
 
@@ -1330,6 +1337,66 @@ def accum_pass_window_device(scene, window, width, height, seq, first, count, d_
         _call("rc_accum_pass_window_device", scene.packed(), ctypes.byref(win), width, height,
               ctypes.byref(opt), ctypes.byref(s), int(first), int(count), int(threshold),
               1 if reset else 0, ctypes.c_void_p(d_acc_ptr), ctypes.c_void_p(d_out_ptr),
+              _stream(stream_ptr), t)
+
+
+def window_pan(window, dx, dy):
+    """The window (full_w, full_h, x0, y0) moved by (dx, dy) whole pixels of the virtual image:
+    rc_accum_scroll_device's new window for that pan."""
+    fw, fh, x0, y0 = (int(v) for v in window)
+    return fw, fh, x0 + int(dx), y0 + int(dy)
+
+
+def scroll_kept(width, height, dx, dy):
+    """The kept rectangle of a scroll by (dx, dy) in destination coordinates, (kx, ky, kw, kh);
+    kw = kh = 0 when nothing is kept.  The exposed pixels are the other W*H - kw*kh."""
+    w, h, dx, dy = int(width), int(height), int(dx), int(dy)
+    if abs(dx) >= w or abs(dy) >= h:
+        return 0, 0, 0, 0
+    return max(0, -dx), max(0, -dy), w - abs(dx), h - abs(dy)
+
+
+def accum_scroll(acc, out, big, g, points, dx, dy):
+    """rc_accum_scroll_device's contract in numpy: the state (acc, out) moved by (-dx, -dy) where
+    source and destination overlap, and a reset pass plus t = 0 passes over `points` (1..64, in
+    chunks of 16: accum_step) everywhere else, on `big`, the NEW window's [g*H, g*W, 3] samples
+    (window_crop).  Returns (acc', out', exposed pixels); the arguments are not written."""
+    acc, out = _accum_state(acc), np.asarray(out)
+    h, w = acc.shape[:2]
+    if out.shape != (h, w, 3) or out.dtype != np.uint8:
+        raise ValueError(f"accum_scroll: acc {acc.shape} and out {out.dtype} {out.shape} do not "
+                         "fit one image")
+    points = [(int(x), int(y)) for x, y in points]
+    if not 1 <= len(points) <= ACCUM_MAX_SAMPLES:
+        raise ValueError(f"accum_scroll: {len(points)} samples, not 1..{ACCUM_MAX_SAMPLES}")
+    new_acc, new_out = np.zeros_like(acc), np.zeros_like(out)
+    for k in range(0, len(points), ACCUM_MAX_COUNT):
+        new_acc, new_out, _, _ = accum_step(new_acc, new_out, big, g,
+                                            points[k:k + ACCUM_MAX_COUNT], 0, reset=k == 0)
+    kx, ky, kw, kh = scroll_kept(w, h, dx, dy)
+    if kw:
+        sx, sy = kx + int(dx), ky + int(dy)
+        new_acc[ky:ky + kh, kx:kx + kw] = acc[sy:sy + kh, sx:sx + kw]
+        new_out[ky:ky + kh, kx:kx + kw] = out[sy:sy + kh, sx:sx + kw]
+    return new_acc, new_out, w * h - kw * kh
+
+
+def accum_scroll_device(scene, window, width, height, seq, count, dx, dy, d_acc_src_ptr,
+                        d_out_src_ptr, d_acc_dst_ptr, d_out_dst_ptr, stream_ptr=None, depth=6,
+                        mode="fast", timing=None):
+    """rc_accum_scroll_device (accum_scroll): `window` is the NEW window, (dx, dy) its origin minus
+    the old one.  The destination state gets the source's records and bytes where the two windows
+    overlap and seq[0..count) freshly accumulated where the pan exposed new pixels; the two states
+    are separate device buffers of the same W x H.  Enqueued on the stream and asynchronous unless
+    `timing` is given."""
+    win = _rc_window(window)
+    s = _rc_sample_seq(seq)
+    opt = options(depth, mode)
+    with _timed(timing) as (_, t):
+        _call("rc_accum_scroll_device", scene.packed(), ctypes.byref(win), width, height,
+              ctypes.byref(opt), ctypes.byref(s), int(count), int(dx), int(dy),
+              ctypes.c_void_p(d_acc_src_ptr), ctypes.c_void_p(d_out_src_ptr),
+              ctypes.c_void_p(d_acc_dst_ptr), ctypes.c_void_p(d_out_dst_ptr),
               _stream(stream_ptr), t)
 
 

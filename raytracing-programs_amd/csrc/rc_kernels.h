@@ -234,6 +234,40 @@ hipError_t launch_accum_list_window(const LaunchScene& s, const Window& w, int W
                                     uint8_t* out, unsigned long long* zcount, unsigned* sat,
                                     int blocks, hipStream_t stream, bool cuda_sem);
 
+// Scrolling an accumulated view (rc_accum_scroll_device; fast and cuda modes): the window moved
+// by (dx, dy) = new origin - old origin, source and destination two states of the same W x H.
+// scroll_rects: the kept rectangle K in destination coordinates, kw x kh at (kx, ky) (kw = kh = 0:
+// nothing is kept), and the exposed set, the complement of K, as four rectangles in the order rows
+// above K, columns left of K, columns right of K, rows below K: rectangle k holds entries
+// [first[k], first[k + 1]) of [0, total), row-major, w[k] wide (1 where it is empty) at
+// (x[k], y[k]).  total = W*H - kw*kh.  W*H >= 2^32 or a side below 1: everything is 0.
+//   launch_accum_move     the records and bytes of K from the source to the destination, nothing
+//                         shot; the arrays must not overlap;
+//   launch_accum_exposed  `count` (1..16) samples for every exposed pixel of the window `w`, with
+//                         `blocks` workgroups (accum_exposed_blocks) striding over the exposed set;
+//                         reset: the records are not read and count as zero.  acc and out are the
+//                         destination's; the pixels of K are not stored to.
+// Both return hipErrorInvalidValue for what accum_supported(W, H, g, true) refuses; the former
+// for an empty K, the latter for an empty exposed set, a window outside its image, count outside
+// 1..16 and blocks outside 1..4096.
+struct ScrollRects {
+  unsigned first[4], w[4];
+  int x[4], y[4];
+  unsigned total;
+  int kx, ky, kw, kh;
+};
+ScrollRects scroll_rects(int W, int H, int dx, int dy);
+hipError_t launch_accum_move(int W, int H, int g, int dx, int dy, const void* acc_src,
+                             const uint8_t* out_src, void* acc_dst, uint8_t* out_dst,
+                             hipStream_t stream);
+hipError_t launch_accum_exposed(const LaunchScene& s, const Window& w, int W, int H, int g,
+                                int dx, int dy, int count, const uint8_t* px, const uint8_t* py,
+                                bool reset, int maxrec, void* acc, uint8_t* out,
+                                unsigned long long* zcount, int blocks, hipStream_t stream,
+                                bool cuda_sem);
+// want > 0: that many; else from the CU count, at most the wave steps `exposed` pixels can need
+int accum_exposed_blocks(unsigned exposed, int cus, int want);
+
 hipError_t launch_parity(const LaunchScene& s, int W, int H, int maxrec, uint8_t* out,
                          const ParityWork& w, unsigned long long* zcount, hipStream_t stream,
                          const hipEvent_t* ev);

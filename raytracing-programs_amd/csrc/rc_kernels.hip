@@ -4462,4 +4462,174 @@ hipError_t launch_accum_list_window(const LaunchScene& s, const Window& w, int W
   return hipGetLastError();
 }
 
+// ------------------------------------ scrolling an accumulated view (fast, cuda) --
+// rc_accum_scroll_device (include/raycast_hip.h): the destination state is the source state moved
+// by (-dx, -dy) where the two windows overlap (the kept rectangle K, scroll_rects) and freshly
+// accumulated where the pan exposed new pixels.  Two kernels, behind every other kernel of the
+// file as section 16's and 17's were.
+//
+// k_accum_move: the kept rectangle, one lane a pixel, adjacent lanes adjacent pixels of a row: one
+// 8-byte load and one 8-byte store of the record and three bytes of the image.  grid.x covers a
+// row of K in 256-pixel pieces, grid.y strides over its rows; every offset is a 64-bit pixel
+// index.  (kx, ky): K's corner in the destination, (sx, sy) = (kx + dx, ky + dy) in the source.
+__global__ void __launch_bounds__(256) k_accum_move(
+    const uint2* __restrict__ acc_src, const uint8_t* __restrict__ out_src,
+    uint2* __restrict__ acc_dst, uint8_t* __restrict__ out_dst, int W, int kw, int kh, int kx,
+    int ky, int sx, int sy) {
+  const unsigned x = blockIdx.x * 256u + threadIdx.x;
+  if (x >= (unsigned)kw) return;
+  for (unsigned y = blockIdx.y; y < (unsigned)kh; y += gridDim.y) {
+    const size_t s = (size_t)((unsigned)sy + y) * (unsigned)W + ((unsigned)sx + x);
+    const size_t d = (size_t)((unsigned)ky + y) * (unsigned)W + ((unsigned)kx + x);
+    acc_dst[d] = acc_src[s];
+    const uint8_t* q = out_src + s * 3;
+    uint8_t* o = out_dst + d * 3;
+    const uint8_t r8 = q[0], g8 = q[1], b8 = q[2];
+    o[0] = r8;
+    o[1] = g8;
+    o[2] = b8;
+  }
+}
+
+// Pixel e of the exposed set, e < r.total: the rectangle is found by comparing e with the
+// rectangles' first entries (an empty rectangle shares its first entry with the next one, so it is
+// never the last one at or below e), then one unsigned divide by that rectangle's width.
+__device__ __forceinline__ void exposed_pixel(const ScrollRects& r, unsigned e, int& x, int& y) {
+  unsigned first = r.first[0], w = r.w[0];
+  int x0 = r.x[0], y0 = r.y[0];
+#pragma unroll
+  for (int k = 1; k < 4; ++k) {
+    const bool here = e >= r.first[k];
+    first = here ? r.first[k] : first;
+    w = here ? r.w[k] : w;
+    x0 = here ? r.x[k] : x0;
+    y0 = here ? r.y[k] : y0;
+  }
+  const unsigned i = e - first, row = i / w;
+  x = x0 + (int)(i - row * w);
+  y = y0 + (int)row;
+}
+
+// k_accum_exposed: accum_listed's body over the exposed set instead of a list: a fixed number of
+// workgroups whose waves stride over [0, r.total) with a 64-bit index, one lane per exposed pixel,
+// so a strip three pixels wide fills whole waves.  `reset` (the call's first chunk): the record is
+// not read and counts as zero, as in accum_dense; a later chunk adds to the record the chunk
+// before it stored.  No saturation: a scroll takes at most 64 samples.  The pixel is derived
+// again from the entry after the samples (opaque lane, as accum_listed reads its list entry
+// again) rather than carried across sample_shoot.  (ox, oy): as accum_dense's.
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_exposed(
+    Scene sc, Cam cam, int W, ScrollRects r, int ox, int oy, int lg, int count, PatWords pat,
+    int reset, int maxrec, uint2* __restrict__ acc, uint8_t* __restrict__ out,
+    unsigned long long* __restrict__ zcount) {
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  stage_scene<kStage>(sc, stage);   // its barrier comes before the loop: every thread is here
+  const int lane = threadIdx.x & 63;
+  // wave-uniform by construction: told to the compiler, so the loop's counters stay scalar
+  const unsigned wave =
+      __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
+  const unsigned step = gridDim.x * (kBlock / 64) * 64u;   // <= 4096 * 4 * 64
+  const unsigned n = r.total;
+  // 64-bit index: n + step may pass 2^32
+  for (unsigned long long first = (unsigned long long)wave * 64u; first < n; first += step) {
+    if (first + (unsigned)lane >= n) continue;
+    int x, y;
+    exposed_pixel(r, (unsigned)first + (unsigned)lane, x, y);
+    const int xs = (int)(((unsigned)x + (unsigned)ox) << lg);
+    const int ys = (int)(((unsigned)y + (unsigned)oy) << lg);
+    unsigned rg = 0u, b = 0u;
+    for (int k = 0; k < count; ++k) {   // uniform
+      unsigned srg, sb;
+      sample_shoot<kCuda>(sc, cam, xs + pat_entry(pat.x, (unsigned)k),
+                          ys + pat_entry(pat.y, (unsigned)k), maxrec, zcount, srg, sb);
+      rg += srg;
+      b += sb;
+    }
+    unsigned l = (unsigned)lane;
+    asm volatile("" : "+v"(l));
+    exposed_pixel(r, (unsigned)first + l, x, y);
+    const size_t q = (size_t)(unsigned)y * (unsigned)W + (unsigned)x;
+    uint2 rec = make_uint2(0u, 0u);
+    if (!reset) rec = acc[q];
+    rec.x += rg;
+    rec.y += b + ((unsigned)count << 16);
+    acc[q] = rec;
+    uint8_t r8, g8, b8;
+    accum_resolve_px(rec, r8, g8, b8);
+    uint8_t* o = out + q * 3;
+    o[0] = r8;
+    o[1] = g8;
+    o[2] = b8;
+  }
+}
+
+ScrollRects scroll_rects(int W, int H, int dx, int dy) {
+  ScrollRects r = {};
+  if (W < 1 || H < 1 || (unsigned long long)W * (unsigned long long)H >= (1ull << 32)) return r;
+  // 64 bits: -INT_MIN does not occur
+  const long long ax = dx < 0 ? -(long long)dx : dx, ay = dy < 0 ? -(long long)dy : dy;
+  if (ax < W && ay < H) {
+    r.kw = W - (int)ax, r.kh = H - (int)ay;
+    r.kx = dx < 0 ? (int)ax : 0, r.ky = dy < 0 ? (int)ay : 0;
+  }   // else nothing is kept: K is empty at (0, 0), and the rows below it are the whole window
+  const int right = r.kx + r.kw;
+  const unsigned wd[4] = {(unsigned)W, (unsigned)r.kx, (unsigned)(W - right), (unsigned)W};
+  const unsigned ht[4] = {(unsigned)r.ky, (unsigned)r.kh, (unsigned)r.kh,
+                          (unsigned)(H - r.ky - r.kh)};
+  const int xs[4] = {0, 0, right, 0}, ys[4] = {0, r.ky, r.ky, r.ky + r.kh};
+  for (int k = 0; k < 4; ++k) {
+    r.first[k] = r.total;
+    r.w[k] = wd[k] ? wd[k] : 1u;   // an empty rectangle is never divided by
+    r.x[k] = xs[k], r.y[k] = ys[k];
+    r.total += wd[k] * ht[k];      // the four are disjoint parts of W*H < 2^32
+  }
+  return r;
+}
+
+int accum_exposed_blocks(unsigned exposed, int cus, int want) {
+  if (want > 0) return want;
+  const unsigned need = exposed / kBlock + (exposed % kBlock ? 1u : 0u);   // as list_blocks
+  const unsigned cap = (unsigned)(cus > 0 ? cus : 256) * RC_PHASE_A_WAVES;
+  if (need <= cap) return (int)need;   // one step a wave: nothing strides
+  // The entries of a rectangle are row-major, so a static stride that is a multiple of its width
+  // keeps a wave in one column of the window and the waves whose column crosses the expensive
+  // shapes finish last; an odd number of workgroups makes the stride drift through the columns
+  // (the rate map's lists: DESIGN.md section 12; here: section 18).
+  return (int)(cap > 2u && (cap & 1u) == 0u ? cap - 1u : cap);
+}
+
+hipError_t launch_accum_move(int W, int H, int g, int dx, int dy, const void* acc_src,
+                             const uint8_t* out_src, void* acc_dst, uint8_t* out_dst,
+                             hipStream_t stream) {
+  const ScrollRects r = scroll_rects(W, H, dx, dy);
+  if (!accum_supported(W, H, g, true) || r.kw < 1 || r.kh < 1) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(r.kw + 255) / 256u, (unsigned)(r.kh < 65535 ? r.kh : 65535));
+  hipLaunchKernelGGL(k_accum_move, grid, dim3(256), 0, stream, (const uint2*)acc_src, out_src,
+                     (uint2*)acc_dst, out_dst, W, r.kw, r.kh, r.kx, r.ky, r.kx + dx, r.ky + dy);
+  return hipGetLastError();
+}
+
+hipError_t launch_accum_exposed(const LaunchScene& s, const Window& w, int W, int H, int g,
+                                int dx, int dy, int count, const uint8_t* px, const uint8_t* py,
+                                bool reset, int maxrec, void* acc, uint8_t* out,
+                                unsigned long long* zcount, int blocks, hipStream_t stream,
+                                bool cuda_sem) {
+  if (!accum_supported(W, H, g, true) || !window_inside(w, W, H, g) || count < 1 || count > 16 ||
+      blocks < 1 || blocks > 4096)
+    return hipErrorInvalidValue;
+  const ScrollRects r = scroll_rects(W, H, dx, dy);
+  if (r.total == 0u) return hipErrorInvalidValue;
+  const int lg = pattern_log2(g, 1, 3);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, w.full_w * g, w.full_h * g);   // of the g*full_w x g*full_h image
+  const PatWords pat = pattern_words(count, px, py);
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_accum_exposed<cuda.value, st.value>), dim3((unsigned)blocks),
+                       dim3(kBlock), 0, stream, sc, cam, W, r, w.x0, w.y0, lg, count, pat,
+                       reset ? 1 : 0, maxrec, (uint2*)acc, out, zcount);
+  });
+  return hipGetLastError();
+}
+
 }  // namespace rc

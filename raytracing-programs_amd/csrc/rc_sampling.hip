@@ -416,8 +416,8 @@ int rc_accum_stats_get(rc_accum_stats* out) {
   HIP_TRY(hipEventSynchronize(f.done));   // the call's stream, up to its last pass
   unsigned n[AccumFrame::kSlots][2] = {};   // per pass {listed, saturated}
   HIP_TRY(hipMemcpy(n, f.count.p, (size_t)f.passes * sizeof n[0], hipMemcpyDeviceToHost));
+  std::memset(out, 0, sizeof *out);   // a call without a pass (a scroll that exposes nothing)
   out->passes = f.passes;
-  out->rays = 0;
   for (int k = 0; k < f.passes; ++k) {
     out->active_pixels = f.listed[k] ? (int64_t)n[k][0] : (int64_t)f.pixels;
     out->saturated = (int64_t)n[k][1];
@@ -770,6 +770,57 @@ static int enqueue_accum(DevCtx& c, const rc_scene* s, int W, int H, const rc_op
   });
 }
 
+// One scroll on `stream` through the device's one-frame workspace (the caller holds c.mu and has
+// passed rc_accum_scroll_device's refusals): the kept rectangle moved from the source state to the
+// destination, then seq[0..count) for the exposed pixels in chunks of at most 16, the first one
+// resetting; chunk k counts into slot k, nothing waits for the host.  The accumulation family's
+// record and spans: ev[3] stands between the move and the samples, so rc_accum_phase_ms reads
+// {move, samples} through its listed form.
+static int enqueue_scroll(DevCtx& c, const rc_scene* s, const rc_window* win, int W, int H,
+                          const rc_options* opt, const rc_sample_seq* seq, int count, int dx,
+                          int dy, const rc_accum_px* d_acc_src, const uint8_t* d_out_src,
+                          rc_accum_px* d_acc_dst, uint8_t* d_out_dst, hipStream_t stream) {
+  AccumFrame& a = c.acc;
+  const rc::ScrollRects r = rc::scroll_rects(W, H, dx, dy);
+  const int chunks = r.total ? (count + 15) / 16 : 0;
+  auto prepare = [&]() -> int {
+    if (a.count.ensure(AccumFrame::kSlots * 8)) {
+      std::fprintf(stderr, "Error: out of device memory for the pass counters\n");
+      return -1;
+    }
+    return ensure_done(a.done);
+  };
+  return ws_frame(c, stream, prepare, [&]() -> int {
+    a.valid = false;   // the block is this call's from here on
+    SampleFrame f{c, stream, kSpanAccum};
+    if (f.begin(s, &a.count, (size_t)chunks * 8)) return -1;
+    const int g = seq->grid;
+    if (r.kw > 0)
+      HIP_TRY(rc::launch_accum_move(W, H, g, dx, dy, d_acc_src, d_out_src, d_acc_dst, d_out_dst,
+                                    stream));
+    HIP_TRY(hipEventRecord(f.ev[3], stream));
+    const rc::Window vw{win->full_w, win->full_h, win->x0, win->y0};
+    const int blocks = rc::accum_exposed_blocks(r.total, c.cus, tune().adaptive_blocks);
+    for (int k = 0; k < chunks; ++k) {
+      const int n = count - 16 * k < 16 ? count - 16 * k : 16;
+      HIP_TRY(rc::launch_accum_exposed(f.ls, vw, W, H, g, dx, dy, n, seq->x + 16 * k,
+                                       seq->y + 16 * k, k == 0, opt->max_recursion, d_acc_dst,
+                                       d_out_dst, f.zc, blocks, stream,
+                                       opt->mode == RC_MODE_CUDA));
+      a.samples[k] = (uint8_t)n;
+      a.listed[k] = false;
+    }
+    if (f.end()) return -1;
+    HIP_TRY(hipEventRecord(a.done, stream));
+    a.valid = true;
+    a.passes = chunks;
+    a.pixels = (long long)r.total;
+    a.ev_first = 0;
+    a.ev_listed = true;
+    return 0;
+  });
+}
+
 // One window frame on `stream` through the device's one-frame workspace (the caller holds c.mu
 // and has passed window_refused): one launch of k_window at the options' factor.
 static int enqueue_window(DevCtx& c, const rc_scene* s, const rc_window* win, int W, int H,
@@ -932,6 +983,39 @@ int rc_accum_pass_window_device(const rc_scene* s, const rc_window* win, int W, 
   if (!win) return say("Error: %s: a null pointer\n", who);
   return accum_pass(who, s, win, W, H, opt, seq, first, count, threshold, reset, d_acc, d_out,
                     stream, timing);
+}
+
+int rc_accum_scroll_device(const rc_scene* s, const rc_window* win, int W, int H,
+                           const rc_options* opt, const rc_sample_seq* seq, int count, int dx,
+                           int dy, const rc_accum_px* d_acc_src, const uint8_t* d_out_src,
+                           rc_accum_px* d_acc_dst, uint8_t* d_out_dst, void* stream,
+                           rc_timing* timing) {
+  const char* who = "rc_accum_scroll_device";
+  if (!s || !win || !opt || !seq || !d_acc_src || !d_out_src || !d_acc_dst || !d_out_dst)
+    return say("Error: %s: a null pointer\n", who);
+  if (((uintptr_t)d_acc_src | (uintptr_t)d_acc_dst) & 7u)
+    return say("Error: %s: an accumulator is not 8-byte aligned\n", who);
+  if (accum_refused(who, opt, W, H, seq, 0, true, false)) return -1;
+  if (rc_window_check(win, W, H, seq->grid)) return -1;
+  if ((unsigned long long)W * (unsigned long long)H >= (1ull << 32))
+    return say("Error: %s: %d x %d is too large to scroll (32-bit pixel indices)\n", who, W, H);
+  if (count < 1 || count > seq->nsamples)
+    return say("Error: %s: count %d is not 1..%d (the sequence's length)\n", who, count,
+               seq->nsamples);
+  const size_t pixels = (size_t)W * H;
+  const auto overlap = [](const void* a, const void* b, size_t n) {
+    return (uintptr_t)a < (uintptr_t)b + n && (uintptr_t)b < (uintptr_t)a + n;
+  };
+  if (overlap(d_acc_src, d_acc_dst, pixels * sizeof(rc_accum_px)))
+    return say("Error: %s: the source and the destination accumulators overlap: a kept record "
+               "moves from one state to the other, keep two states and swap them\n", who);
+  if (overlap(d_out_src, d_out_dst, pixels * 3))
+    return say("Error: %s: the source and the destination images overlap: a kept pixel moves "
+               "from one state to the other, keep two states and swap them\n", who);
+  return device_entry(opt, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_scroll(c, s, win, W, H, opt, seq, count, dx, dy, d_acc_src, d_out_src,
+                          d_acc_dst, d_out_dst, st);
+  });
 }
 
 int rc_render_window_device(const rc_scene* s, const rc_window* win, int W, int H,
