@@ -25,8 +25,8 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -Wno-c11-extensions -Wno-unused-result
 CFLAGS   := -O3 -ffp-contract=off -fPIC -Wall -Wno-unused-result -Iinclude -I$(SRC)
 
-HIP_SRCS  := $(SRC)/rc_kernels.hip $(SRC)/rc_api.hip $(SRC)/rc_sampling.hip $(SRC)/rc_shard.hip $(SRC)/rc_filter.hip
-HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
+HIP_SRCS  := $(SRC)/rc_kernels.hip $(SRC)/rc_sample_kernels.hip $(SRC)/rc_api.hip $(SRC)/rc_sampling.hip $(SRC)/rc_shard.hip $(SRC)/rc_filter.hip
+HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_pixel.hpp $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
 FRONT_SRC := $(SRC)/front/parse.c $(SRC)/front/objects.c $(SRC)/front/ppm.c
 
 .PHONY: all oracle ref clean stamps stamps2 sanitize
@@ -42,9 +42,11 @@ $(OBJ)/rc_scene.o: $(SRC)/rc_scene.c $(SRC)/rc_scene.h include/raycast_hip.h
 
 ROCM    ?= /opt/rocm
 HIPLIBS := -L$(ROCM)/lib -lrccl -Wl,-rpath,$(ROCM)/lib -lpthread
-# the objects every variant of the library shares with the product: they read no build-time
-# switch (RC_STAMPS, RC_DIAG and the kernels' -D options reach rc_kernels.hip and rc_api.hip only)
-PLAIN_OBJS := $(OBJ)/rc_sampling.o $(OBJ)/rc_shard.o $(OBJ)/rc_filter.o $(OBJ)/rc_scene.o
+# the objects every variant of the library shares with the product: they are built without the
+# variants' -D options (RC_STAMPS and RC_DIAG reach rc_kernels.hip and rc_api.hip only, the kernels'
+# -D options rc_kernels.hip only: the render, parity and phase C kernels), so the sampling kernels
+# of every variant are the product's
+PLAIN_OBJS := $(OBJ)/rc_sample_kernels.o $(OBJ)/rc_sampling.o $(OBJ)/rc_shard.o $(OBJ)/rc_filter.o $(OBJ)/rc_scene.o
 
 $(LIB)/libraycast_hip.so: $(OBJ)/rc_kernels.o $(OBJ)/rc_api.o $(PLAIN_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ $(HIPLIBS)

@@ -1,4 +1,6 @@
-// rc_kernels.h — launch interface between the host runtime (rc_api.hip) and the kernels.
+// rc_kernels.h — launch interface between the host runtime (rc_api.hip, rc_sampling.hip,
+// rc_shard.hip) and the kernels: the sampling family's launchers (rc_sample_kernels.hip, and
+// rc_filter.hip's one) first, then the renderer's and the parity pipeline's (rc_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -86,11 +88,7 @@ constexpr int kCinBytes = 24;         // one carry-in = three tagged 8-byte gran
 constexpr int kLdsShapesMax = 64;     // k_resolve stages up to this many shapes in LDS
 constexpr int kDenseSlots = 64;       // k_resolve's hand-off ring (helper workgroups at most)
 
-// cuda_sem: RC_MODE_CUDA (the CUDA port's arithmetic, rc_cudasem.hpp) instead of fast mode
-hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_step, int nrows,
-                         int maxrec, uint8_t* out, unsigned long long* zcount,
-                         hipStream_t stream, bool cuda_sem = false);
-
+// ------------------------------------ defined in rc_sample_kernels.hip: the sampling family --
 // Supersampled fast mode (rc_options.ssaa = 2, 4 or 8), fused: rows row0 + k*row_step of the
 // W x H box-filtered image into `out`; the ssaa*W x ssaa*H subsample image is never stored.
 // zcount counts the zero-normalize events of every subsample.
@@ -267,6 +265,12 @@ hipError_t launch_accum_exposed(const LaunchScene& s, const Window& w, int W, in
                                 bool cuda_sem);
 // want > 0: that many; else from the CU count, at most the wave steps `exposed` pixels can need
 int accum_exposed_blocks(unsigned exposed, int cus, int want);
+
+// ------------------- defined in rc_kernels.hip: the renderer, the parity pipeline, row shards --
+// cuda_sem: RC_MODE_CUDA (the CUDA port's arithmetic, rc_cudasem.hpp) instead of fast mode
+hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_step, int nrows,
+                         int maxrec, uint8_t* out, unsigned long long* zcount,
+                         hipStream_t stream, bool cuda_sem = false);
 
 hipError_t launch_parity(const LaunchScene& s, int W, int H, int maxrec, uint8_t* out,
                          const ParityWork& w, unsigned long long* zcount, hipStream_t stream,

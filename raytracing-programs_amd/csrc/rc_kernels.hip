@@ -1,8 +1,12 @@
-// rc_kernels.hip — HIP kernels of the MI355X raycaster (gfx950).
+// rc_kernels.hip — HIP kernels of the MI355X raycaster (gfx950): the renderer and the parity
+// pipeline.  The sampling family (supersampling, patterns, accumulation, windows, scrolling) is
+// in rc_sample_kernels.hip; what the two files share is in rc_pixel.hpp.
 //
 //   k_render      one lane per pixel, 16x16-pixel workgroups (four 8x8 wave tiles for ray
 //                 coherence), full iterative_shoot + quantisation, RGB store.  Fast mode, and
 //                 parity mode at depth 0 (no bounce loop => no carry).
+//   k_render_cuda RC_MODE_CUDA: k_render's layout with the CUDA port's arithmetic
+//                 (rc_cudasem.hpp, SURVEY §8 row f4).
 //   k_classify    parity phase A, carry part: per pixel the class (ident / writer / DEP: a
 //                 pixel whose first reflection misses reads the scan-order carry), the DEP
 //                 record and the writers' carry-out — no shading.
@@ -11,24 +15,18 @@
 //   k_row_stats / k_row_scan / k_row_compact
 //                 scan-order list of the DEP pixels and the segment table (start, writer key),
 //                 one wave per row with ballot scans.
+//   k_seg_order   the segments longest first, for the resolver's queue.
 //   k_resolve     parity phase B: exact carry chain.  One workgroup per segment (dequeued
 //                 from a counter): evaluate a window of DEP pixels at the current carry in
 //                 parallel, the first pixel that changes the carry ends the step.
 //   k_side        side stream, beside the resolver: shade the non-DEP pixels, then every DEP
 //                 pixel with its resolved carry-in (parity phase C) as the carries appear.
 //   k_finish      after the resolver: whatever k_side has not claimed.
-//   k_render_cuda RC_MODE_CUDA: k_render's layout with the CUDA port's arithmetic
-//                 (rc_cudasem.hpp, SURVEY §8 row f4).
-//   k_render_ssaa fast mode with s x s supersampling: one lane per subsample, the box filter
-//                 across the lanes of a wave, one store per output pixel.
-//   k_box_down    the box filter of an s*W x s*H image in memory (parity and cuda modes).
-//   k_aa_mark / k_aa_refine
-//                 adaptive supersampling (fast and cuda modes): the list of the one-ray image's
-//                 edge pixels (3x3 contrast >= t), then the s x s subsamples of those pixels only.
-//   k_rates_render / k_rates_refine8
-//                 supersampling by the caller's per-pixel rate map (fast and cuda modes): the
-//                 rate-1 pixels and one list per factor, refined by k_aa_refine (2, 4) and by
-//                 k_rates_refine8 (8, whose list grows downwards).
+//   k_dep_chunks  phase C after the resolver has finished: the DEP entries in chunks, clean
+//                 entries stored at once and the others shaded in full waves.
+//   k_shard_pack / k_shard_rows / k_shard_unpack / k_deinterleave
+//                 row shards (rc_shard.hip): a rank's wire entries and row summaries, the
+//                 root's scan order from the gathered ones, and its image from the row blocks.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -38,16 +36,13 @@
 #include "rc_cudasem.hpp"
 #include "rc_device.hpp"
 #include "rc_kernels.h"
+#include "rc_pixel.hpp"
 
-// Which kernels use the cross-term-free quadric form (quad_x0: Scene::has_quadric == 2,
-// rc_device.hpp quad_abc) when the scene allows it.  A kernel with 0 folds has_quadric to 0/1,
-// so quad_x0 is a constant false there and the form and its branches are compiled out.
+// The parity side's build-time switches (RC_X0_PIXEL and RC_PHASE_A_WAVES, which the sampling
+// kernels read too, are in rc_pixel.hpp).
 #ifndef RC_EXP_NODEPW
 #define RC_EXP_NODEPW 0   // timing attribution build only (wrong images): phase A without its
                           // DEP record and primary-shade stores
-#endif
-#ifndef RC_X0_PIXEL
-#define RC_X0_PIXEL 1     // k_render, k_phase_a, k_classify
 #endif
 #ifndef RC_X0_PHASE_C
 #define RC_X0_PHASE_C 0   // k_dep_chunks, k_finish, k_side
@@ -55,137 +50,8 @@
 #ifndef RC_X0_RESOLVE
 #define RC_X0_RESOLVE 0   // k_resolve (its inlined phase C included)
 #endif
-#ifndef RC_PHASE_A_WAVES
-#define RC_PHASE_A_WAVES 4   // waves per SIMD the render kernels are compiled for
-#endif
 
 namespace rc {
-
-// Pixel kernels: a workgroup renders a 16x16-pixel tile of four 8x8 wave tiles (ray coherence
-// inside a wave); each lane stores its own three framebuffer bytes.  The LDS-staged form
-// (RC_TILE_STAGE=1, built as libraycast_hip_coalesced.so with 32x8 tiles) writes every tile row
-// as one 96-byte run instead: rocprofv3 WRITE_SIZE of k_render at quadric 4096^2 50.6 MB (=
-// the 50.3 MB framebuffer) against 64.0 MB for the lane stores, but k_render 0.74-0.76 ms
-// against 0.69 ms and phase A 0.93-0.96 against 0.86 ms: these kernels are VALU-
-// bound and their stores use < 1 % of HBM bandwidth, so the lane stores are the default.
-#ifndef RC_TILE_W
-#define RC_TILE_W 16
-#endif
-#ifndef RC_TILE_STAGE
-#define RC_TILE_STAGE 0   // 1: tiles staged in LDS, written as whole rows (variant)
-#endif
-constexpr int kTileW = RC_TILE_W, kTileH = 256 / RC_TILE_W;
-constexpr int kBlock = kTileW * kTileH;
-static_assert(kTileW % 8 == 0 && kTileH % 8 == 0, "8x8 wave tiles");
-
-// XCD-aware tile order (MI355X_MICROARCH.md: workgroups are dealt round-robin to the 8 XCDs,
-// each with its own L2).  With the grid's own order, horizontally adjacent tiles run on
-// different XCDs, so a 128-byte line of class bytes (8 tiles wide) or of framebuffer bytes
-// (~3 tiles) is written piecewise from several L2s and reaches HBM as partial-line writes
-// (rocprofv3 WRITE_SIZE of k_phase_a 1.26x its bytes).
-//   RC_XCD_TILES 1: XCD k takes the k-th contiguous eighth of the tiles — measured: phase A
-//                   0.745 -> 0.878 ms (the image's heavy bands land on a few XCDs);
-//   RC_XCD_TILES 2: chunks of 8 horizontally adjacent tiles per XCD, chunks dealt round-robin
-//                   (a line's tiles share one L2; the load stays interleaved).
-#ifndef RC_XCD_TILES
-#define RC_XCD_TILES 2   // measured: k_phase_a WRITE_SIZE 312 -> 269 MB in flight, time within noise
-#endif
-// order: RC_XCD_TILES for k_phase_a; k_render keeps the grid order (its only stores are the
-// framebuffer's; fast mode 0.64 ms in round 3 against 0.65-0.66 ms with chunks, r04l)
-template <int kOrder = RC_XCD_TILES>
-__device__ __forceinline__ void xcd_tile(int& bx, int& by) {
-  const int nx = gridDim.x, n = nx * (int)gridDim.y;
-  const int lin = (int)blockIdx.y * nx + (int)blockIdx.x;
-  int t = lin;
-  if (kOrder == 1) {
-    const int xcd = lin & 7, k = lin >> 3, q = n >> 3, r = n & 7;
-    // XCDs below r take q + 1 tiles, the others q: a bijection of [0, n)
-    t = xcd < r ? xcd * (q + 1) + k : r * (q + 1) + (xcd - r) * q + k;
-  } else if (kOrder == 2 && lin < (n & ~63)) {
-    // the XCD's k-th workgroup -> chunk (k / 8) * 8 + xcd, tile k % 8 of it (a bijection of
-    // the first n & ~63 tiles; the rest keep the grid order)
-    const int xcd = lin & 7, k = lin >> 3;
-    t = ((k >> 3) * 8 + xcd) * 8 + (k & 7);
-  }
-  bx = t % nx;
-  by = t / nx;
-}
-
-__device__ __forceinline__ void tile_pixel(int& lx, int& ly) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  lx = (wave % (kTileW / 8)) * 8 + (lane & 7);
-  ly = (wave / (kTileW / 8)) * 8 + (lane >> 3);
-}
-
-// A tile's framebuffer bytes (and, for phase A, its class bytes) staged in LDS: every lane
-// drops its 3 (1) bytes in, then the workgroup writes each row of the tile as one contiguous
-// run — dword stores when the run is whole and 4-byte aligned (W % 4 == 0), bytes otherwise —
-// instead of three byte stores per lane into 8-pixel row fragments (the store
-// north_star names is the coalesced one; C/raycast.c:122-127 is the store replaced).
-struct TileBytes {
-  uint32_t rgb[kTileH][kTileW * 3 / 4];
-  uint32_t cls[kTileH][kTileW / 4];
-  int done;   // waves that have staged their pixels
-};
-
-// Zeroes the wave counter; the caller's next barrier publishes it.
-__device__ __forceinline__ void tile_init(TileBytes& t) {
-  if (threadIdx.x == 0) t.done = 0;
-}
-
-// No workgroup barrier before the row writes (waiting for the slowest wave of a tile held the
-// others' slots: measured +7 % on k_render): each wave releases its staged bytes and counts
-// itself in; the LAST wave of the tile writes every row and the others simply end.
-__device__ __forceinline__ bool tile_last_wave(TileBytes& t) {
-  if (!RC_TILE_STAGE) return false;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  int old = 0;
-  if ((threadIdx.x & 63) == 0)
-    old = __hip_atomic_fetch_add(&t.done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-  old = __shfl(old, 0, 64);
-  if (old != kBlock / 64 - 1) return false;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  return true;
-}
-
-__device__ __forceinline__ void tile_put_rgb(TileBytes& t, int lx, int ly, uint8_t r, uint8_t g,
-                                             uint8_t b, uint8_t* direct) {
-  if (!RC_TILE_STAGE) {   // the default: the lane's own three byte stores
-    direct[0] = r;
-    direct[1] = g;
-    direct[2] = b;
-    return;
-  }
-  uint8_t* q = (uint8_t*)t.rgb[ly] + lx * 3;
-  q[0] = r;
-  q[1] = g;
-  q[2] = b;
-}
-
-// Row ly of the tile goes to dst_row(ly) (nullptr: the row is outside the image), nbytes
-// valid bytes per row.  The tile's last wave calls this (tile_last_wave).
-template <int kWords, typename RowPtr>
-__device__ __forceinline__ void tile_write_rows(const uint32_t (*src)[kWords], RowPtr dst_row,
-                                                int nbytes) {
-  const int t = threadIdx.x & 63;   // one wave writes the tile (tile_last_wave)
-  for (int i = t; i < kTileH * kWords; i += 64) {
-    const int ly = i / kWords, k = i % kWords;
-    uint8_t* d = dst_row(ly);
-    if (!d) continue;
-    if (nbytes == kWords * 4 && ((uintptr_t)d & 3u) == 0u) {
-      ((uint32_t*)d)[k] = src[ly][k];
-    } else {
-      const uint8_t* sb = (const uint8_t*)src[ly];
-      for (int b = k * 4; b < k * 4 + 4 && b < nbytes; ++b) d[b] = sb[b];
-    }
-  }
-}
-
-__device__ __forceinline__ void store_rgb(uint8_t* __restrict__ p, V3 c) {
-  p[0] = quant(c.x);
-  p[1] = quant(c.y);
-  p[2] = quant(c.z);
-}
 
 // Phase C's store of DEP entry j at pixel p: the framebuffer, and — when the host is copying
 // the framebuffer out while the resolver runs (rc_render) — the entry's packed RGB in `patch`,
@@ -200,45 +66,6 @@ __device__ __forceinline__ void store_dep(uint8_t* __restrict__ out, uint32_t* _
   q[1] = g;
   q[2] = b;
   if (patch) patch[j] = patch_mark(tag) | (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
-}
-
-__device__ __forceinline__ void flush_events(int zero_events, unsigned long long* counter) {
-  if (zero_events) atomicAdd(counter, (unsigned long long)zero_events);
-}
-
-// The pixel kernels' divergent record reads (the winner's frame, shading record and colour
-// pairs: Scene::lshapes / lpairs) come from an LDS copy of the scene when it is small
-// enough: an LDS read instead of a vector-memory round trip per lane.  The
-// uniform loops over shapes and lights keep their scalar loads.
-constexpr int kStageShapes = 32;   // shape records, phantom included
-constexpr int kStagePairs = 128;   // (shape, light) colour pairs
-struct SceneStage {
-  rc_shape shapes[kStageShapes];
-  rc_shade_pair pairs[kStagePairs];
-};
-template <bool kStage>
-struct StageBuf {
-  SceneStage s;
-};
-template <>
-struct StageBuf<false> {
-  int unused;
-};
-
-// Every thread of the workgroup must call this (it has a barrier).
-template <bool kStage>
-__device__ __forceinline__ void stage_scene(Scene& sc, StageBuf<kStage>& buf) {
-  if constexpr (kStage) {
-    const int ws = (int)(sizeof(rc_shape) / 4) * (sc.n + 1);
-    for (int i = threadIdx.x; i < ws; i += blockDim.x)
-      ((unsigned*)buf.s.shapes)[i] = ((const unsigned*)sc.shapes)[i];
-    const int wp = (int)(sizeof(rc_shade_pair) / 4) * (sc.n + 1) * sc.m;
-    for (int i = threadIdx.x; i < wp; i += blockDim.x)
-      ((unsigned*)buf.s.pairs)[i] = ((const unsigned*)sc.pairs)[i];
-    __syncthreads();
-    sc.lshapes = buf.s.shapes;
-    sc.lpairs = buf.s.pairs;
-  }
 }
 
 // ------------------------------------------------------------------ fast / depth 0 --
@@ -277,131 +104,6 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
   }, nx * 3);
 }
 
-// ---------------------------------------- one subsample, for the supersampling kernels --
-// The quantised channels of subsample (xs, ys) of the image whose camera is `cam`, in fast
-// mode's arithmetic or (kCuda) the CUDA port's (k_render_cuda's pixel routine), packed for the
-// sums below: R | G << 16 and B (a channel's sum over a wave is <= 64 * 255).
-template <bool kCuda>
-__device__ __forceinline__ void sample_shoot(const Scene& sc, const Cam& cam, int xs, int ys,
-                                             int maxrec, unsigned long long* __restrict__ zcount,
-                                             unsigned& rg, unsigned& b) {
-  V3 c;
-  if constexpr (kCuda) {
-    c = cusem::render_pixel(sc, cam, xs, ys, maxrec - 1);
-  } else {
-    int zero = 0;
-    const V3 d = primary_dir(cam, xs, ys, zero);
-    PixelOut po;
-    shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
-    c = po.rgb;
-    flush_events(zero, zcount);
-  }
-  rg = (unsigned)quant(c.x) | ((unsigned)quant(c.y) << 16);
-  b = quant(c.z);
-}
-// The sums over the 1 << ln lanes of a group (xor butterflies over the lane bits 1 .. n/2).
-// Called by every lane of the wave.
-__device__ __forceinline__ void sample_reduce(unsigned& rg, unsigned& b, int ln) {
-  for (int m = 1; m < (1 << ln); m <<= 1) {
-    rg += __shfl_xor(rg, m, 64);
-    b += __shfl_xor(b, m, 64);
-  }
-}
-// The rounded mean of 1 << ln samples, (sum + n/2) >> ln per channel, stored at q.
-__device__ __forceinline__ void sample_store(uint8_t* __restrict__ q, unsigned rg, unsigned b,
-                                             int ln) {
-  const unsigned half = 1u << (ln - 1);
-  q[0] = (uint8_t)(((rg & 0xffffu) + half) >> ln);
-  q[1] = (uint8_t)(((rg >> 16) + half) >> ln);
-  q[2] = (uint8_t)((b + half) >> ln);
-}
-
-// ------------------------------------------------- fast mode, supersampled (ssaa) --
-// k_render over the subsample grid of an s x s supersampled image (s = 1 << ls; 2, 4 or 8):
-// one lane shoots one subsample with the camera of the s*W x s*H image, the same tiles as
-// k_render in subsample coordinates.  lane = 8 * row + col inside a wave tile and s divides 8,
-// so the s x s subsamples of an output pixel are lanes of one wave: their quantised channels
-// are summed with xor butterflies over the column bits (1 .. s/2) and the row bits (8 .. 4s),
-// and the group's first lane stores the rounded mean, (sum + s*s/2) / (s*s).  The subsample
-// image is never written.  W, nrows, row0 and row_step are in output pixels: output row r
-// covers subsample rows s * (row0 + r * row_step) + j, j < s.
-// Tile origins are multiples of 8 subsamples, so a group is wholly inside the image or wholly
-// outside it: outside lanes skip shoot, add zeros in the butterflies (which every lane of the
-// wave executes) and store nothing.
-template <bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_render_ssaa(
-    Scene sc, Cam cam, int W, int ls, int row0, int row_step, int nrows, int maxrec,
-    uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount) {
-  if (!RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // no cross-term-free form here (RC_X0_*)
-  __shared__ StageBuf<kStage> stage;
-  stage_scene<kStage>(sc, stage);
-  int lx, ly;
-  tile_pixel(lx, ly);
-  int bx, by;
-  xcd_tile<0>(bx, by);
-  const int s = 1 << ls;
-  const int xs = bx * kTileW + lx;   // subsample column
-  const int rs = by * kTileH + ly;   // subsample row of the local (shard) rows
-  // only xs and rs stay live across shoot (k_render's x and r): the output pixel, the bounds
-  // test and the group's first lane all follow from them
-  const bool inside = (xs >> ls) < W && (rs >> ls) < nrows;
-  unsigned rg = 0u, b = 0u;          // R | G << 16 and B: a channel's sum is <= 64 * 255
-  if (inside) {
-    const int y = ((row0 + (rs >> ls) * row_step) << ls) + (rs & (s - 1));
-    int zero = 0;
-    const V3 d = primary_dir(cam, xs, y, zero);
-    PixelOut po;
-    shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
-    rg = (unsigned)quant(po.rgb.x) | ((unsigned)quant(po.rgb.y) << 16);
-    b = quant(po.rgb.z);
-    flush_events(zero, zcount);
-  }
-  for (int m = 1; m < s; m <<= 1) {       // columns of the group
-    rg += __shfl_xor(rg, m, 64);
-    b += __shfl_xor(b, m, 64);
-  }
-  for (int m = 8; m < 8 * s; m <<= 1) {   // rows of the group
-    rg += __shfl_xor(rg, m, 64);
-    b += __shfl_xor(b, m, 64);
-  }
-  // the group's first lane (tile origins are multiples of 8, so of s)
-  if (inside && ((xs | rs) & (s - 1)) == 0) {
-    const unsigned half = 1u << (2 * ls - 1);
-    const int x = xs >> ls, r = rs >> ls;   // r: local (shard) output row
-    uint8_t* p = out + ((size_t)r * W + x) * 3;
-    p[0] = (uint8_t)(((rg & 0xffffu) + half) >> (2 * ls));
-    p[1] = (uint8_t)(((rg >> 16) + half) >> (2 * ls));
-    p[2] = (uint8_t)((b + half) >> (2 * ls));
-  }
-}
-
-// Box filter of the two-pass path (parity and cuda modes, whose s*W x s*H image exists in
-// memory): dst pixel (x, y) = the rounded mean of src's s x s block at (s*x, s*y), per channel,
-// (sum + s*s/2) / (s*s).  One thread per output pixel; src is (s*W) x (s*H), dst W x H.
-__global__ void __launch_bounds__(256) k_box_down(const uint8_t* __restrict__ src, int W, int H,
-                                                  int ls, uint8_t* __restrict__ dst) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)W * H) return;
-  const int s = 1 << ls;
-  const size_t y = i / (size_t)W, x = i % (size_t)W;
-  const size_t srow = (size_t)W * s * 3;
-  const uint8_t* p = src + y * s * srow + x * s * 3;
-  unsigned r = 0u, g = 0u, b = 0u;
-  for (int j = 0; j < s; ++j) {
-    const uint8_t* q = p + (size_t)j * srow;
-    for (int k = 0; k < s; ++k) {
-      r += q[3 * k];
-      g += q[3 * k + 1];
-      b += q[3 * k + 2];
-    }
-  }
-  const unsigned half = 1u << (2 * ls - 1);
-  uint8_t* d = dst + i * 3;
-  d[0] = (uint8_t)((r + half) >> (2 * ls));
-  d[1] = (uint8_t)((g + half) >> (2 * ls));
-  d[2] = (uint8_t)((b + half) >> (2 * ls));
-}
-
 // ------------------------------------------------------- CUDA-port semantics (f4) --
 // One lane per pixel like k_render; up to maxrec - 1 bounces (MAX_ITER, CUDA/raycast.cu:13).
 template <bool kStage>
@@ -417,429 +119,6 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
   if (x >= W || r >= nrows) return;
   const V3 c = cusem::render_pixel(sc, cam, x, row0 + r * row_step, maxrec - 1);
   store_rgb(out + ((size_t)r * W + x) * 3, c);
-}
-
-// ------------------------------------------- adaptive supersampling (fast, cuda) --
-// rc_options.ssaa = RC_SSAA_ADAPTIVE(s, t): the one-ray image A is rendered into `out` by
-// k_render / k_render_cuda, k_aa_mark lists the pixels of A whose 3x3 contrast reaches t, and
-// k_aa_refine shoots the s x s subsamples of the listed pixels only and stores their box filter
-// over A's pixel.  Mark reads neighbours that refine overwrites, so the two are separate
-// launches on one stream: the list is complete before the first refined store.
-//
-// k_aa_mark: one lane per pixel.  A workgroup is four waves side by side, each taking 64 adjacent
-// columns of kMarkRows rows of tile (tx, ty) (the tile index is divided once per workgroup, in
-// scalars).  A wave walks down its rows with a rolling window of three: of every row it loads
-// each lane's own pixel once (packed R | G << 8 | B << 16), takes the left and right neighbours
-// from the adjacent lanes, and only lanes 0 and 63 load the pixel beyond the wave, so a pixel
-// costs 3 * (kMarkRows + 2) / kMarkRows byte loads instead of 27.  Coordinates are clamped to
-// the image: a clamped neighbour is a pixel of the window taken twice, which changes neither max
-// nor min.  List slots are reserved per wave: a ballot of the flagged lanes of every row, one
-// atomicAdd of their popcounts' sum by lane 0, and each flagged lane writes at base + the flagged
-// pixels of the rows above + the popcount of the flagged lanes below it in its row.  Every lane
-// of a wave reaches the shuffles and the ballots (lanes past the image load and flag nothing;
-// skipping a row past the image is uniform).  The list's order follows
-// the atomics' arrival and is not deterministic; no output byte depends on it.
-constexpr int kMarkBlock = 256, kMarkRows = 8;
-struct MarkRow {
-  int lo[3], hi[3];   // per channel, over the pixel and its two neighbours in the row
-};
-__device__ __forceinline__ unsigned mark_load(const uint8_t* __restrict__ q) {
-  return (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
-}
-// in: x < W.  y < H.  Called by every lane of the wave.
-__device__ __forceinline__ MarkRow mark_row(const uint8_t* __restrict__ img, unsigned W, unsigned x,
-                                            unsigned y, int lane, bool in) {
-  const uint8_t* q = img + (size_t)y * W * 3;
-  const unsigned v = in ? mark_load(q + (size_t)x * 3) : 0u;
-  unsigned l = __shfl_up(v, 1, 64), r = __shfl_down(v, 1, 64);
-  if (in) {
-    if (x == 0u) l = v;
-    else if (lane == 0) l = mark_load(q + (size_t)(x - 1u) * 3);
-    if (x + 1u >= W) r = v;
-    else if (lane == 63) r = mark_load(q + (size_t)(x + 1u) * 3);
-  }
-  MarkRow m;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int a = (int)((v >> (8 * c)) & 255u), b = (int)((l >> (8 * c)) & 255u),
-              d = (int)((r >> (8 * c)) & 255u);
-    const int lo = a < b ? a : b, hi = a > b ? a : b;
-    m.lo[c] = lo < d ? lo : d;
-    m.hi[c] = hi > d ? hi : d;
-  }
-  return m;
-}
-__global__ void __launch_bounds__(kMarkBlock) k_aa_mark(const uint8_t* __restrict__ img, int W,
-                                                        int H, unsigned tiles_x, int thr,
-                                                        uint32_t* __restrict__ list,
-                                                        unsigned* __restrict__ count) {
-  const unsigned ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
-  const int lane = threadIdx.x & 63;
-  const unsigned x = tx * kMarkBlock + threadIdx.x;   // tx * 256 < W + 256 <= 2^31 + 255
-  const unsigned y0 = ty * kMarkRows, w = (unsigned)W, h = (unsigned)H;   // y0 < H
-  const bool in = x < w;
-  MarkRow p = mark_row(img, w, x, y0 > 0u ? y0 - 1u : 0u, lane, in);
-  MarkRow c = mark_row(img, w, x, y0, lane, in);
-  unsigned long long flagged[kMarkRows];   // per row, the ballot of its flagged lanes (uniform)
-  unsigned total = 0u;
-#pragma unroll
-  for (int k = 0; k < kMarkRows; ++k) {
-    const unsigned y = y0 + (unsigned)k;
-    flagged[k] = 0ull;
-    if (y >= h) continue;   // uniform
-    const MarkRow n = mark_row(img, w, x, y + 1u < h ? y + 1u : y, lane, in);
-    int con = 0;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      int lo = p.lo[ch] < c.lo[ch] ? p.lo[ch] : c.lo[ch];
-      int hi = p.hi[ch] > c.hi[ch] ? p.hi[ch] : c.hi[ch];
-      lo = n.lo[ch] < lo ? n.lo[ch] : lo;
-      hi = n.hi[ch] > hi ? n.hi[ch] : hi;
-      con = hi - lo > con ? hi - lo : con;
-    }
-    flagged[k] = __ballot(in && con >= thr);
-    total += (unsigned)__popcll(flagged[k]);
-    p = c;
-    c = n;
-  }
-  // one reservation per wave for all its rows: the atomics all hit one address
-  unsigned base = 0u;
-  if (lane == 0 && total) base = atomicAdd(count, total);
-  base = __shfl(base, 0, 64);
-#pragma unroll
-  for (int k = 0; k < kMarkRows; ++k) {
-    const unsigned long long m = flagged[k];
-    if ((m >> lane) & 1ull)   // y*W + x < W*H < 2^32 (launch_aa_mark)
-      list[base + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] =
-          (uint32_t)((size_t)(y0 + (unsigned)k) * w + x);
-    base += (unsigned)__popcll(m);
-  }
-}
-
-// k_aa_refine: over the list, not the image.  A wave serves 64 / (s*s) listed pixels per step
-// (s = 1 << ls: 16, 4 or 1): lane l belongs to group l / (s*s) and shoots subsample
-// (i, j) = ((l % (s*s)) % s, (l % (s*s)) / s) of its group's pixel (x, y), that is the pixel
-// (s*x + i, s*y + j) of the s*W x s*H image with that image's camera (`cam`), exactly as
-// k_render_ssaa / the two-pass path do, so every subsample byte is that image's byte.  The
-// quantised channels are summed over the group with xor butterflies over the lane bits
-// 1 .. s*s/2 and the group's first lane stores (sum + s*s/2) / (s*s) over A's pixel.
-// The list's length is read from device memory (k_aa_mark's counter) and the grid is a fixed
-// number of workgroups whose waves stride over the list, so the host never waits between mark
-// and refine.  A wave's trip count depends on the wave alone, so all its lanes execute every
-// butterfly; lanes past the list's end shoot nothing, add zeros and store nothing.
-// kCuda: the CUDA port's arithmetic (k_render_cuda's pixel routine) instead of fast mode.
-template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_aa_refine(
-    Scene sc, Cam cam, int W, int ls, int maxrec, const uint32_t* __restrict__ list,
-    const unsigned* __restrict__ count, uint8_t* __restrict__ out,
-    unsigned long long* __restrict__ zcount) {
-  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
-  __shared__ StageBuf<kStage> stage;
-  stage_scene<kStage>(sc, stage);   // its barrier comes before the loop: every thread is here
-  const unsigned n = *count;
-  const int lane = threadIdx.x & 63;
-  const unsigned per = 64u >> (2 * ls);                    // listed pixels per wave step
-  const unsigned sub = (unsigned)lane & ((1u << (2 * ls)) - 1u);   // subsample within the group
-  // wave-uniform by construction: told to the compiler, so the loop's counters stay scalar
-  const unsigned wave =
-      __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
-  const unsigned step = gridDim.x * (kBlock / 64) * per;   // <= 4096 * 4 * 16
-  // 64-bit index: n + step may pass 2^32
-  for (unsigned long long first = (unsigned long long)wave * per; first < n; first += step) {
-    const unsigned long long k = first + ((unsigned)lane >> (2 * ls));
-    const bool live = k < n;
-    unsigned p = 0u, rg = 0u, b = 0u;   // R | G << 16 and B: a channel's sum is <= 64 * 255
-    if (live) {
-      p = list[k];
-      const int xs = (int)((p % (unsigned)W) << ls) + (int)(sub & ((1u << ls) - 1u));
-      const int ys = (int)((p / (unsigned)W) << ls) + (int)(sub >> ls);
-      sample_shoot<kCuda>(sc, cam, xs, ys, maxrec, zcount, rg, b);
-    }
-    sample_reduce(rg, b, 2 * ls);
-    if (live && sub == 0u) {
-      // the entry is read again (opaque index) rather than kept in a register across shoot,
-      // where the kernel sits at the 128-register edge
-      unsigned g = (unsigned)lane >> (2 * ls);
-      asm volatile("" : "+v"(g));
-      p = list[first + g];
-      sample_store(out + (size_t)p * 3, rg, b, 2 * ls);
-    }
-  }
-}
-
-// ---------------------------------------- rate-map supersampling (fast, cuda) --
-// rc_render_rates*: the caller's map gives every pixel a rate in {0, 1, 2, 4, 8} (one byte per
-// pixel, row-major): 0 leaves the pixel's bytes alone, 1 is the one-ray pixel, s > 1 the ssaa = s
-// pixel.  k_rates_render shoots the rate-1 pixels and bins the others into one list per factor;
-// k_aa_refine (rates 2 and 4) and k_rates_refine8 then shoot the listed pixels' subsamples.  No
-// pixel is in two classes and nobody reads a pixel, so the stream order of the launches is all
-// the ordering there is.
-//
-// k_rates_render: k_render's grid and tiles (one lane per pixel) for the rate-1 pixels.  The
-// binning comes first, so nothing of it is live across shoot, and it does not follow the tiles:
-// the map is cut into chunks of kRateChunk * 256 consecutive pixels (row-major, so the byte loads
-// are contiguous) and one workgroup in every kRateChunk takes a chunk, so a class's counter gets
-// one atomicAdd per chunk and not one per wave (same-address atomics were what the first form's
-// time followed).  The chunk's workgroup counts first: per wave and step
-// a ballot per class, the waves' sums through LDS, one atomicAdd per class by one thread; then it
-// reads the chunk again and every flagged lane writes its pixel index y*W + x at the class's base
-// + the flagged pixels of the waves and steps before it + the popcount of the flagged lanes below
-// it (k_aa_mark's reservation, one level up).  Every lane of a wave reaches the ballots; lanes
-// past the map flag nothing.  The duty rotates over the eight residues of the workgroup index, so
-// it does not fall on one XCD.  cnt: [0] [1] [2] the lengths of the rate-2, rate-4 and rate-8
-// lists, [3] the rate-1 pixels, [4] the map bytes that are no rate (those pixels are left alone,
-// like rate 0).  The rate-2 list grows upwards from list2up, the rate-8 list downwards from
-// list8down (the two ends of one W*H-entry buffer: together they never hold more than W*H
-// entries), the rate-4 list upwards from list4.
-// A workgroup without a rate-1 pixel ends before stage_scene; the decision is one
-// __syncthreads_or, so stage_scene's barrier stays uniform.  A rate-1 lane stores its own three
-// bytes: a wider store would write into a neighbour that may have rate 0.
-constexpr int kRateChunk = 8;   // tiles' worth of pixels per binning workgroup (a power of two)
-template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_rates_render(
-    Scene sc, Cam cam, int W, int H, int maxrec, const uint8_t* __restrict__ rates,
-    uint8_t* __restrict__ out, uint32_t* __restrict__ list2up, uint32_t* __restrict__ list4,
-    uint32_t* __restrict__ list8down, unsigned* __restrict__ cnt,
-    unsigned long long* __restrict__ zcount) {
-  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
-  __shared__ StageBuf<kStage> stage;
-  __shared__ unsigned wsum[kBlock / 64][5];   // per wave: the chunk's pixels per counter of cnt
-  __shared__ unsigned wbase[3];               // the chunk's first slot in each list
-  {
-    const int lin = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
-    const int nwg = (int)gridDim.x * (int)gridDim.y;
-    const int chunk = lin / kRateChunk;
-    int duty = chunk % kRateChunk;   // which workgroup of the chunk's kRateChunk bins it
-    if (chunk * kRateChunk + duty >= nwg) duty = 0;
-    if (lin % kRateChunk == duty) {   // uniform over the workgroup: the barriers below are too
-      const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-      const unsigned long long below = (1ull << lane) - 1ull;
-      const size_t n = (size_t)W * H;   // < 2^32; the grid's workgroups * 256 >= n
-      const size_t first = (size_t)chunk * (kRateChunk * kBlock) + threadIdx.x;
-      unsigned tot[5] = {0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int it = 0; it < kRateChunk; ++it) {
-        const size_t i = first + (size_t)it * kBlock;
-        const unsigned rate = i < n ? (unsigned)rates[i] : 0u;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) tot[k] += (unsigned)__popcll(__ballot(rate == (2u << k)));
-        tot[3] += (unsigned)__popcll(__ballot(rate == 1u));
-        tot[4] += (unsigned)__popcll(__ballot(!(rate <= 2u || rate == 4u || rate == 8u)));
-      }
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) wsum[wave][k] = tot[k];
-      }
-      __syncthreads();
-      if (threadIdx.x < 5) {
-        unsigned sum = 0u;
-        for (int w = 0; w < kBlock / 64; ++w) sum += wsum[w][threadIdx.x];
-        unsigned base = 0u;
-        if (sum) base = atomicAdd(cnt + threadIdx.x, sum);
-        if (threadIdx.x < 3) wbase[threadIdx.x] = base;
-      }
-      __syncthreads();
-      unsigned base[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        base[k] = wbase[k];
-        for (int w = 0; w < wave; ++w) base[k] += wsum[w][k];
-      }
-      if (tot[0] | tot[1] | tot[2]) {   // uniform over the wave
-#pragma unroll
-        for (int it = 0; it < kRateChunk; ++it) {
-          const size_t i = first + (size_t)it * kBlock;
-          const unsigned rate = i < n ? (unsigned)rates[i] : 0u;
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            const unsigned long long m = __ballot(rate == (2u << k));
-            if ((m >> lane) & 1ull) {   // i < n: a pixel index below 2^32
-              const size_t at = (size_t)base[k] + (unsigned)__popcll(m & below);
-              if (k == 0) list2up[at] = (uint32_t)i;
-              else if (k == 1) list4[at] = (uint32_t)i;
-              else *(list8down - at) = (uint32_t)i;
-            }
-            base[k] += (unsigned)__popcll(m);
-          }
-        }
-      }
-    }
-  }
-  int lx, ly;
-  tile_pixel(lx, ly);
-  int bx, by;
-  xcd_tile<0>(bx, by);
-  const int x = bx * kTileW + lx;
-  const int y = by * kTileH + ly;
-  const bool one = x < W && y < H && rates[(size_t)y * W + x] == 1;
-  if (!__syncthreads_or(one ? 1 : 0)) return;   // uniform: no rate-1 pixel in this tile
-  stage_scene<kStage>(sc, stage);
-  if (!one) return;
-  V3 c;
-  if constexpr (kCuda) {
-    c = cusem::render_pixel(sc, cam, x, y, maxrec - 1);
-  } else {
-    int zero = 0;
-    const V3 d = primary_dir(cam, x, y, zero);
-    PixelOut po;
-    shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
-    c = po.rgb;
-    flush_events(zero, zcount);
-  }
-  store_rgb(out + ((size_t)y * W + x) * 3, c);
-}
-
-// k_rates_refine8: k_aa_refine at s = 8 over a list that grows downwards (entry k is
-// last[-k]): a wave serves one listed pixel per step, lane l shoots subsample (l % 8, l / 8) of
-// it with the camera of the 8*W x 8*H image, the quantised channels are summed over the wave
-// with xor butterflies and lane 0 stores (sum + 32) / 64.  The entry is wave-uniform and stays
-// in a scalar register across shoot.  The list's length is read on the device; the grid is a
-// fixed number of workgroups whose waves stride over the list.
-template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_rates_refine8(
-    Scene sc, Cam cam, int W, int maxrec, const uint32_t* __restrict__ last,
-    const unsigned* __restrict__ count, uint8_t* __restrict__ out,
-    unsigned long long* __restrict__ zcount) {
-  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
-  __shared__ StageBuf<kStage> stage;
-  const unsigned n = *count;
-  if (n == 0u) return;   // uniform over the grid: an empty list costs its launch
-  stage_scene<kStage>(sc, stage);
-  const int lane = threadIdx.x & 63;
-  const unsigned wave =
-      __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
-  const unsigned step = gridDim.x * (kBlock / 64);
-  // 64-bit index: n + step may pass 2^32
-  for (unsigned long long k = wave; k < n; k += step) {
-    const unsigned p = __builtin_amdgcn_readfirstlane(*(last - (size_t)k));
-    const int xs = (int)((p % (unsigned)W) << 3) + (lane & 7);
-    const int ys = (int)((p / (unsigned)W) << 3) + (lane >> 3);
-    V3 c;
-    if constexpr (kCuda) {
-      c = cusem::render_pixel(sc, cam, xs, ys, maxrec - 1);
-    } else {
-      int zero = 0;
-      const V3 d = primary_dir(cam, xs, ys, zero);
-      PixelOut po;
-      shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero);
-      c = po.rgb;
-      flush_events(zero, zcount);
-    }
-    unsigned rg = (unsigned)quant(c.x) | ((unsigned)quant(c.y) << 16);   // sums <= 64 * 255
-    unsigned b = quant(c.z);
-    for (int m = 1; m < 64; m <<= 1) {
-      rg += __shfl_xor(rg, m, 64);
-      b += __shfl_xor(b, m, 64);
-    }
-    if (lane == 0) {
-      uint8_t* q = out + (size_t)p * 3;
-      q[0] = (uint8_t)(((rg & 0xffffu) + 32u) >> 6);
-      q[1] = (uint8_t)(((rg >> 16) + 32u) >> 6);
-      q[2] = (uint8_t)((b + 32u) >> 6);
-    }
-  }
-}
-
-// ------------------------------------- sparse sample patterns (fast, cuda) --
-// rc_render_pattern*: n samples of a pixel on its g x g subsample lattice (rc_pattern in
-// include/raycast_hip.h; g = 1 << lg in {2, 4, 8}, n = 1 << ln in {2, 4, 8, 16}).  Sample k of
-// pixel (x, y) is pixel (g*x + px[k], g*y + py[k]) of the g*W x g*H image, shot with that image's
-// camera (`cam`) exactly as k_render_ssaa and k_aa_refine shoot theirs, so every sample byte is
-// that image's byte; the image itself is never stored.
-// Lane l of a wave belongs to pixel group l / n and shoots sample l % n.  The pattern travels as
-// two 64-bit words of 4-bit entries (entry k in bits 4k .. 4k+3 of PatWords::x and ::y), kernel
-// arguments held in scalar registers: a lane takes its own entry with one shift, no table in
-// memory or LDS.  The quantised channels are summed over the group with xor butterflies over the
-// lane bits 1 .. n/2, packed R | G << 16 and B (a channel's sum is <= 16 * 255), and the group's
-// first lane stores (sum + n/2) >> ln.  Every lane of a wave executes every butterfly; lanes whose
-// group is outside the image or past the list shoot nothing, add zeros and store nothing.  A
-// group's lanes share one pixel, so a group is wholly inside or wholly outside.
-struct PatWords {
-  unsigned long long x, y;
-};
-__device__ __forceinline__ int pat_entry(unsigned long long word, unsigned k) {
-  return (int)((word >> (4u * k)) & 15ull);
-}
-
-// The wave block of the dense form: a wave's 64 / n pixels are a compact bw x bh block,
-//   n = 2: 8 x 4    n = 4: 4 x 4    n = 8: 4 x 2    n = 16: 2 x 2     (bw >= bh, both powers of two)
-// and a workgroup's four waves sit 2 x 2, so a workgroup owns a tile of 2*bw x 2*bh = 256 / n
-// output pixels: 16 x 8, 8 x 8, 8 x 4, 4 x 4.
-__host__ __device__ constexpr int pat_lbw(int ln) { return (7 - ln) / 2; }   // log2 bw
-__host__ __device__ constexpr int pat_lbh(int ln) { return (6 - ln) / 2; }   // log2 bh
-static_assert(pat_lbw(1) == 3 && pat_lbh(1) == 2 && pat_lbw(2) == 2 && pat_lbh(2) == 2 &&
-              pat_lbw(3) == 2 && pat_lbh(3) == 1 && pat_lbw(4) == 1 && pat_lbh(4) == 1,
-              "a wave's 64 / n pixels");
-
-// Dense form (threshold 0): every pixel of the image, one workgroup per tile, the tiles taken
-// through xcd_tile in the grid's own order like k_render's.  The tiles are small, so a 128-byte
-// line of the framebuffer spans several of them, but k_phase_a's order (chunks of 8 horizontally
-// adjacent tiles share an L2) measured slower at every n (quadric, rgss4: 1024^2 0.189 against
-// 0.176 ms, 2048^2 0.659 against 0.635 ms), as it did for k_render.
-template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_pattern(
-    Scene sc, Cam cam, int W, int H, int lg, int ln, PatWords pat, int maxrec,
-    uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount) {
-  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
-  __shared__ StageBuf<kStage> stage;
-  stage_scene<kStage>(sc, stage);
-  int bx, by;
-  xcd_tile<0>(bx, by);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lbw = pat_lbw(ln), lbh = pat_lbh(ln);
-  const int grp = lane >> ln;                                    // the wave's pixel group
-  const unsigned k = (unsigned)lane & ((1u << ln) - 1u);         // the lane's sample
-  const int x = (((bx << 1) + (wave & 1)) << lbw) + (grp & ((1 << lbw) - 1));
-  const int y = (((by << 1) + (wave >> 1)) << lbh) + (grp >> lbw);
-  const bool inside = x < W && y < H;
-  unsigned rg = 0u, b = 0u;
-  if (inside)
-    sample_shoot<kCuda>(sc, cam, (x << lg) + pat_entry(pat.x, k), (y << lg) + pat_entry(pat.y, k),
-                     maxrec, zcount, rg, b);
-  sample_reduce(rg, b, ln);
-  if (inside && k == 0u) sample_store(out + ((size_t)y * W + x) * 3, rg, b, ln);
-}
-
-// List form (threshold t > 0): over k_aa_mark's list like k_aa_refine, 64 / n listed pixels per
-// wave step; the list's length is read from device memory and the grid is a fixed number of
-// workgroups whose waves stride over the list.  A wave's trip count depends on the wave alone.
-template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_pattern_list(
-    Scene sc, Cam cam, int W, int lg, int ln, PatWords pat, int maxrec,
-    const uint32_t* __restrict__ list, const unsigned* __restrict__ count,
-    uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount) {
-  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
-  __shared__ StageBuf<kStage> stage;
-  const unsigned n = *count;
-  if (n == 0u) return;   // uniform over the grid: an empty list costs its launch
-  stage_scene<kStage>(sc, stage);   // its barrier comes before the loop: every thread is here
-  const int lane = threadIdx.x & 63;
-  const unsigned per = 64u >> ln;                              // listed pixels per wave step
-  const unsigned k = (unsigned)lane & ((1u << ln) - 1u);       // the lane's sample
-  const int px = pat_entry(pat.x, k), py = pat_entry(pat.y, k);
-  // wave-uniform by construction: told to the compiler, so the loop's counters stay scalar
-  const unsigned wave =
-      __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
-  const unsigned step = gridDim.x * (kBlock / 64) * per;   // <= 4096 * 4 * 32
-  // 64-bit index: n + step may pass 2^32
-  for (unsigned long long first = (unsigned long long)wave * per; first < n; first += step) {
-    const unsigned long long e = first + ((unsigned)lane >> ln);
-    const bool live = e < n;
-    unsigned rg = 0u, b = 0u;
-    if (live) {
-      const unsigned p = list[e];
-      sample_shoot<kCuda>(sc, cam, (int)((p % (unsigned)W) << lg) + px,
-                       (int)((p / (unsigned)W) << lg) + py, maxrec, zcount, rg, b);
-    }
-    sample_reduce(rg, b, ln);
-    if (live && k == 0u) {
-      // the entry is read again (opaque index) rather than kept in a register across shoot, as
-      // in k_aa_refine
-      unsigned g = (unsigned)lane >> ln;
-      asm volatile("" : "+v"(g));
-      sample_store(out + (size_t)list[first + g] * 3, rg, b, ln);
-    }
-  }
 }
 
 // ------------------------------------------------------------------ parity phase A --
@@ -3544,50 +2823,6 @@ __global__ void __launch_bounds__(256) k_deinterleave(const uint8_t* __restrict_
 }
 
 // ---------------------------------------------------------------------- launchers --
-static Scene make_scene(const LaunchScene& s) {
-  Scene sc;
-  sc.shapes = s.shapes;
-  sc.lights = s.lights;
-  sc.pairs = s.pairs;
-  sc.lshapes = s.shapes;
-  sc.lpairs = s.pairs;
-  sc.n = s.n;
-  sc.m = s.m;
-  sc.refl_mask = s.refl_mask;
-  sc.has_quadric = s.has_quadric;
-  sc.o0_ok = s.o0_ok;
-  sc.dep_fast = s.dep_fast;
-  return sc;
-}
-static bool stage_fits(const LaunchScene& s) {
-  return s.n + 1 <= kStageShapes && (s.n + 1) * s.m <= kStagePairs;
-}
-static Cam make_cam(const LaunchScene& s, int W, int H) {
-  Cam c;
-  c.hx = 0.0 - (double)s.cam_w / 2.0;
-  c.hy = 0.0 + (double)s.cam_h / 2.0;
-  c.pw = s.cam_w / (float)W;
-  c.ph = s.cam_h / (float)H;
-  return c;
-}
-
-// The launchers' runtime flags as the kernels' template flags: fn(st) or fn(cuda, st) with
-// std::bool_constant arguments, so a launcher names its kernel once as k<cuda.value, st.value>.
-// cuda_sem is the outer branch: kernels are emitted in the order they are instantiated, and
-// <true, true>, <true, false>, <false, true>, <false, false> keeps the code object's layout as
-// it has been measured.
-template <class Fn>
-static void dispatch(bool st, Fn fn) {
-  st ? fn(std::true_type{}) : fn(std::false_type{});
-}
-template <class Fn>
-static void dispatch(bool cuda_sem, bool st, Fn fn) {
-  if (cuda_sem)
-    dispatch(st, [&](auto s) { fn(std::true_type{}, s); });
-  else
-    dispatch(st, [&](auto s) { fn(std::false_type{}, s); });
-}
-
 hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_step, int nrows,
                          int maxrec, uint8_t* out, unsigned long long* zcount,
                          hipStream_t stream, bool cuda_sem) {
@@ -3602,186 +2837,6 @@ hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_s
       hipLaunchKernelGGL(k_render<st.value>, grid, dim3(kBlock), 0, stream, make_scene(s),
                          make_cam(s, W, H), W, H, row0, row_step, nrows, maxrec, out, zcount);
     });
-  return hipGetLastError();
-}
-
-static int ssaa_log2(int ssaa) { return ssaa == 2 ? 1 : ssaa == 4 ? 2 : ssaa == 8 ? 3 : -1; }
-
-hipError_t launch_render_ssaa(const LaunchScene& s, int W, int H, int ssaa, int row0, int row_step,
-                              int nrows, int maxrec, uint8_t* out, unsigned long long* zcount,
-                              hipStream_t stream) {
-  const int ls = ssaa_log2(ssaa);
-  if (ls < 0 || W > 0x7fffffff / ssaa || H > 0x7fffffff / ssaa || nrows > 0x7fffffff / ssaa)
-    return hipErrorInvalidValue;
-  const int sw = W * ssaa, sr = nrows * ssaa;
-  dim3 grid((sw + kTileW - 1) / kTileW, (sr + kTileH - 1) / kTileH);
-  if (grid.y > 65535u) return hipErrorInvalidValue;   // grid.y of k_render's tile layout
-  dispatch(stage_fits(s), [&](auto st) {
-    hipLaunchKernelGGL(k_render_ssaa<st.value>, grid, dim3(kBlock), 0, stream, make_scene(s),
-                       make_cam(s, sw, H * ssaa), W, ls, row0, row_step, nrows, maxrec, out,
-                       zcount);
-  });
-  return hipGetLastError();
-}
-
-hipError_t launch_box_down(const uint8_t* src, int W, int H, int ssaa, uint8_t* dst,
-                           hipStream_t stream) {
-  const int ls = ssaa_log2(ssaa);
-  const size_t blocks = ((size_t)W * H + 255) / 256;
-  if (ls < 0 || W <= 0 || H <= 0 || blocks > 0x7fffffffu) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_box_down, dim3((unsigned)blocks), dim3(256), 0, stream, src, W, H, ls, dst);
-  return hipGetLastError();
-}
-
-hipError_t launch_aa_mark(const uint8_t* img, int W, int H, int threshold, uint32_t* list,
-                          unsigned* count, hipStream_t stream) {
-  if (W <= 0 || H <= 0 || threshold < 1 || threshold > 255) return hipErrorInvalidValue;
-  if ((unsigned long long)W * (unsigned long long)H >= (1ull << 32))
-    return hipErrorInvalidValue;   // pixel indices are uint32
-  const unsigned long long tiles_x = ((unsigned long long)W + kMarkBlock - 1) / kMarkBlock;
-  const unsigned long long tiles = tiles_x * (((unsigned long long)H + kMarkRows - 1) / kMarkRows);
-  if (tiles > 0x7fffffffull) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_aa_mark, dim3((unsigned)tiles), dim3(kMarkBlock), 0, stream, img, W, H,
-                     (unsigned)tiles_x, threshold, list, count);
-  return hipGetLastError();
-}
-
-// the grid of a kernel that strides over a list of at most W*H pixels with `lanes` lanes a pixel
-static int list_blocks(int W, int H, int lanes, int cus, int want) {
-  if (want > 0) return want;
-  // the kernels are compiled for RC_PHASE_A_WAVES waves per SIMD: that many 4-wave workgroups
-  // per CU are resident at once; never more workgroups than the image has wave steps
-  const unsigned long long per = 64u / (unsigned)lanes * (kBlock / 64);
-  const unsigned long long need = ((unsigned long long)W * H + per - 1) / per;
-  const unsigned long long cap = (unsigned long long)(cus > 0 ? cus : 256) * RC_PHASE_A_WAVES;
-  return (int)(need < cap ? need : cap);
-}
-
-int aa_refine_blocks(int W, int H, int ssaa, int cus, int want) {
-  return list_blocks(W, H, ssaa * ssaa, cus, want);
-}
-
-hipError_t launch_aa_refine(const LaunchScene& s, int W, int H, int ssaa, int maxrec,
-                            const uint32_t* list, const unsigned* count, uint8_t* out,
-                            unsigned long long* zcount, int blocks, hipStream_t stream,
-                            bool cuda_sem) {
-  const int ls = ssaa_log2(ssaa);
-  if (ls < 0 || W <= 0 || H <= 0 || W > 0x7fffffff / ssaa || H > 0x7fffffff / ssaa ||
-      blocks < 1 || blocks > 4096)
-    return hipErrorInvalidValue;
-  const Scene sc = make_scene(s);
-  const Cam cam = make_cam(s, W * ssaa, H * ssaa);   // the camera of the s*W x s*H image
-  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
-    hipLaunchKernelGGL((k_aa_refine<cuda.value, st.value>), dim3((unsigned)blocks), dim3(kBlock),
-                       0, stream, sc, cam, W, ls, maxrec, list, count, out, zcount);
-  });
-  return hipGetLastError();
-}
-
-int rates_supported(int W, int H) {
-  if (W <= 0 || H <= 0) return 0;
-  if ((unsigned long long)W * (unsigned long long)H >= (1ull << 32)) return 0;   // uint32 entries
-  if (W > 0x7fffffff / 8 || H > 0x7fffffff / 8) return 0;   // subsample coordinates at rate 8
-  return ((unsigned)H + kTileH - 1) / kTileH <= 65535u;     // grid.y of k_render's tile layout
-}
-
-hipError_t launch_rates_render(const LaunchScene& s, int W, int H, int maxrec,
-                               const uint8_t* rates, uint8_t* out, uint32_t* list4,
-                               uint32_t* list28, unsigned* cnt, unsigned long long* zcount,
-                               hipStream_t stream, bool cuda_sem) {
-  if (!rates_supported(W, H)) return hipErrorInvalidValue;
-  dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
-  const Scene sc = make_scene(s);
-  const Cam cam = make_cam(s, W, H);
-  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
-    hipLaunchKernelGGL((k_rates_render<cuda.value, st.value>), grid, dim3(kBlock), 0, stream, sc,
-                       cam, W, H, maxrec, rates, out, list28, list4,
-                       list28 + ((size_t)W * H - 1), cnt, zcount);
-  });
-  return hipGetLastError();
-}
-
-hipError_t launch_rates_refine8(const LaunchScene& s, int W, int H, int maxrec,
-                                const uint32_t* list28, const unsigned* count, uint8_t* out,
-                                unsigned long long* zcount, int blocks, hipStream_t stream,
-                                bool cuda_sem) {
-  if (!rates_supported(W, H) || blocks < 1 || blocks > 4096) return hipErrorInvalidValue;
-  const Scene sc = make_scene(s);
-  const Cam cam = make_cam(s, W * 8, H * 8);   // the camera of the 8*W x 8*H image
-  const uint32_t* last = list28 + ((size_t)W * H - 1);
-  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
-    hipLaunchKernelGGL((k_rates_refine8<cuda.value, st.value>), dim3((unsigned)blocks),
-                       dim3(kBlock), 0, stream, sc, cam, W, maxrec, last, count, out, zcount);
-  });
-  return hipGetLastError();
-}
-
-static int pattern_log2(int v, int lo, int hi) {
-  for (int l = lo; l <= hi; ++l)
-    if (v == 1 << l) return l;
-  return -1;
-}
-
-int pattern_supported(int W, int H, int g, int n, bool listed) {
-  const int lg = pattern_log2(g, 1, 3), ln = pattern_log2(n, 1, 4);
-  if (lg < 0 || ln < 0 || n > g * g) return 0;
-  if (W <= 0 || H <= 0 || W > (1 << 28) / g || H > (1 << 28) / g) return 0;   // g*W, g*H within int
-  if (!listed) {   // the dense form's tiles: grid.y, and xcd_tile's int tile index
-    const unsigned long long tx = (((unsigned)W - 1u) >> (pat_lbw(ln) + 1)) + 1u;
-    const unsigned long long ty = (((unsigned)H - 1u) >> (pat_lbh(ln) + 1)) + 1u;
-    return ty <= 65535ull && tx * ty <= 0x7fffffffull;
-  }
-  if ((unsigned long long)W * (unsigned long long)H >= (1ull << 32)) return 0;   // uint32 entries
-  return ((unsigned)H + kTileH - 1) / kTileH <= 65535u;   // grid.y of k_render's tile layout
-}
-
-int pattern_list_blocks(int W, int H, int n, int cus, int want) {
-  return list_blocks(W, H, n, cus, want);
-}
-
-// entry k of the 4-bit words: v[k] < 16 for k < n <= 16 (pattern_supported's g <= 8)
-static PatWords pattern_words(int n, const uint8_t* px, const uint8_t* py) {
-  PatWords w{0ull, 0ull};
-  for (int k = 0; k < n; ++k) {
-    w.x |= (unsigned long long)(px[k] & 15u) << (4 * k);
-    w.y |= (unsigned long long)(py[k] & 15u) << (4 * k);
-  }
-  return w;
-}
-
-hipError_t launch_pattern(const LaunchScene& s, int W, int H, int g, int n, const uint8_t* px,
-                          const uint8_t* py, int maxrec, uint8_t* out,
-                          unsigned long long* zcount, hipStream_t stream, bool cuda_sem) {
-  if (!pattern_supported(W, H, g, n, false)) return hipErrorInvalidValue;
-  const int lg = pattern_log2(g, 1, 3), ln = pattern_log2(n, 1, 4);
-  const int ltw = pat_lbw(ln) + 1, lth = pat_lbh(ln) + 1;   // the workgroup's tile
-  dim3 grid((((unsigned)W - 1u) >> ltw) + 1u, (((unsigned)H - 1u) >> lth) + 1u);
-  const Scene sc = make_scene(s);
-  const Cam cam = make_cam(s, W * g, H * g);   // the camera of the g*W x g*H image
-  const PatWords pat = pattern_words(n, px, py);
-  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
-    hipLaunchKernelGGL((k_pattern<cuda.value, st.value>), grid, dim3(kBlock), 0, stream, sc, cam,
-                       W, H, lg, ln, pat, maxrec, out, zcount);
-  });
-  return hipGetLastError();
-}
-
-hipError_t launch_pattern_list(const LaunchScene& s, int W, int H, int g, int n,
-                               const uint8_t* px, const uint8_t* py, int maxrec,
-                               const uint32_t* list, const unsigned* count, uint8_t* out,
-                               unsigned long long* zcount, int blocks, hipStream_t stream,
-                               bool cuda_sem) {
-  if (!pattern_supported(W, H, g, n, true) || blocks < 1 || blocks > 4096)
-    return hipErrorInvalidValue;
-  const int lg = pattern_log2(g, 1, 3), ln = pattern_log2(n, 1, 4);
-  const Scene sc = make_scene(s);
-  const Cam cam = make_cam(s, W * g, H * g);   // the camera of the g*W x g*H image
-  const PatWords pat = pattern_words(n, px, py);
-  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
-    hipLaunchKernelGGL((k_pattern_list<cuda.value, st.value>), dim3((unsigned)blocks),
-                       dim3(kBlock), 0, stream, sc, cam, W, lg, ln, pat, maxrec, list, count, out,
-                       zcount);
-  });
   return hipGetLastError();
 }
 
@@ -4069,567 +3124,5 @@ hipError_t launch_deinterleave(const uint8_t* gathered, const uint8_t* block0, i
 
 size_t deprec_bytes() { return sizeof(DepLine); }   // one line per pixel (DepLine)
 size_t row_stats_bytes() { return sizeof(RowStats); }
-
-// -------------------------------------- progressive supersampling (fast, cuda) --
-// rc_accum_pass_device / rc_render_accum (include/raycast_hip.h, rc_accum_px): the caller keeps
-// one 8-byte record per pixel, the sums of the n sample bytes taken so far and n itself, and a
-// pass adds `count` (1..16) further samples of a sequence on the g x g subsample lattice and
-// stores the rounded mean of all of them.  Sample k of pixel (x, y) is pixel
-// (g*x + px[k], g*y + py[k]) of the g*W x g*H image, shot with that image's camera (`cam`) through
-// sample_shoot exactly as k_pattern shoots its samples, so every sample byte is that image's byte.
-// The pass's slice of the sequence travels as PatWords (entry j of the words is sample first + j),
-// read with a uniform index, so the positions stay in scalar registers.  These kernels and their
-// launchers stand behind every other kernel of the file: kernels are emitted in instantiation
-// order, and the layout of the code object before them stays the parent's.
-//
-// One lane per pixel shoots its `count` samples one after the other (a uniform trip count), so any
-// count works, not only the powers of two a lane butterfly can reduce.  The record is a uint2:
-// .x = sum[0] | sum[1] << 16, .y = sum[2] | n << 16.  sample_shoot's packing R | G << 16 and B
-// adds onto it directly: a channel's sum is at most 256 * 255 = 65280 < 2^16, so nothing carries
-// from R into G or from B into n.  A pixel with n + count > 256 is saturated: nothing of it
-// changes, and the pass counts it in *sat (one ballot a wave, an atomic by its first lane only
-// when the ballot is not empty).
-__device__ __forceinline__ void accum_resolve_px(uint2 rec, uint8_t& r, uint8_t& g, uint8_t& b) {
-  const unsigned n = rec.y >> 16;
-  if (n == 0u) {
-    r = g = b = 0;
-    return;
-  }
-  const unsigned half = n >> 1;
-  r = (uint8_t)(((rec.x & 0xffffu) + half) / n);
-  g = (uint8_t)(((rec.x >> 16) + half) / n);
-  b = (uint8_t)(((rec.y & 0xffffu) + half) / n);
-}
-
-// Called by every lane of the wave.
-__device__ __forceinline__ void accum_count_saturated(bool saturated, unsigned* __restrict__ sat) {
-  const unsigned long long m = __ballot(saturated);
-  if (m && (threadIdx.x & 63) == 0) atomicAdd(sat, (unsigned)__popcll(m));
-}
-
-// Dense pass: every pixel of the image, k_render's grid, tiles and framebuffer stores.  The
-// record's n is read alone before the samples (two bytes; the branch keeps it in the exec mask,
-// not in a register across shoot) and the whole record once after them: one 8-byte load and one
-// 8-byte store a lane, adjacent lanes of a tile row adjacent in memory.  `reset`: the record is
-// not read at all and counts as zero.
-// (ox, oy): the window's origin in the virtual image, in pixels (k_accum: 0, 0; k_accum_win below).
-template <bool kCuda, bool kStage>
-__device__ __forceinline__ void accum_dense(
-    Scene sc, Cam cam, int W, int H, int ox, int oy, int lg, int count, PatWords pat, int reset,
-    int maxrec, uint2* __restrict__ acc, uint8_t* __restrict__ out,
-    unsigned long long* __restrict__ zcount, unsigned* __restrict__ sat) {
-  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
-  __shared__ StageBuf<kStage> stage;
-  __shared__ TileBytes tb;
-  tile_init(tb);
-  stage_scene<kStage>(sc, stage);
-  if (!kStage) __syncthreads();
-  int lx, ly;
-  tile_pixel(lx, ly);
-  int bx, by;
-  xcd_tile<0>(bx, by);
-  const int x0 = bx * kTileW, y0 = by * kTileH;
-  const int x = x0 + lx, y = y0 + ly;
-  bool saturated = false;
-  if (x < W && y < H) {
-    const size_t p = (size_t)y * W + x;
-    const unsigned had = reset ? 0u : (unsigned)((const uint16_t*)(acc + p))[3];
-    saturated = had + (unsigned)count > 256u;
-    if (!saturated) {
-      unsigned rg = 0u, b = 0u;
-      for (int k = 0; k < count; ++k) {   // uniform
-        unsigned srg, sb;
-        sample_shoot<kCuda>(sc, cam, ((ox + x) << lg) + pat_entry(pat.x, (unsigned)k),
-                            ((oy + y) << lg) + pat_entry(pat.y, (unsigned)k), maxrec, zcount, srg,
-                            sb);
-        rg += srg;
-        b += sb;
-      }
-      uint2 rec = make_uint2(0u, 0u);
-      if (!reset) rec = acc[p];
-      rec.x += rg;
-      rec.y += b + ((unsigned)count << 16);
-      acc[p] = rec;
-      uint8_t r8, g8, b8;
-      accum_resolve_px(rec, r8, g8, b8);
-      tile_put_rgb(tb, lx, ly, r8, g8, b8, out + p * 3);
-    } else if (RC_TILE_STAGE) {   // the staged tile's whole-row stores write this pixel too
-      const uint8_t* q = out + p * 3;
-      tile_put_rgb(tb, lx, ly, q[0], q[1], q[2], out + p * 3);
-    }
-  }
-  accum_count_saturated(saturated, sat);
-  if (!tile_last_wave(tb)) return;
-  const int nx = W - x0 < kTileW ? W - x0 : kTileW;
-  tile_write_rows<kTileW * 3 / 4>(tb.rgb, [&](int q) -> uint8_t* {
-    return y0 + q < H ? out + ((size_t)(y0 + q) * W + x0) * 3 : nullptr;
-  }, nx * 3);
-}
-template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum(
-    Scene sc, Cam cam, int W, int H, int lg, int count, PatWords pat, int reset, int maxrec,
-    uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
-    unsigned* __restrict__ sat) {
-  accum_dense<kCuda, kStage>(sc, cam, W, H, 0, 0, lg, count, pat, reset, maxrec, acc, out, zcount,
-                             sat);
-}
-
-// Masked pass: over k_aa_mark's list like k_pattern_list, one lane per listed pixel (64 a wave
-// step); the list's length is read from device memory and the grid is a fixed number of
-// workgroups whose waves stride over the list.  A wave's trip count depends on the wave alone, so
-// every lane reaches the ballot.  A listed pixel is in the list once, so its record and its three
-// bytes have one writer.
-// (ox, oy): as accum_dense's.
-template <bool kCuda, bool kStage>
-__device__ __forceinline__ void accum_listed(
-    Scene sc, Cam cam, int W, int ox, int oy, int lg, int count, PatWords pat, int maxrec,
-    const uint32_t* __restrict__ list, const unsigned* __restrict__ nlist,
-    uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
-    unsigned* __restrict__ sat) {
-  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
-  __shared__ StageBuf<kStage> stage;
-  const unsigned n = *nlist;
-  if (n == 0u) return;   // uniform over the grid: an empty list costs its launch
-  stage_scene<kStage>(sc, stage);   // its barrier comes before the loop: every thread is here
-  const int lane = threadIdx.x & 63;
-  // wave-uniform by construction: told to the compiler, so the loop's counters stay scalar
-  const unsigned wave =
-      __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
-  const unsigned step = gridDim.x * (kBlock / 64) * 64u;   // <= 4096 * 4 * 64
-  // 64-bit index: n + step may pass 2^32
-  for (unsigned long long first = (unsigned long long)wave * 64u; first < n; first += step) {
-    const unsigned long long e = first + (unsigned)lane;
-    bool saturated = false;
-    if (e < n) {
-      const unsigned p = list[e];
-      saturated = (unsigned)((const uint16_t*)(acc + p))[3] + (unsigned)count > 256u;
-      if (!saturated) {
-        const int xs = (int)((p % (unsigned)W + (unsigned)ox) << lg);
-        const int ys = (int)((p / (unsigned)W + (unsigned)oy) << lg);
-        unsigned rg = 0u, b = 0u;
-        for (int k = 0; k < count; ++k) {   // uniform
-          unsigned srg, sb;
-          sample_shoot<kCuda>(sc, cam, xs + pat_entry(pat.x, (unsigned)k),
-                              ys + pat_entry(pat.y, (unsigned)k), maxrec, zcount, srg, sb);
-          rg += srg;
-          b += sb;
-        }
-        // the entry is read again (opaque index) rather than kept in a register across shoot, as
-        // in k_aa_refine
-        unsigned l = (unsigned)lane;
-        asm volatile("" : "+v"(l));
-        const size_t q = list[first + l];
-        uint2 rec = acc[q];
-        rec.x += rg;
-        rec.y += b + ((unsigned)count << 16);
-        acc[q] = rec;
-        uint8_t r8, g8, b8;
-        accum_resolve_px(rec, r8, g8, b8);
-        uint8_t* o = out + q * 3;
-        o[0] = r8;
-        o[1] = g8;
-        o[2] = b8;
-      }
-    }
-    accum_count_saturated(saturated, sat);
-  }
-}
-template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_list(
-    Scene sc, Cam cam, int W, int lg, int count, PatWords pat, int maxrec,
-    const uint32_t* __restrict__ list, const unsigned* __restrict__ nlist,
-    uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
-    unsigned* __restrict__ sat) {
-  accum_listed<kCuda, kStage>(sc, cam, W, 0, 0, lg, count, pat, maxrec, list, nlist, acc, out,
-                              zcount, sat);
-}
-
-// out = res(acc) for every pixel, nothing shot: 8 bytes in and 3 out a pixel, memory-bound.
-__global__ void __launch_bounds__(256) k_accum_resolve(const uint2* __restrict__ acc,
-                                                       unsigned long long pixels,
-                                                       uint8_t* __restrict__ out) {
-  const unsigned long long p = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-  if (p >= pixels) return;
-  uint8_t r8, g8, b8;
-  accum_resolve_px(acc[p], r8, g8, b8);
-  uint8_t* o = out + p * 3;
-  o[0] = r8;
-  o[1] = g8;
-  o[2] = b8;
-}
-
-int accum_supported(int W, int H, int g, bool listed) {
-  if (pattern_log2(g, 1, 3) < 0) return 0;
-  if (W <= 0 || H <= 0 || W > (1 << 28) / g || H > (1 << 28) / g) return 0;   // g*W, g*H within int
-  if (!listed) {   // k_render's tiles: grid.y, and xcd_tile's int tile index
-    const unsigned long long tx = ((unsigned)W + kTileW - 1) / kTileW;
-    const unsigned long long ty = ((unsigned)H + kTileH - 1) / kTileH;
-    return ty <= 65535ull && tx * ty <= 0x7fffffffull;
-  }
-  if ((unsigned long long)W * (unsigned long long)H >= (1ull << 32)) return 0;   // uint32 entries
-  const unsigned long long mx = ((unsigned long long)W + kMarkBlock - 1) / kMarkBlock;
-  const unsigned long long my = ((unsigned long long)H + kMarkRows - 1) / kMarkRows;
-  return mx * my <= 0x7fffffffull;   // k_aa_mark's grid
-}
-
-int accum_list_blocks(int W, int H, int cus, int want) { return list_blocks(W, H, 1, cus, want); }
-
-hipError_t launch_accum(const LaunchScene& s, int W, int H, int g, int count, const uint8_t* px,
-                        const uint8_t* py, bool reset, int maxrec, void* acc, uint8_t* out,
-                        unsigned long long* zcount, unsigned* sat, hipStream_t stream,
-                        bool cuda_sem) {
-  if (!accum_supported(W, H, g, false) || count < 1 || count > 16) return hipErrorInvalidValue;
-  const int lg = pattern_log2(g, 1, 3);
-  dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
-  const Scene sc = make_scene(s);
-  const Cam cam = make_cam(s, W * g, H * g);   // the camera of the g*W x g*H image
-  const PatWords pat = pattern_words(count, px, py);
-  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
-    hipLaunchKernelGGL((k_accum<cuda.value, st.value>), grid, dim3(kBlock), 0, stream, sc, cam, W,
-                       H, lg, count, pat, reset ? 1 : 0, maxrec, (uint2*)acc, out, zcount, sat);
-  });
-  return hipGetLastError();
-}
-
-hipError_t launch_accum_list(const LaunchScene& s, int W, int H, int g, int count,
-                             const uint8_t* px, const uint8_t* py, int maxrec,
-                             const uint32_t* list, const unsigned* nlist, void* acc, uint8_t* out,
-                             unsigned long long* zcount, unsigned* sat, int blocks,
-                             hipStream_t stream, bool cuda_sem) {
-  if (!accum_supported(W, H, g, true) || count < 1 || count > 16 || blocks < 1 || blocks > 4096)
-    return hipErrorInvalidValue;
-  const int lg = pattern_log2(g, 1, 3);
-  const Scene sc = make_scene(s);
-  const Cam cam = make_cam(s, W * g, H * g);   // the camera of the g*W x g*H image
-  const PatWords pat = pattern_words(count, px, py);
-  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
-    hipLaunchKernelGGL((k_accum_list<cuda.value, st.value>), dim3((unsigned)blocks), dim3(kBlock),
-                       0, stream, sc, cam, W, lg, count, pat, maxrec, list, nlist, (uint2*)acc,
-                       out, zcount, sat);
-  });
-  return hipGetLastError();
-}
-
-hipError_t launch_accum_resolve(const void* acc, int W, int H, uint8_t* out, hipStream_t stream) {
-  if (W <= 0 || H <= 0) return hipErrorInvalidValue;
-  const unsigned long long pixels = (unsigned long long)W * (unsigned long long)H;
-  const unsigned long long blocks = (pixels + 255) / 256;
-  if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_accum_resolve, dim3((unsigned)blocks), dim3(256), 0, stream,
-                     (const uint2*)acc, pixels, out);
-  return hipGetLastError();
-}
-
-// ------------------------------------- windows of a virtual image (fast, cuda) --
-// rc_render_window*, rc_accum_pass_window_device (include/raycast_hip.h, rc_window): the W x H
-// output is the rectangle at (x0, y0) of the full_w x full_h image, so pixel (x, y) of the window
-// is pixel (x0 + x, y0 + y) of that image and its subsamples are shot with the camera of the
-// s*full_w x s*full_h image (`cam`) at the coordinates s*(x0 + x) + i, s*(y0 + y) + j: what
-// k_render_ssaa, k_pattern and k_accum shoot for that pixel of the whole image.  Nothing of the
-// arithmetic changes, only where in the picture the rays start.  These kernels stand behind every
-// other kernel of the file, as section 16's did.
-//
-// k_window: k_render_ssaa's tiles over the window's own subsample grid (s = 1 << ls in 1, 2, 4, 8;
-// a workgroup owns 16 x 16 subsamples, a wave an 8 x 8 block of them), one lane per subsample.
-// Inside a wave's block the s x s subsamples of an output pixel are s*s adjacent lanes (lane l:
-// group l / (s*s), subsample l % (s*s) of it, row-major in both), so sample_reduce sums them and
-// the group's first lane stores the rounded mean.  The origin (ox, oy) = (s*x0, s*y0) is whole
-// pixels, so the groups stay aligned to the wave blocks whatever x0 and y0 are, and a group is
-// wholly inside the window or wholly outside it.  At s = 1 a lane is a pixel and stores its own
-// bytes.  The subsample image is never stored, in cuda mode either.
-template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_window(
-    Scene sc, Cam cam, int W, int H, int ls, int ox, int oy, int maxrec, uint8_t* __restrict__ out,
-    unsigned long long* __restrict__ zcount) {
-  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
-  __shared__ StageBuf<kStage> stage;
-  stage_scene<kStage>(sc, stage);
-  int bx, by;
-  xcd_tile<0>(bx, by);
-  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const unsigned sub = lane & ((1u << (2 * ls)) - 1u);   // subsample within the group
-  const unsigned grp = lane >> (2 * ls);                  // group within the wave's 8 x 8 block
-  const int lgw = 3 - ls;                                 // log2 of the groups in a row of it
-  // unsigned: the last tile's columns may reach past 2^31 - 1 when s*W is close to it
-  const unsigned xs = (unsigned)bx * kTileW + (wave % (kTileW / 8)) * 8u +
-                      ((grp & ((1u << lgw) - 1u)) << ls) + (sub & ((1u << ls) - 1u));
-  const unsigned rs = (unsigned)by * kTileH + (wave / (kTileW / 8)) * 8u + ((grp >> lgw) << ls) +
-                      (sub >> ls);
-  // only xs and rs stay live across shoot, as in k_render_ssaa
-  const bool inside = (xs >> ls) < (unsigned)W && (rs >> ls) < (unsigned)H;
-  unsigned rg = 0u, b = 0u;
-  if (inside) sample_shoot<kCuda>(sc, cam, ox + (int)xs, oy + (int)rs, maxrec, zcount, rg, b);
-  sample_reduce(rg, b, 2 * ls);
-  if (inside && sub == 0u) {   // the group's first lane
-    uint8_t* q = out + ((size_t)(rs >> ls) * W + (xs >> ls)) * 3;
-    if (ls == 0) {   // one sample: its own bytes (sample_store's half is for two samples and more)
-      q[0] = (uint8_t)(rg & 0xffffu);
-      q[1] = (uint8_t)(rg >> 16);
-      q[2] = (uint8_t)b;
-    } else {
-      sample_store(q, rg, b, 2 * ls);
-    }
-  }
-}
-
-// The accumulation passes through a window: accum_dense's and accum_listed's bodies with the
-// window's origin; the records and the image are the window's own W x H.
-template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_win(
-    Scene sc, Cam cam, int W, int H, int ox, int oy, int lg, int count, PatWords pat, int reset,
-    int maxrec, uint2* __restrict__ acc, uint8_t* __restrict__ out,
-    unsigned long long* __restrict__ zcount, unsigned* __restrict__ sat) {
-  accum_dense<kCuda, kStage>(sc, cam, W, H, ox, oy, lg, count, pat, reset, maxrec, acc, out,
-                             zcount, sat);
-}
-template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_list_win(
-    Scene sc, Cam cam, int W, int ox, int oy, int lg, int count, PatWords pat, int maxrec,
-    const uint32_t* __restrict__ list, const unsigned* __restrict__ nlist,
-    uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
-    unsigned* __restrict__ sat) {
-  accum_listed<kCuda, kStage>(sc, cam, W, ox, oy, lg, count, pat, maxrec, list, nlist, acc, out,
-                              zcount, sat);
-}
-
-// the window lies inside the virtual image and s times that image's sides fit an int
-static bool window_inside(const Window& w, int W, int H, int s) {
-  return W >= 1 && H >= 1 && w.full_w >= 1 && w.full_h >= 1 && w.x0 >= 0 && w.y0 >= 0 &&
-         W <= w.full_w - w.x0 && H <= w.full_h - w.y0 && w.full_w <= 0x7fffffff / s &&
-         w.full_h <= 0x7fffffff / s;
-}
-
-int window_supported(const Window& w, int W, int H, int s) {
-  if ((s != 1 && ssaa_log2(s) < 0) || !window_inside(w, W, H, s)) return 0;
-  // k_render's tiles over the window's subsamples: grid.y, and xcd_tile's int tile index
-  const unsigned long long tx = ((unsigned long long)W * s + kTileW - 1) / kTileW;
-  const unsigned long long ty = ((unsigned long long)H * s + kTileH - 1) / kTileH;
-  return ty <= 65535ull && tx * ty <= 0x7fffffffull;
-}
-
-hipError_t launch_window(const LaunchScene& s, const Window& w, int W, int H, int ssaa, int maxrec,
-                         uint8_t* out, unsigned long long* zcount, hipStream_t stream,
-                         bool cuda_sem) {
-  if (!window_supported(w, W, H, ssaa)) return hipErrorInvalidValue;
-  const int ls = ssaa == 1 ? 0 : ssaa_log2(ssaa);
-  dim3 grid((unsigned)(((unsigned long long)W * ssaa + kTileW - 1) / kTileW),
-            (unsigned)(((unsigned long long)H * ssaa + kTileH - 1) / kTileH));
-  const Scene sc = make_scene(s);
-  const Cam cam = make_cam(s, w.full_w * ssaa, w.full_h * ssaa);   // of the s*full_w x s*full_h image
-  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
-    hipLaunchKernelGGL((k_window<cuda.value, st.value>), grid, dim3(kBlock), 0, stream, sc, cam, W,
-                       H, ls, w.x0 * ssaa, w.y0 * ssaa, maxrec, out, zcount);
-  });
-  return hipGetLastError();
-}
-
-hipError_t launch_accum_window(const LaunchScene& s, const Window& w, int W, int H, int g,
-                               int count, const uint8_t* px, const uint8_t* py, bool reset,
-                               int maxrec, void* acc, uint8_t* out, unsigned long long* zcount,
-                               unsigned* sat, hipStream_t stream, bool cuda_sem) {
-  if (!accum_supported(W, H, g, false) || !window_inside(w, W, H, g) || count < 1 || count > 16)
-    return hipErrorInvalidValue;
-  const int lg = pattern_log2(g, 1, 3);
-  dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
-  const Scene sc = make_scene(s);
-  const Cam cam = make_cam(s, w.full_w * g, w.full_h * g);   // of the g*full_w x g*full_h image
-  const PatWords pat = pattern_words(count, px, py);
-  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
-    hipLaunchKernelGGL((k_accum_win<cuda.value, st.value>), grid, dim3(kBlock), 0, stream, sc, cam,
-                       W, H, w.x0, w.y0, lg, count, pat, reset ? 1 : 0, maxrec, (uint2*)acc, out,
-                       zcount, sat);
-  });
-  return hipGetLastError();
-}
-
-hipError_t launch_accum_list_window(const LaunchScene& s, const Window& w, int W, int H, int g,
-                                    int count, const uint8_t* px, const uint8_t* py, int maxrec,
-                                    const uint32_t* list, const unsigned* nlist, void* acc,
-                                    uint8_t* out, unsigned long long* zcount, unsigned* sat,
-                                    int blocks, hipStream_t stream, bool cuda_sem) {
-  if (!accum_supported(W, H, g, true) || !window_inside(w, W, H, g) || count < 1 || count > 16 ||
-      blocks < 1 || blocks > 4096)
-    return hipErrorInvalidValue;
-  const int lg = pattern_log2(g, 1, 3);
-  const Scene sc = make_scene(s);
-  const Cam cam = make_cam(s, w.full_w * g, w.full_h * g);   // of the g*full_w x g*full_h image
-  const PatWords pat = pattern_words(count, px, py);
-  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
-    hipLaunchKernelGGL((k_accum_list_win<cuda.value, st.value>), dim3((unsigned)blocks),
-                       dim3(kBlock), 0, stream, sc, cam, W, w.x0, w.y0, lg, count, pat, maxrec,
-                       list, nlist, (uint2*)acc, out, zcount, sat);
-  });
-  return hipGetLastError();
-}
-
-// ------------------------------------ scrolling an accumulated view (fast, cuda) --
-// rc_accum_scroll_device (include/raycast_hip.h): the destination state is the source state moved
-// by (-dx, -dy) where the two windows overlap (the kept rectangle K, scroll_rects) and freshly
-// accumulated where the pan exposed new pixels.  Two kernels, behind every other kernel of the
-// file as section 16's and 17's were.
-//
-// k_accum_move: the kept rectangle, one lane a pixel, adjacent lanes adjacent pixels of a row: one
-// 8-byte load and one 8-byte store of the record and three bytes of the image.  grid.x covers a
-// row of K in 256-pixel pieces, grid.y strides over its rows; every offset is a 64-bit pixel
-// index.  (kx, ky): K's corner in the destination, (sx, sy) = (kx + dx, ky + dy) in the source.
-__global__ void __launch_bounds__(256) k_accum_move(
-    const uint2* __restrict__ acc_src, const uint8_t* __restrict__ out_src,
-    uint2* __restrict__ acc_dst, uint8_t* __restrict__ out_dst, int W, int kw, int kh, int kx,
-    int ky, int sx, int sy) {
-  const unsigned x = blockIdx.x * 256u + threadIdx.x;
-  if (x >= (unsigned)kw) return;
-  for (unsigned y = blockIdx.y; y < (unsigned)kh; y += gridDim.y) {
-    const size_t s = (size_t)((unsigned)sy + y) * (unsigned)W + ((unsigned)sx + x);
-    const size_t d = (size_t)((unsigned)ky + y) * (unsigned)W + ((unsigned)kx + x);
-    acc_dst[d] = acc_src[s];
-    const uint8_t* q = out_src + s * 3;
-    uint8_t* o = out_dst + d * 3;
-    const uint8_t r8 = q[0], g8 = q[1], b8 = q[2];
-    o[0] = r8;
-    o[1] = g8;
-    o[2] = b8;
-  }
-}
-
-// Pixel e of the exposed set, e < r.total: the rectangle is found by comparing e with the
-// rectangles' first entries (an empty rectangle shares its first entry with the next one, so it is
-// never the last one at or below e), then one unsigned divide by that rectangle's width.
-__device__ __forceinline__ void exposed_pixel(const ScrollRects& r, unsigned e, int& x, int& y) {
-  unsigned first = r.first[0], w = r.w[0];
-  int x0 = r.x[0], y0 = r.y[0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) {
-    const bool here = e >= r.first[k];
-    first = here ? r.first[k] : first;
-    w = here ? r.w[k] : w;
-    x0 = here ? r.x[k] : x0;
-    y0 = here ? r.y[k] : y0;
-  }
-  const unsigned i = e - first, row = i / w;
-  x = x0 + (int)(i - row * w);
-  y = y0 + (int)row;
-}
-
-// k_accum_exposed: accum_listed's body over the exposed set instead of a list: a fixed number of
-// workgroups whose waves stride over [0, r.total) with a 64-bit index, one lane per exposed pixel,
-// so a strip three pixels wide fills whole waves.  `reset` (the call's first chunk): the record is
-// not read and counts as zero, as in accum_dense; a later chunk adds to the record the chunk
-// before it stored.  No saturation: a scroll takes at most 64 samples.  The pixel is derived
-// again from the entry after the samples (opaque lane, as accum_listed reads its list entry
-// again) rather than carried across sample_shoot.  (ox, oy): as accum_dense's.
-template <bool kCuda, bool kStage>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_exposed(
-    Scene sc, Cam cam, int W, ScrollRects r, int ox, int oy, int lg, int count, PatWords pat,
-    int reset, int maxrec, uint2* __restrict__ acc, uint8_t* __restrict__ out,
-    unsigned long long* __restrict__ zcount) {
-  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
-  __shared__ StageBuf<kStage> stage;
-  stage_scene<kStage>(sc, stage);   // its barrier comes before the loop: every thread is here
-  const int lane = threadIdx.x & 63;
-  // wave-uniform by construction: told to the compiler, so the loop's counters stay scalar
-  const unsigned wave =
-      __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
-  const unsigned step = gridDim.x * (kBlock / 64) * 64u;   // <= 4096 * 4 * 64
-  const unsigned n = r.total;
-  // 64-bit index: n + step may pass 2^32
-  for (unsigned long long first = (unsigned long long)wave * 64u; first < n; first += step) {
-    if (first + (unsigned)lane >= n) continue;
-    int x, y;
-    exposed_pixel(r, (unsigned)first + (unsigned)lane, x, y);
-    const int xs = (int)(((unsigned)x + (unsigned)ox) << lg);
-    const int ys = (int)(((unsigned)y + (unsigned)oy) << lg);
-    unsigned rg = 0u, b = 0u;
-    for (int k = 0; k < count; ++k) {   // uniform
-      unsigned srg, sb;
-      sample_shoot<kCuda>(sc, cam, xs + pat_entry(pat.x, (unsigned)k),
-                          ys + pat_entry(pat.y, (unsigned)k), maxrec, zcount, srg, sb);
-      rg += srg;
-      b += sb;
-    }
-    unsigned l = (unsigned)lane;
-    asm volatile("" : "+v"(l));
-    exposed_pixel(r, (unsigned)first + l, x, y);
-    const size_t q = (size_t)(unsigned)y * (unsigned)W + (unsigned)x;
-    uint2 rec = make_uint2(0u, 0u);
-    if (!reset) rec = acc[q];
-    rec.x += rg;
-    rec.y += b + ((unsigned)count << 16);
-    acc[q] = rec;
-    uint8_t r8, g8, b8;
-    accum_resolve_px(rec, r8, g8, b8);
-    uint8_t* o = out + q * 3;
-    o[0] = r8;
-    o[1] = g8;
-    o[2] = b8;
-  }
-}
-
-ScrollRects scroll_rects(int W, int H, int dx, int dy) {
-  ScrollRects r = {};
-  if (W < 1 || H < 1 || (unsigned long long)W * (unsigned long long)H >= (1ull << 32)) return r;
-  // 64 bits: -INT_MIN does not occur
-  const long long ax = dx < 0 ? -(long long)dx : dx, ay = dy < 0 ? -(long long)dy : dy;
-  if (ax < W && ay < H) {
-    r.kw = W - (int)ax, r.kh = H - (int)ay;
-    r.kx = dx < 0 ? (int)ax : 0, r.ky = dy < 0 ? (int)ay : 0;
-  }   // else nothing is kept: K is empty at (0, 0), and the rows below it are the whole window
-  const int right = r.kx + r.kw;
-  const unsigned wd[4] = {(unsigned)W, (unsigned)r.kx, (unsigned)(W - right), (unsigned)W};
-  const unsigned ht[4] = {(unsigned)r.ky, (unsigned)r.kh, (unsigned)r.kh,
-                          (unsigned)(H - r.ky - r.kh)};
-  const int xs[4] = {0, 0, right, 0}, ys[4] = {0, r.ky, r.ky, r.ky + r.kh};
-  for (int k = 0; k < 4; ++k) {
-    r.first[k] = r.total;
-    r.w[k] = wd[k] ? wd[k] : 1u;   // an empty rectangle is never divided by
-    r.x[k] = xs[k], r.y[k] = ys[k];
-    r.total += wd[k] * ht[k];      // the four are disjoint parts of W*H < 2^32
-  }
-  return r;
-}
-
-int accum_exposed_blocks(unsigned exposed, int cus, int want) {
-  if (want > 0) return want;
-  const unsigned need = exposed / kBlock + (exposed % kBlock ? 1u : 0u);   // as list_blocks
-  const unsigned cap = (unsigned)(cus > 0 ? cus : 256) * RC_PHASE_A_WAVES;
-  if (need <= cap) return (int)need;   // one step a wave: nothing strides
-  // The entries of a rectangle are row-major, so a static stride that is a multiple of its width
-  // keeps a wave in one column of the window and the waves whose column crosses the expensive
-  // shapes finish last; an odd number of workgroups makes the stride drift through the columns
-  // (the rate map's lists: DESIGN.md section 12; here: section 18).
-  return (int)(cap > 2u && (cap & 1u) == 0u ? cap - 1u : cap);
-}
-
-hipError_t launch_accum_move(int W, int H, int g, int dx, int dy, const void* acc_src,
-                             const uint8_t* out_src, void* acc_dst, uint8_t* out_dst,
-                             hipStream_t stream) {
-  const ScrollRects r = scroll_rects(W, H, dx, dy);
-  if (!accum_supported(W, H, g, true) || r.kw < 1 || r.kh < 1) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)(r.kw + 255) / 256u, (unsigned)(r.kh < 65535 ? r.kh : 65535));
-  hipLaunchKernelGGL(k_accum_move, grid, dim3(256), 0, stream, (const uint2*)acc_src, out_src,
-                     (uint2*)acc_dst, out_dst, W, r.kw, r.kh, r.kx, r.ky, r.kx + dx, r.ky + dy);
-  return hipGetLastError();
-}
-
-hipError_t launch_accum_exposed(const LaunchScene& s, const Window& w, int W, int H, int g,
-                                int dx, int dy, int count, const uint8_t* px, const uint8_t* py,
-                                bool reset, int maxrec, void* acc, uint8_t* out,
-                                unsigned long long* zcount, int blocks, hipStream_t stream,
-                                bool cuda_sem) {
-  if (!accum_supported(W, H, g, true) || !window_inside(w, W, H, g) || count < 1 || count > 16 ||
-      blocks < 1 || blocks > 4096)
-    return hipErrorInvalidValue;
-  const ScrollRects r = scroll_rects(W, H, dx, dy);
-  if (r.total == 0u) return hipErrorInvalidValue;
-  const int lg = pattern_log2(g, 1, 3);
-  const Scene sc = make_scene(s);
-  const Cam cam = make_cam(s, w.full_w * g, w.full_h * g);   // of the g*full_w x g*full_h image
-  const PatWords pat = pattern_words(count, px, py);
-  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
-    hipLaunchKernelGGL((k_accum_exposed<cuda.value, st.value>), dim3((unsigned)blocks),
-                       dim3(kBlock), 0, stream, sc, cam, W, r, w.x0, w.y0, lg, count, pat,
-                       reset ? 1 : 0, maxrec, (uint2*)acc, out, zcount);
-  });
-  return hipGetLastError();
-}
 
 }  // namespace rc

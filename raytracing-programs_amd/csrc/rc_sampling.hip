@@ -1,7 +1,7 @@
 // rc_sampling.hip — the sampling features of libraycast_hip.so's C-ABI (include/raycast_hip.h):
 // rate maps, reconstruction filters, sparse sample patterns, progressive accumulation and windows
 // of a virtual image, with adaptive supersampling's getters.  Host code only: the kernels are
-// rc_kernels.hip's and rc_filter.hip's, the device context and the frame scaffold (enter,
+// rc_sample_kernels.hip's and rc_filter.hip's (the one-ray image is rc_kernels.hip's k_render), the device context and the frame scaffold (enter,
 // ws_frame, claim_event_set, finish_device, finish_host) are rc_api.hip's, through rc_runtime.h.
 //
 // A feature is one Refusal description, one enqueue body between SampleFrame::begin and ::end,

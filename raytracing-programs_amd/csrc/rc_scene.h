@@ -1,6 +1,6 @@
 /*
  * rc_scene.h — packed scene image shared by the host flattener (rc_scene.c) and the HIP
- * kernels (rc_kernels.hip).
+ * kernels (rc_kernels.hip, rc_sample_kernels.hip).
  *
  * The reference walks two linked lists of 104-B shape_t / 72-B light_t records copied into
  * stack VLAs (C/raycast.c:87-107).  On MI355X the whole scene is one small read-only

@@ -1,4 +1,4 @@
-"""Host-side checks of two index rules the pixel kernels rely on (rc_kernels.hip), restated in
+"""Host-side checks of two index rules the pixel kernels rely on (rc_pixel.hpp, rc_kernels.hip), restated in
 Python: the XCD-aware tile order must visit every tile exactly once, and the key-writer filter
 of phase A must keep every writer carry-out that the compaction (segment keys) or the row
 shards (in-row writer before a DEP pixel, a row's last writer) can read."""
@@ -7,7 +7,7 @@ import pytest
 
 
 def xcd_tile(lin, n, order):
-    """rc_kernels.hip xcd_tile(): tile index of linear workgroup id `lin` of `n`."""
+    """rc_pixel.hpp xcd_tile(): tile index of linear workgroup id `lin` of `n`."""
     if order == 1:
         xcd, k, q, r = lin & 7, lin >> 3, n >> 3, n & 7
         return xcd * (q + 1) + k if xcd < r else r * (q + 1) + (xcd - r) * q + k

@@ -317,7 +317,7 @@ def test_lane_maps(n):
     for lane in range(64):
         k = lane & (n - 1)
         assert ((wx >> (4 * k)) & 15, (wy >> (4 * k)) & 15) == pts[k]
-    # the dense form's tile (rc_kernels.hip pat_lbw / pat_lbh)
+    # the dense form's tile (rc_sample_kernels.hip pat_lbw / pat_lbh)
     lbw, lbh = (7 - ln) // 2, (6 - ln) // 2
     assert (1 << lbw) * (1 << lbh) == 64 // n and lbw >= lbh
     assert (2 << lbw, 2 << lbh) == {2: (16, 8), 4: (8, 8), 8: (8, 4), 16: (4, 4)}[n]

@@ -1,7 +1,7 @@
 """Scrolling an accumulated view without a GPU (rc_accum_scroll_device): the numpy contract
 against states built from scratch on the oracle's image, every refusal of the entry point pinned
 byte for byte, and the layout: the ctypes argument list against the header and the exposed set's
-index mapping (rc_kernels.hip, scroll_rects and exposed_pixel) restated in Python.
+index mapping (rc_sample_kernels.hip, scroll_rects and exposed_pixel) restated in Python.
 
 The pan (-60, 30) of the 40 x 24 window cannot come from a window inside the 97 x 61 image (the
 origin moves by at most 57 columns), and the old window is no argument of the call: nothing is
@@ -264,7 +264,7 @@ def test_ctypes_arguments_match_the_header():
 
 
 def scroll_rects(w, h, dx, dy):
-    """rc_kernels.hip scroll_rects(): the kept rectangle and the four exposed rectangles (rows
+    """rc_sample_kernels.hip scroll_rects(): the kept rectangle and the four exposed rectangles (rows
     above, columns left, columns right, rows below) as (first, width, x, y), and their total."""
     ax, ay = abs(dx), abs(dy)
     kx = ky = kw = kh = 0
@@ -283,7 +283,7 @@ def scroll_rects(w, h, dx, dy):
 
 
 def exposed_pixel(rects, e):
-    """rc_kernels.hip exposed_pixel(): the last rectangle whose first entry is at or below e."""
+    """rc_sample_kernels.hip exposed_pixel(): the last rectangle whose first entry is at or below e."""
     first, width, x0, y0 = rects[0]
     for k in range(1, 4):
         if e >= rects[k][0]:
