@@ -1,7 +1,8 @@
 # Build of the MI355X raycaster (gfx950) — everything in-tree.
 #
 #   make            libraycast_hip.so (HIP kernels + C-ABI), libraycast_front.so (host
-#                   scene parser / P3 writer), bin/raytrace (drop-in CLI), oracle
+#                   scene parser / P3 writer), bin/raytrace (drop-in CLI), oracle, primcheck
+#                   (tests/build/libprimcheck.so, the ray-level suite's device harness)
 #   make ref        oracle/_ref: the reference C/ sources compiled in place (test oracle)
 #
 # Numerics flags (parity with the x86-64 gcc -O3 reference):
@@ -29,8 +30,8 @@ HIP_SRCS  := $(SRC)/rc_kernels.hip $(SRC)/rc_sample_kernels.hip $(SRC)/rc_api.hi
 HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_pixel.hpp $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
 FRONT_SRC := $(SRC)/front/parse.c $(SRC)/front/objects.c $(SRC)/front/ppm.c
 
-.PHONY: all oracle ref clean stamps stamps2 sanitize
-all: $(LIB)/libraycast_hip.so $(LIB)/libraycast_front.so $(BIN)/raytrace oracle
+.PHONY: all oracle ref clean stamps stamps2 sanitize primcheck
+all: $(LIB)/libraycast_hip.so $(LIB)/libraycast_front.so $(BIN)/raytrace oracle primcheck
 
 $(OBJ)/%.o: $(SRC)/%.hip $(HIP_HDRS)
 	@mkdir -p $(OBJ)
@@ -88,7 +89,7 @@ ref:
 	$(MAKE) -C oracle ref
 
 clean:
-	rm -rf $(LIB) $(BIN)
+	rm -rf $(LIB) $(BIN) $(PRIM_OUT)
 	$(MAKE) -C oracle clean
 
 # measurement variants of the pixel kernels' framebuffer store (RC_HIP_LIB=libraycast_hip_<v>.so):
@@ -118,6 +119,16 @@ $(SAN_OUT)/oracle_raytrace: oracle/oracle_main.c oracle/rc_oracle.c oracle/rc_or
 $(SAN_OUT)/front_check: tests/tools/front_check.c $(FRONT_SRC) include/raycast_hip.h
 	@mkdir -p $(SAN_OUT)
 	$(CC) -O1 -ffp-contract=off $(SAN) -Iinclude -I$(SRC) tests/tools/front_check.c $(FRONT_SRC) -o $@ -lm -lpthread
+
+# Test-only device harness of the ray-level suite (tests/test_gpu_prims.py): the product's own
+# rc_device.hpp / rc_cudasem.hpp routines behind plain C entries, one thread per case, compiled
+# with the product's HIPFLAGS and fed by rc_pack_scene's records (rc_scene.o).  The product
+# library never links it.
+PRIM_OUT := tests/build
+primcheck: $(PRIM_OUT)/libprimcheck.so
+$(PRIM_OUT)/libprimcheck.so: tests/tools/prim_check.hip $(HIP_HDRS) $(OBJ)/rc_scene.o | oracle
+	@mkdir -p $(PRIM_OUT)
+	$(HIPCC) $(HIPFLAGS) -shared $(OBJ)/rc_scene.o tests/tools/prim_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
 
 # occupancy variants of the pixel kernels (RC_HIP_LIB=libraycast_hip_<v>.so): w3 = phase A /
 # k_render compiled for 3 waves per SIMD (no VGPR spills), f3 = phase C (k_dep_chunks, k_finish)

@@ -66,11 +66,18 @@ static void o_reflect(float *dst, const float *v, const float *n) {
 }
 
 /* --------------------------------------------------- intersections (C/raycast.c) -- */
+/* Diagnostics for the ray-level tests (rco_prim_*, below; not part of the reference's
+ * algorithm): which branch each shape test took.  Not thread-safe; read by the tests only. */
+rco_prim_counts rco_prim_g;
+
 /* C/raycast.c:545-562 */
 static int o_plane(const float *O, const float *D, const shape_t *s, float *t) {
   float sub[3] = {O[0] - s->position[0], O[1] - s->position[1], O[2] - s->position[2]};
   float num = o_dot(sub, s->normal);
   float den = o_dot(D, s->normal);
+  if (den == 0.0f) rco_prim_g.plane_den0++;
+  else if (fpclassify(den) == FP_SUBNORMAL) rco_prim_g.plane_den_sub++;
+  if (num == 0.0f) rco_prim_g.plane_num0++;
   if (den == 0.0f) return 0;
   float tt = (-num) / den;              /* -1 * num is exact negation */
   if (tt < 0.0f) return 0;
@@ -89,9 +96,10 @@ static int o_sphere(const float *O, const float *D, const shape_t *s, float *t) 
   float c = (float)((double)o_dot(tv, tv) - (double)s->radius * (double)s->radius);
   float fac = (4.0f * a) * c;
   float disc = (float)((double)b * (double)b - (double)fac);
-  if (disc < 0.0f) return 0;
+  if (disc < 0.0f) { rco_prim_g.disc_neg++; return 0; }
   double den = 2.0 * (double)a;
   float tt = (float)(((double)(-b) - pow((double)disc, 0.5)) / den);
+  if (tt < 0.0f) rco_prim_g.second_root++;
   if (tt < 0.0f) tt = (float)(((double)(-b) + pow((double)disc, 0.5)) / den);
   *t = tt;
   return 1;
@@ -113,8 +121,10 @@ static int o_quadric(const float *O, const float *D, const shape_t *q, float *t)
       (isnan(q->d * D[0] * D[1]) || isnan(q->e * D[0] * D[2]) || isnan(q->f * D[1] * D[2]) ||
        isnan(q->d * (O[0] * D[1] + O[1] * D[0])) || isnan(q->e * (O[0] * D[2] + O[2] * D[0])) ||
        isnan(q->f * (O[1] * D[2] + O[2] * D[1])) || isnan(q->d * O[0] * O[1]) ||
-       isnan(q->e * O[0] * O[2]) || isnan(q->f * O[1] * O[2])))
+       isnan(q->e * O[0] * O[2]) || isnan(q->f * O[1] * O[2]))) {
     g_cross_nan++;
+    rco_prim_g.cross_nan++;
+  }
   const double A = q->a, B = q->b, C = q->c;
   double acc;
   /* a_q (C/raycast.c:615-617) */
@@ -150,19 +160,57 @@ static int o_quadric(const float *O, const float *D, const shape_t *q, float *t)
   float cq = (float)acc;
 
   if ((double)aq == 0.0) {                                   /* C/raycast.c:640-642 */
+    rco_prim_g.linear++;
+    if (bq == 0.0f) rco_prim_g.linear_b0++;
     *t = (float)((-1.0 * (double)cq) / (double)bq);
     return 1;
   }
   float disc = (float)((double)bq * (double)bq - 4.0 * (double)aq * (double)cq);
-  if ((double)disc < 0.0) return 0;
+  if ((double)disc < 0.0) { rco_prim_g.disc_neg++; return 0; }
   double den = 2.0 * (double)aq;
   float tt = (float)(((double)(-bq) - pow((double)disc, 0.5)) / den);
+  if (tt <= 0.0f) rco_prim_g.second_root++;
   if (tt <= 0.0f) tt = (float)(((double)(-bq) + pow((double)disc, 0.5)) / den);
   *t = tt;
   return 1;
 }
 
 /* -------------------------------------------- nearest hit (C/raycast.c:441-531) -- */
+/* Hit point and normal of shape s at distance t (C/raycast.c:461-523): the body of the accept
+ * branch.  A zero length leaves N unnormalised, as in the source. */
+static void o_frame(octx *c, const shape_t *s, const float *O, const float *D, float t, float *P,
+                    float *N) {
+  float p0 = O[0] + D[0] * t, p1 = O[1] + D[1] * t, p2 = O[2] + D[2] * t;
+  P[0] = p0; P[1] = p1; P[2] = p2;
+  if (s->type == SPHERE) {                                   /* :465-469 */
+    float inv = (float)(1.0 / (double)s->radius);
+    N[0] = (p0 - s->position[0]) * inv;
+    N[1] = (p1 - s->position[1]) * inv;
+    N[2] = (p2 - s->position[2]) * inv;
+    o_normalize(c, N, N);
+  } else if (s->type == PLANE) {                             /* :484 */
+    N[0] = s->normal[0]; N[1] = s->normal[1]; N[2] = s->normal[2];
+  } else {                                                   /* :504-523 */
+    double n0 = 2.0 * (double)s->a * (double)p0;
+    n0 = n0 + (double)(s->d * p1);
+    n0 = n0 + (double)(s->e * p2);
+    n0 = n0 + (double)s->g;
+    double n1 = 2.0 * (double)s->b * (double)p1;
+    n1 = n1 + (double)(s->d * p0);
+    n1 = n1 + (double)(s->f * p2);
+    n1 = n1 + (double)s->h;
+    double n2 = 2.0 * (double)s->c * (double)p2;
+    n2 = n2 + (double)(s->e * p0);
+    n2 = n2 + (double)(s->f * p1);
+    n2 = n2 + (double)s->i;
+    N[0] = (float)n0; N[1] = (float)n1; N[2] = (float)n2;
+    o_normalize(c, N, N);
+    if (o_dot(N, D) > 0.0f) {
+      N[0] = N[0] * -1.0f; N[1] = N[1] * -1.0f; N[2] = N[2] * -1.0f;
+    }
+  }
+}
+
 static int o_nearest(octx *c, const float *O, const float *D, float *P, float *N, int skip,
                      int shadow) {
   float best = INFINITY, t = 0.0f;
@@ -191,35 +239,7 @@ static int o_nearest(octx *c, const float *O, const float *D, float *P, float *N
     best = t;
     idx = k;
     if (shadow) continue;
-    float p0 = O[0] + D[0] * best, p1 = O[1] + D[1] * best, p2 = O[2] + D[2] * best;
-    P[0] = p0; P[1] = p1; P[2] = p2;
-    if (s->type == SPHERE) {                                   /* :465-469 */
-      float inv = (float)(1.0 / (double)s->radius);
-      N[0] = (p0 - s->position[0]) * inv;
-      N[1] = (p1 - s->position[1]) * inv;
-      N[2] = (p2 - s->position[2]) * inv;
-      o_normalize(c, N, N);
-    } else if (s->type == PLANE) {                             /* :484 */
-      N[0] = s->normal[0]; N[1] = s->normal[1]; N[2] = s->normal[2];
-    } else {                                                   /* :504-523 */
-      double n0 = 2.0 * (double)s->a * (double)p0;
-      n0 = n0 + (double)(s->d * p1);
-      n0 = n0 + (double)(s->e * p2);
-      n0 = n0 + (double)s->g;
-      double n1 = 2.0 * (double)s->b * (double)p1;
-      n1 = n1 + (double)(s->d * p0);
-      n1 = n1 + (double)(s->f * p2);
-      n1 = n1 + (double)s->h;
-      double n2 = 2.0 * (double)s->c * (double)p2;
-      n2 = n2 + (double)(s->e * p0);
-      n2 = n2 + (double)(s->f * p1);
-      n2 = n2 + (double)s->i;
-      N[0] = (float)n0; N[1] = (float)n1; N[2] = (float)n2;
-      o_normalize(c, N, N);
-      if (o_dot(N, D) > 0.0f) {
-        N[0] = N[0] * -1.0f; N[1] = N[1] * -1.0f; N[2] = N[2] * -1.0f;
-      }
-    }
+    o_frame(c, s, O, D, best, P, N);
   }
   return idx;
 }
@@ -597,4 +617,117 @@ void rco_free_scene(json_data_t *js) {
   while (l) { light_t *n = l->next; free(l); l = n; }
   js->shapes_list = NULL;
   js->lights_list = NULL;
+}
+
+/* ------------------------------------------- ray-level exports (tests only) ------- */
+/* The static routines above, one case per array element (rc_oracle.h).  They run exactly the
+ * code the renders run; nothing here is part of the reference's algorithm. */
+shape_t *rco_prim_shapes(const json_data_t *js) {
+  const int n = js->num_shapes;
+  shape_t *sh = (shape_t *)calloc((size_t)(n > 0 ? n : 1), sizeof(shape_t));
+  if (!sh) return NULL;
+  const shape_t *s = js->shapes_list;
+  for (int k = 0; k < n; k++) {
+    if (!s) { free(sh); return NULL; }
+    sh[k] = *s;
+    s = s->next;
+  }
+  return sh;
+}
+
+/* the wrapper-level counters of one tested case */
+void rco_prim_count_case(rco_prim_counts *g, int type, int hit, float t) {
+  g->cases++;
+  if (type == SPHERE) g->sphere++;
+  else if (type == PLANE) g->plane++;
+  else g->quadric++;
+  if (!hit) return;
+  g->hits++;
+  if (t > 0.0f && t < INFINITY) g->accepted++;
+  else if (t != t) g->t_nan++;
+  else if (t == 0.0f) g->t_zero++;
+  else if (t == INFINITY || t == -INFINITY) g->t_inf++;
+  else g->t_neg++;
+}
+
+static int o_test(const shape_t *s, const float *O, const float *D, int skip, float *t) {
+  int hit = 0;
+  if (s->type == SPHERE) hit = o_sphere(O, D, s, t);
+  else if (s->type == PLANE) hit = o_plane(O, D, s, t);
+  else if (s->type == QUADRIC) {
+    hit = o_quadric(O, D, s, t);
+    /* C/raycast.c:492-494, as in o_nearest */
+    if (hit && skip != -1 && (O[2] + *t * D[2]) < O[2]) { rco_prim_g.z_rule++; hit = 0; }
+  }
+  return hit;
+}
+
+int rco_prim_shape(const json_data_t *js, int64_t n, const float *O, const float *D,
+                   const int32_t *shape, const int32_t *skip, int32_t *hit, float *t,
+                   rco_prim_counts *counts) {
+  shape_t *sh = rco_prim_shapes(js);
+  if (!sh) return -1;
+  memset(&rco_prim_g, 0, sizeof rco_prim_g);
+  for (int64_t i = 0; i < n; i++) {
+    if (shape[i] < 0 || shape[i] >= js->num_shapes) { free(sh); return -2; }
+    float tt = 0.0f;
+    const int h = o_test(&sh[shape[i]], &O[3 * i], &D[3 * i], skip[i], &tt);
+    hit[i] = h;
+    t[i] = h ? tt : 0.0f;
+    rco_prim_count_case(&rco_prim_g, sh[shape[i]].type, h, tt);
+  }
+  if (counts) *counts = rco_prim_g;
+  free(sh);
+  return 0;
+}
+
+int rco_prim_nearest(const json_data_t *js, int64_t n, const float *O, const float *D,
+                     const int32_t *skip, int shadow, int32_t *idx, float *t, float *P, float *N,
+                     int32_t *zero) {
+  rco_stats st;
+  octx c;
+  memset(&c, 0, sizeof c);
+  memset(&st, 0, sizeof st);
+  shape_t *sh = rco_prim_shapes(js);
+  if (!sh) return -1;
+  c.st = &st;
+  c.shapes = sh;
+  c.n = js->num_shapes;
+  for (int64_t i = 0; i < n; i++) {
+    float p[3] = {0.0f, 0.0f, 0.0f}, nn[3] = {0.0f, 0.0f, 0.0f};
+    const int64_t z0 = st.zero_normalize;
+    const int k = o_nearest(&c, &O[3 * i], &D[3 * i], p, nn, skip[i], shadow);
+    idx[i] = k;
+    /* o_nearest keeps its best t to itself: the winner's test again gives the same value */
+    float tt = 0.0f;
+    if (k >= 0) o_test(&sh[k], &O[3 * i], &D[3 * i], skip[i], &tt);
+    t[i] = tt;
+    if (!shadow) {
+      for (int j = 0; j < 3; j++) { P[3 * i + j] = p[j]; N[3 * i + j] = nn[j]; }
+      zero[i] = (int32_t)(st.zero_normalize - z0);
+    }
+  }
+  free(sh);
+  return 0;
+}
+
+int rco_prim_frame(const json_data_t *js, int64_t n, const int32_t *shape, const float *O,
+                   const float *D, const float *t, float *P, float *N, int32_t *zero) {
+  rco_stats st;
+  octx c;
+  memset(&c, 0, sizeof c);
+  memset(&st, 0, sizeof st);
+  shape_t *sh = rco_prim_shapes(js);
+  if (!sh) return -1;
+  c.st = &st;
+  for (int64_t i = 0; i < n; i++) {
+    if (shape[i] < 0 || shape[i] >= js->num_shapes) { free(sh); return -2; }
+    const int64_t z0 = st.zero_normalize;
+    P[3 * i] = P[3 * i + 1] = P[3 * i + 2] = 0.0f;
+    N[3 * i] = N[3 * i + 1] = N[3 * i + 2] = 0.0f;
+    o_frame(&c, &sh[shape[i]], &O[3 * i], &D[3 * i], t[i], &P[3 * i], &N[3 * i]);
+    zero[i] = (int32_t)(st.zero_normalize - z0);
+  }
+  free(sh);
+  return 0;
 }

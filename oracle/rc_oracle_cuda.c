@@ -25,6 +25,7 @@
 #include "rc_oracle.h"
 
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 typedef struct {
@@ -70,7 +71,7 @@ static int c_sphere(const float *O, const float *D, const shape_t *s, float *t) 
   float b = 2.0f * c_dot(D, tv);
   float c = c_dot(tv, tv) - s->radius * s->radius;
   float disc = b * b - (4.0f * a) * c;
-  if (disc < 0.0f) return 0;
+  if (disc < 0.0f) { rco_prim_g.disc_neg++; return 0; }
   double den = 2.0 * (double)a;
   float sq = c_sqrtf(disc);
   float tt = (float)((double)(-b - sq) / den);
@@ -123,11 +124,13 @@ static int c_quadric(const float *O, const float *D, const shape_t *q, float *t)
   cq = cq + q->j;
 
   if ((double)aq == 0.0) {                                     /* :517-519 */
+    rco_prim_g.linear++;
+    if (bq == 0.0f) rco_prim_g.linear_b0++;
     *t = (float)((-1.0 * (double)cq) / (double)bq);
     return 1;
   }
   float disc = (float)((double)(bq * bq) - 4.0 * (double)aq * (double)cq);
-  if ((double)disc < 0.0) return 0;
+  if ((double)disc < 0.0) { rco_prim_g.disc_neg++; return 0; }
   double den = 2.0 * (double)aq;
   float sq = c_sqrtf(disc);
   float tt = (float)((double)(-bq - sq) / den);
@@ -294,5 +297,58 @@ int rco_render_cuda(const json_data_t *js, int width, int height, int max_iter,
       px[2] = c_quant(col[2]);
     }
   }
+  return 0;
+}
+
+/* ------------------------------------------- ray-level exports (tests only) ------- */
+/* c_sphere / c_plane / c_quadric with the bounce rays' z rule, and c_nearest, one case per
+ * array element (rc_oracle.h; the C port's are in rc_oracle.c). */
+static int c_test(const shape_t *s, const float *O, const float *D, int skip, float *t) {
+  int hit = 0;
+  if (s->type == SPHERE) hit = c_sphere(O, D, s, t);
+  else if (s->type == PLANE) hit = c_plane(O, D, s, t);
+  else if (s->type == QUADRIC) {
+    hit = c_quadric(O, D, s, t);
+    if (hit && skip != -1 && (O[2] + *t * D[2]) < O[2]) { rco_prim_g.z_rule++; hit = 0; }
+  }
+  return hit;
+}
+
+int rco_prim_shape_cuda(const json_data_t *js, int64_t n, const float *O, const float *D,
+                        const int32_t *shape, const int32_t *skip, int32_t *hit, float *t,
+                        rco_prim_counts *counts) {
+  shape_t *sh = rco_prim_shapes(js);
+  if (!sh) return -1;
+  memset(&rco_prim_g, 0, sizeof rco_prim_g);
+  for (int64_t i = 0; i < n; i++) {
+    if (shape[i] < 0 || shape[i] >= js->num_shapes) { free(sh); return -2; }
+    float tt = 0.0f;
+    const int h = c_test(&sh[shape[i]], &O[3 * i], &D[3 * i], skip[i], &tt);
+    hit[i] = h;
+    t[i] = h ? tt : 0.0f;
+    rco_prim_count_case(&rco_prim_g, sh[shape[i]].type, h, tt);
+  }
+  if (counts) *counts = rco_prim_g;
+  free(sh);
+  return 0;
+}
+
+int rco_prim_nearest_cuda(const json_data_t *js, int64_t n, const float *O, const float *D,
+                          const int32_t *skip, int shadow, int32_t *idx, float *t) {
+  cctx c;
+  shape_t *sh = rco_prim_shapes(js);
+  if (!sh) return -1;
+  memset(&c, 0, sizeof c);
+  c.shapes = sh;
+  c.n = js->num_shapes;
+  for (int64_t i = 0; i < n; i++) {
+    float p[3], nn[3];
+    const int k = c_nearest(&c, &O[3 * i], &D[3 * i], p, nn, skip[i], shadow);
+    idx[i] = k;
+    float tt = 0.0f;
+    if (k >= 0) c_test(&sh[k], &O[3 * i], &D[3 * i], skip[i], &tt);
+    t[i] = tt;
+  }
+  free(sh);
   return 0;
 }

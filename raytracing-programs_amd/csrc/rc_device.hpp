@@ -82,11 +82,16 @@ __device__ __forceinline__ V3 sub(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, 
 // r = n - d*q0 and q = q0 + r*y, each rounded once) without its v_div_scale / v_div_fmas /
 // v_div_fixup steps, which change nothing unless an operand is extreme: they rescale only for
 // |n| < 2^-969, |d| > 2^1021 or exponent gaps beyond 768, and fix up zero, inf and NaN
-// operands.  The tests' operands are float-derived (|n| in [2^-201, 2^130] or 0, |d| in
-// [2^-148, 2^130]), so every finite quotient is bit-identical to n / d; where n or d is 0, inf
-// or NaN the value differs (NaN or an unsigned zero instead of +-inf or -0) but such a t is
-// rejected either way (t > 0 and t < inf; a zero or infinite denominator never yields an
-// accepted root), which is all the callers use it for.
+// operands.  The tests' operands are float-derived (|n| in [2^-201, 2^130] or 0; |d| in
+// [2^-149, 2^130]: 2 * (double)a, or the linear branch's (double)b_q, which can be the smallest
+// subnormal float — a float widened is a normal double or zero, never a subnormal one), so
+// every finite quotient is bit-identical to n / d; where n or d is 0, inf or NaN the value
+// differs (NaN or an unsigned zero instead of +-inf or -0) but such a t is rejected either way
+// (t > 0 and t < inf; a zero or infinite denominator never yields an accepted root), which is
+// all the callers use it for.
+// Backed ray by ray by the `division` family of tests/test_gpu_prims.py: every
+// float exponent of d, numerators down to 2^-201, and quotients constructed to sit on a rounding
+// midpoint to within 2^-54 ulp, every bit against IEEE n / d.
 #ifndef RC_NRDIV
 #define RC_NRDIV 1
 #endif
@@ -107,6 +112,9 @@ __device__ __forceinline__ double div_nr(double n, double d, double y) {
 // on here: sums of squares of floats (0 or >= 2^-298) and non-negative floats widened to
 // double (0 or >= 2^-149).  This is the compiler's own rsq + Goldschmidt/Newton sequence
 // without its range scaling, which it applies only below 2^-767, so results are identical.
+// Backed by the `sqrt` family of tests/test_gpu_prims.py: every binade from
+// 2^-767 up, perfect squares and their neighbours, roots constructed to sit on a rounding
+// midpoint to within 2^-43 ulp.
 __device__ __forceinline__ double sqrt_ns(double s) {
   const double y = __builtin_amdgcn_rsq(s);
   double g = s * y, h = y * 0.5;
@@ -130,7 +138,8 @@ __device__ __forceinline__ double sumsq3(double x, double y, double z) {
 // Discriminants b*b - p with b a float and p an exact double product (4*a*c of floats, or a
 // float widened): b*b is exact too, so fma(b, b, -p) rounds the same difference once.
 
-// C/v3math.c:169-172 — (float)sqrt of an exact double sum of squares
+// C/v3math.c:169-172 — (float)sqrt of an exact double sum of squares (sumsq3 and this: the
+// `length / div3` family of tests/test_gpu_prims.py, components over 2^-149 .. 2^127)
 __device__ __forceinline__ float length(V3 a) {
   return (float)sqrt_ns(sumsq3((double)a.x, (double)a.y, (double)a.z));
 }
@@ -140,7 +149,8 @@ __device__ __forceinline__ float length(V3 a) {
 // of two 24-bit floats is either a float or at least 2^-49 (relative) away from every
 // rounding midpoint of the float grid, so RN32(q) = RN32(a_i/len), the IEEE f32 quotient.
 // len = +inf: r = 0 gives a_i/inf (+-0, NaN for inf a_i); len NaN gives NaN; len = 0 is the
-// caller's case.
+// caller's case.  (The `length / div3` family of tests/test_gpu_prims.py: every bit against the
+// float32 quotient, arbitrary (a, len) pairs, exact quotients, len = inf and NaN.)
 __device__ __forceinline__ V3 div3(V3 a, float len) {
   const double L = (double)len;
   double r = __builtin_amdgcn_rcp(L);
@@ -208,6 +218,11 @@ __device__ __forceinline__ double dd_round(DD a) { return a.hi + a.lo; }
 
 // pow(x, 20) for the specular term (C/raycast.c:755-757); x = (double)float, so x*x is
 // exact in double and x^20 = (x^2)^8 * (x^2)^2 is built in double-double and rounded once.
+// The reference calls libm's pow, which is NOT the exactly rounded power for every input; the
+// `pow20` / `pown` families of tests/test_gpu_prims.py pin both facts parity rests on: this value
+// is within one ulp of the exact power (it equalled it on every input tried), and narrowed the
+// way shade narrows it — (float)((double)sl * p), (float)p for the spot term — it equals the
+// same expression formed with libm's pow (DESIGN.md §19 has the counts).
 __device__ __forceinline__ double pow20(double x) {
   double x2 = x * x;                  // exact: x has 24 significant bits
   DD x4 = dd_from_prod(x2, x2);       // exact
@@ -310,6 +325,9 @@ __device__ __forceinline__ bool hit_plane(V3 O, V3 D, const rc_shape& s, float& 
 // makes a, b or c NaN, and then every branch of the test ends in t = NaN, which every caller
 // rejects (best > t, t > 0, quot_class).  So the short form plus one per-ray flag —
 // x0_reject: some cross term would be NaN, the quadric is rejected — is bit-identical.
+// Backed by the `nonfinite` and `branches` families of tests/test_gpu_prims.py: every x0 form
+// against the oracle's full expression, inf / NaN rays and |O| near 3e38 (overflowing cross sums)
+// included, and x0_reject itself against the oracle's own NaN condition.
 __device__ __forceinline__ bool quad_x0(const Scene& sc) { return sc.has_quadric == 2; }
 __device__ __forceinline__ bool nonfinite3(float a, float b, float c) {
   return !__builtin_isfinite(a) | !__builtin_isfinite(b) | !__builtin_isfinite(c);
@@ -426,6 +444,7 @@ __device__ __forceinline__ int nearest(const Scene& sc, V3 O, V3 D, int skip, fl
 // ((g*Dx + h*Dy) + i*Dz) up to the sign of a zero result — which no caller can see: b enters
 // disc only squared, a zero disc makes both roots +-0 (rejected by t > 0), and the linear
 // case's c / +-0 is +-inf or NaN (rejected by best > t / t > 0 alike).
+// Backed by the `primary` family of tests/test_gpu_prims.py (O = +0, every other family's D).
 __device__ __forceinline__ bool hit_sphere_o0(V3 D, const rc_shape& s, RayK k, float& t) {
   const V3 tv = v3(0.0f - s.p[0], 0.0f - s.p[1], 0.0f - s.p[2]);
   float b = 2.0f * dot(D, tv);
@@ -512,6 +531,9 @@ __device__ __forceinline__ int nearest_primary(const Scene& sc, V3 D, float& tbe
 // bounds representable) keep inside [2^-149, 2^127] — a non-zero finite float of the
 // quotient's sign.  Anything else (a zero, subnormal, inf or NaN operand, or an extreme
 // ratio) takes the division as written.  Saves one or two f64 divisions per shadow test.
+// Backed by the `quot_class` family of tests/test_gpu_prims.py: exponent gaps -160 .. 140 with
+// the extreme mantissas on each side (126 is the last gap that cannot overflow: the same test
+// catches the bound 127), zero, subnormal, inf and NaN operands.
 constexpr int kQNeg = 0, kQZero = 1, kQPos = 2, kQOther = 3;   // t < 0, t = +-0, 0<t<inf, inf/NaN
 __device__ __forceinline__ int quot_class(double num, double den) {
   const unsigned hn = (unsigned)__double2hiint(num), hd = (unsigned)__double2hiint(den);
@@ -1048,6 +1070,10 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 // the same order as hit_sphere / hit_plane / hit_quadric, so results are bit-identical.
 // The plane's f32 quotient (-num)/den is taken as (float)((double)(-num) / (double)den):
 // double rounding is innocuous for division when 53 >= 2*24 + 2.
+// "The same operations in the same order" is tested ray by ray: tests/test_gpu_prims.py runs
+// test_unified<false>, <true, false> and <true, true> and hit_frame_sel on every family's cases
+// (tangent rays, origins on the surface, the linear branch, the plane's edges, non-finite rays)
+// against the oracle, like hit_*, hit_*_o0, the shadow forms and cu_test.
 
 // test_shape() for any type, branch-free.  kQuad = false: the scene has no quadric, so the
 // quadric part is compiled out (every quadric term below is dead).
