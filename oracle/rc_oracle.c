@@ -69,6 +69,8 @@ static void o_reflect(float *dst, const float *v, const float *n) {
 /* Diagnostics for the ray-level tests (rco_prim_*, below; not part of the reference's
  * algorithm): which branch each shape test took.  Not thread-safe; read by the tests only. */
 rco_prim_counts rco_prim_g;
+/* ... and what each shade and each bounce loop met (rco_prim_shade / rco_prim_shoot) */
+rco_shade_counts rco_shade_g;
 
 /* C/raycast.c:545-562 */
 static int o_plane(const float *O, const float *D, const shape_t *s, float *t) {
@@ -249,9 +251,11 @@ static void o_shade(octx *c, float *out, int idx, const float *P, const float *N
                     const float *D) {
   const shape_t *o = (idx >= 0) ? &c->shapes[idx] : &c->phantom;
   if (idx < 0) c->st->phantom_shades++;
+  rco_shade_g.shades++;
+  if (idx < 0) rco_shade_g.phantom++;
   float opacity = (float)((1.0 - (double)o->reflectivity) - (double)o->refractivity);
   out[0] = out[1] = out[2] = 0.0f;
-  if (!(opacity > 0.0f)) return;
+  if (!(opacity > 0.0f)) { rco_shade_g.opacity_le0++; return; }
   if (idx < 0 && !c->phantom_defined) c->st->parity_defined = 0;
   c->st->shaded_hits++;
   for (int l = 0; l < c->m; l++) {
@@ -259,7 +263,9 @@ static void o_shade(octx *c, float *out, int idx, const float *P, const float *N
     float ld[3] = {L->position[0] - P[0], L->position[1] - P[1], L->position[2] - P[2]};
     float dist = o_length(ld);
     o_normalize(c, ld, ld);
-    if (o_nearest(c, P, ld, NULL, NULL, idx, 1) != -1) continue;   /* in shadow */
+    rco_shade_g.lights++;
+    if (dist == 0.0f) rco_shade_g.dist0++;
+    if (o_nearest(c, P, ld, NULL, NULL, idx, 1) != -1) { rco_shade_g.shadowed++; continue; }
     c->st->light_evals++;
     /* radial attenuation C/raycast.c:666-669 */
     float lin = L->radial_coef[0] + L->radial_coef[1] * dist;
@@ -273,10 +279,19 @@ static void o_shade(octx *c, float *out, int idx, const float *P, const float *N
       float alpha = o_dot(v, L->direction);
       if (alpha < L->cos_theta) ang = 0.0f;
       else ang = (float)pow((double)alpha, (double)L->a0);
+      rco_shade_g.spot++;
+      if (alpha < L->cos_theta) rco_shade_g.cone_out++;
+      else if (alpha < 0.0f) rco_shade_g.alpha_neg_in++;
+      if (alpha == L->cos_theta) rco_shade_g.alpha_eq_cos++;
+      if (alpha == 0.0f) rco_shade_g.alpha_zero++;
     }
+    if (!isfinite(rad)) rco_shade_g.rad_nonfinite++;
+    if (!isfinite(ang)) rco_shade_g.ang_nonfinite++;
     /* diffuse C/raycast.c:708-720 and specular C/raycast.c:733-758 */
     float dif[3] = {0, 0, 0}, spe[3] = {0, 0, 0};
     float th = o_dot(N, ld);
+    if (th <= 0.0f) rco_shade_g.th_le0++;
+    else if (th != th) rco_shade_g.th_nan++;
     if (!(th <= 0.0)) {   /* C/raycast.c:713,740: a NaN theta is not <= 0 */
       for (int k = 0; k < 3; k++) dif[k] = (o->diffuse_color[k] * L->color[k]) * th;
       float view[3] = {D[0] * -1.0f, D[1] * -1.0f, D[2] * -1.0f};
@@ -284,6 +299,9 @@ static void o_shade(octx *c, float *out, int idx, const float *P, const float *N
       o_reflect(r, ld, N);
       double angle = (double)o_dot(view, r);
       if (!(angle > 0.0)) {
+        rco_shade_g.specular++;
+        if (angle != angle) rco_shade_g.spec_arg_nan++;
+        else if (fabs(angle) > rco_shade_g.spec_arg_max) rco_shade_g.spec_arg_max = fabs(angle);
         double p20 = pow(angle, 20.0);
         for (int k = 0; k < 3; k++)
           spe[k] = (float)((double)(o->specular_color[k] * L->color[k]) * p20);
@@ -303,7 +321,8 @@ static void o_shoot(octx *c, const float *d, int maxrec, int mode, float *out, p
   out[0] = out[1] = out[2] = 0.0f;
   pi->dep = 0; pi->wrote = 0;
   int i0 = o_nearest(c, (const float[3]){0.0f, 0.0f, 0.0f}, d, P0, N0, -1, 0);
-  if (i0 < 0) return;                                          /* :328-331 */
+  rco_shade_g.shoots++;
+  if (i0 < 0) { rco_shade_g.primary_miss++; return; }          /* :328-331 */
 
   int obj = i0, S = i0;
   float O[3] = {P0[0], P0[1], P0[2]};
@@ -311,18 +330,21 @@ static void o_shoot(octx *c, const float *d, int maxrec, int mode, float *out, p
   float N[3] = {N0[0], N0[1], N0[2]};
   float T = c->shapes[i0].reflectivity;
   float col[3];
-  for (int lvl = 1; lvl < maxrec; lvl++) {                     /* :348-376 */
-    if (!(c->shapes[obj].reflectivity > 0.0f)) break;
+  int lvl;
+  for (lvl = 1; lvl < maxrec; lvl++) {                         /* :348-376 */
+    if (!(c->shapes[obj].reflectivity > 0.0f)) { rco_shade_g.end_nonrefl++; break; }
     c->st->bounce_iters++;
+    rco_shade_g.bounce_iters++;
     float r[3];
     o_reflect(r, D, N);
     o_normalize(c, r, r);
     D[0] = r[0]; D[1] = r[1]; D[2] = r[2];
     int i = o_nearest(c, O, D, c->carry, N, S, 0);            /* writes the carry on hit */
     if (i < 0) {
-      if (mode == RCO_MODE_FAST) break;                        /* CUDA/raycast.cu:224-237 */
+      if (mode == RCO_MODE_FAST) { rco_shade_g.end_miss++; break; }   /* CUDA/raycast.cu:224-237 */
       if (lvl == 1) {                                          /* reads another pixel's carry */
         pi->dep = 1;
+        rco_shade_g.dep++;
         if (cin) { cin[0] = c->carry[0]; cin[1] = c->carry[1]; cin[2] = c->carry[2]; }
       }
     } else {
@@ -336,6 +358,7 @@ static void o_shoot(octx *c, const float *d, int maxrec, int mode, float *out, p
     O[0] = c->carry[0]; O[1] = c->carry[1]; O[2] = c->carry[2];
     S = i;
   }
+  if (lvl >= maxrec) rco_shade_g.end_maxrec++;
   o_shade(c, col, i0, P0, N0, d);                              /* :377-378 */
   out[0] = out[0] + col[0]; out[1] = out[1] + col[1]; out[2] = out[2] + col[2];
 }
@@ -387,6 +410,9 @@ static void o_build_phantom(octx *c) {
   c->phantom_defined = all || m == 0;   /* no lights: the shade is black regardless */
 }
 
+/* NOT thread-safe: o_shade / o_shoot bump the global test counters rco_shade_g (as the shape
+ * tests bump rco_prim_g) on every light and bounce of a render too.  A render that is ever run
+ * from several threads must give them a per-call home first. */
 int rco_render(const json_data_t *js, int width, int height, int max_recursion, int mode,
                uint8_t *pixmap, rco_stats *stats, float *carry_in) {
   return rco_render_cls(js, width, height, max_recursion, mode, pixmap, stats, carry_in, NULL);
@@ -730,4 +756,73 @@ int rco_prim_frame(const json_data_t *js, int64_t n, const int32_t *shape, const
   }
   free(sh);
   return 0;
+}
+
+/* ------------------------------------------- hit-level exports (tests only) ------- */
+/* A render context as rco_render_cls sets it up: shapes, lights, phantom, carry (0,0,0). */
+static int o_open(octx *c, rco_stats *st, const json_data_t *js) {
+  memset(c, 0, sizeof *c);
+  memset(st, 0, sizeof *st);
+  c->st = st;
+  st->parity_defined = 1;
+  c->n = js->num_shapes;
+  c->m = js->num_lights;
+  shape_t *sh = rco_prim_shapes(js);
+  light_t *li = (light_t *)calloc((size_t)(c->m > 0 ? c->m : 1), sizeof(light_t));
+  if (!sh || !li) { free(sh); free(li); return -1; }
+  const light_t *l = js->lights_list;
+  for (int k = 0; k < c->m; k++) { if (!l) { free(sh); free(li); return -2; } li[k] = *l; l = l->next; }
+  c->shapes = sh;
+  c->lights = li;
+  o_build_phantom(c);
+  return 0;
+}
+static void o_close(octx *c) {
+  free((void *)c->shapes);
+  free((void *)c->lights);
+}
+
+int rco_prim_shade(const json_data_t *js, int64_t n, const int32_t *idx, const float *P,
+                   const float *N, const float *D, float *rgb, int32_t *zero,
+                   rco_shade_counts *counts) {
+  rco_stats st;
+  octx c;
+  int r = o_open(&c, &st, js);
+  if (r) return r;
+  memset(&rco_shade_g, 0, sizeof rco_shade_g);
+  for (int64_t i = 0; i < n; i++) {
+    if (idx[i] < -1 || idx[i] >= c.n) { o_close(&c); return -2; }
+    const int64_t z0 = st.zero_normalize;
+    o_shade(&c, &rgb[3 * i], idx[i], &P[3 * i], &N[3 * i], &D[3 * i]);
+    zero[i] = (int32_t)(st.zero_normalize - z0);
+  }
+  if (counts) *counts = rco_shade_g;
+  o_close(&c);
+  return 0;
+}
+
+int rco_prim_shoot(const json_data_t *js, int64_t n, const float *d, int max_recursion, int mode,
+                   const float *carry_in, float *rgb, uint8_t *cls, float *carry_out,
+                   int32_t *zero, rco_shade_counts *counts) {
+  rco_stats st;
+  octx c;
+  int r = o_open(&c, &st, js);
+  if (r) return r;
+  memset(&rco_shade_g, 0, sizeof rco_shade_g);
+  for (int64_t i = 0; i < n; i++) {
+    for (int k = 0; k < 3; k++) c.carry[k] = carry_in ? carry_in[3 * i + k] : 0.0f;
+    const int64_t z0 = st.zero_normalize;
+    pxinfo pi;
+    o_shoot(&c, &d[3 * i], max_recursion, mode, &rgb[3 * i], &pi, NULL);
+    for (int k = 0; k < 3; k++) carry_out[3 * i + k] = c.carry[k];
+    cls[i] = (uint8_t)(pi.dep ? (pi.wrote ? 3 : 2) : (pi.wrote ? 1 : 0));
+    zero[i] = (int32_t)(st.zero_normalize - z0);
+  }
+  if (counts) *counts = rco_shade_g;
+  o_close(&c);
+  return 0;
+}
+
+void rco_prim_quant(int64_t n, const float *c, uint8_t *q) {
+  for (int64_t i = 0; i < n; i++) q[i] = o_quant(c[i]);
 }

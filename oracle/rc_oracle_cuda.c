@@ -197,13 +197,16 @@ static void c_shade(const cctx *c, float *out, int idx, const float *P, const fl
   const shape_t *o = &c->shapes[idx];
   float opacity = (float)((1.0 - (double)o->reflectivity) - (double)o->refractivity);
   out[0] = out[1] = out[2] = 0.0f;
-  if (!(opacity > 0.0f)) return;
+  rco_shade_g.shades++;
+  if (!(opacity > 0.0f)) { rco_shade_g.opacity_le0++; return; }
   for (int l = 0; l < c->m; l++) {
     const light_t *L = &c->lights[l];
     float ld[3] = {L->position[0] - P[0], L->position[1] - P[1], L->position[2] - P[2]};
     float dist = c_length(ld);
     c_normalize(ld, ld);
-    if (c_nearest(c, P, ld, NULL, NULL, idx, 1) != -1) continue;
+    rco_shade_g.lights++;
+    if (dist == 0.0f) rco_shade_g.dist0++;
+    if (c_nearest(c, P, ld, NULL, NULL, idx, 1) != -1) { rco_shade_g.shadowed++; continue; }
     /* :544-546: float sum, double quotient */
     float den = L->radial_coef[0] + L->radial_coef[1] * dist;
     den = den + L->radial_coef[2] * (dist * dist);
@@ -215,9 +218,18 @@ static void c_shade(const cctx *c, float *out, int idx, const float *P, const fl
       float alpha = c_dot(v, L->direction);
       if (alpha < L->cos_theta) ang = 0.0f;
       else ang = (float)pow((double)alpha, (double)L->a0);
+      rco_shade_g.spot++;
+      if (alpha < L->cos_theta) rco_shade_g.cone_out++;
+      else if (alpha < 0.0f) rco_shade_g.alpha_neg_in++;
+      if (alpha == L->cos_theta) rco_shade_g.alpha_eq_cos++;
+      if (alpha == 0.0f) rco_shade_g.alpha_zero++;
     }
+    if (!isfinite(rad)) rco_shade_g.rad_nonfinite++;
+    if (!isfinite(ang)) rco_shade_g.ang_nonfinite++;
     float dif[3] = {0, 0, 0}, spe[3] = {0, 0, 0};
     float th = c_dot(N, ld);
+    if (th <= 0.0f) rco_shade_g.th_le0++;
+    else if (th != th) rco_shade_g.th_nan++;
     if (!(th <= 0.0)) {
       for (int k = 0; k < 3; k++) dif[k] = (o->diffuse_color[k] * L->color[k]) * th;
       float view[3] = {D[0] * -1.0f, D[1] * -1.0f, D[2] * -1.0f};
@@ -225,6 +237,9 @@ static void c_shade(const cctx *c, float *out, int idx, const float *P, const fl
       c_reflect(r, ld, N);
       double angle = (double)c_dot(view, r);
       if (!(angle > 0.0)) {                                    /* :632-634: powf(float, 20) */
+        rco_shade_g.specular++;
+        if (angle != angle) rco_shade_g.spec_arg_nan++;
+        else if (fabs(angle) > rco_shade_g.spec_arg_max) rco_shade_g.spec_arg_max = fabs(angle);
         float p20 = (float)pow(angle, 20.0);
         for (int k = 0; k < 3; k++) spe[k] = (o->specular_color[k] * L->color[k]) * p20;
       }
@@ -240,18 +255,21 @@ static void c_shoot(const cctx *c, const float *d, int max_iter, float *out) {
   out[0] = out[1] = out[2] = 0.0f;
   const float zero[3] = {0.0f, 0.0f, 0.0f};
   int i0 = c_nearest(c, zero, d, P0, N0, -1, 0);
-  if (i0 < 0) return;
+  rco_shade_g.shoots++;
+  if (i0 < 0) { rco_shade_g.primary_miss++; return; }
   int obj = i0, S = i0;
   float O[3] = {P0[0], P0[1], P0[2]}, D[3] = {d[0], d[1], d[2]}, N[3] = {N0[0], N0[1], N0[2]};
   float T = c->shapes[i0].reflectivity, col[3], P[3];
-  for (int iter = 0; iter < max_iter; iter++) {
-    if (!(c->shapes[obj].reflectivity > 0.0f)) break;
+  int iter;
+  for (iter = 0; iter < max_iter; iter++) {
+    if (!(c->shapes[obj].reflectivity > 0.0f)) { rco_shade_g.end_nonrefl++; break; }
+    rco_shade_g.bounce_iters++;
     float r[3];
     c_reflect(r, D, N);
     c_normalize(r, r);
     D[0] = r[0]; D[1] = r[1]; D[2] = r[2];
     int i = c_nearest(c, O, D, P, N, S, 0);
-    if (i < 0) break;                                          /* :236-238 */
+    if (i < 0) { rco_shade_g.end_miss++; break; }              /* :236-238 */
     obj = i;
     c_shade(c, col, i, P, N, D);
     col[0] = col[0] * T; col[1] = col[1] * T; col[2] = col[2] * T;
@@ -260,6 +278,7 @@ static void c_shoot(const cctx *c, const float *d, int max_iter, float *out) {
     O[0] = P[0]; O[1] = P[1]; O[2] = P[2];
     S = i;
   }
+  if (iter >= max_iter) rco_shade_g.end_maxrec++;
   c_shade(c, col, i0, P0, N0, d);                              /* :244-245 */
   out[0] = out[0] + col[0]; out[1] = out[1] + col[1]; out[2] = out[2] + col[2];
 }
@@ -273,6 +292,7 @@ static uint8_t c_quant(float v) {
   return (uint8_t)(int32_t)v;
 }
 
+/* NOT thread-safe: c_shade / c_shoot bump the global test counters rco_shade_g (rc_oracle.c). */
 int rco_render_cuda(const json_data_t *js, int width, int height, int max_iter,
                     uint8_t *pixmap) {
   if (width <= 0 || height <= 0 || max_iter < 0) return -1;
@@ -350,5 +370,41 @@ int rco_prim_nearest_cuda(const json_data_t *js, int64_t n, const float *O, cons
     t[i] = tt;
   }
   free(sh);
+  return 0;
+}
+
+/* c_shade / c_shoot one case per array element (rc_oracle.h), with rco_render_cuda's context */
+static int c_open(cctx *c, shape_t *shapes, light_t *lights, const json_data_t *js) {
+  c->shapes = shapes; c->lights = lights; c->n = 0; c->m = 0;
+  for (const shape_t *s = js->shapes_list; s && c->n < 256; s = s->next) shapes[c->n++] = *s;
+  for (const light_t *l = js->lights_list; l && c->m < 256; l = l->next) lights[c->m++] = *l;
+  return 0;
+}
+
+int rco_prim_shade_cuda(const json_data_t *js, int64_t n, const int32_t *idx, const float *P,
+                        const float *N, const float *D, float *rgb, rco_shade_counts *counts) {
+  shape_t shapes[256];
+  light_t lights[256];
+  cctx c;
+  c_open(&c, shapes, lights, js);
+  memset(&rco_shade_g, 0, sizeof rco_shade_g);
+  for (int64_t i = 0; i < n; i++) {
+    if (idx[i] < 0 || idx[i] >= c.n) return -2;
+    c_shade(&c, &rgb[3 * i], idx[i], &P[3 * i], &N[3 * i], &D[3 * i]);
+  }
+  if (counts) *counts = rco_shade_g;
+  return 0;
+}
+
+int rco_prim_shoot_cuda(const json_data_t *js, int64_t n, const float *d, int max_iter,
+                        float *rgb, rco_shade_counts *counts) {
+  shape_t shapes[256];
+  light_t lights[256];
+  cctx c;
+  if (max_iter < 0) return -1;
+  c_open(&c, shapes, lights, js);
+  memset(&rco_shade_g, 0, sizeof rco_shade_g);
+  for (int64_t i = 0; i < n; i++) c_shoot(&c, &d[3 * i], max_iter, &rgb[3 * i]);
+  if (counts) *counts = rco_shade_g;
   return 0;
 }

@@ -223,6 +223,15 @@ __device__ __forceinline__ double dd_round(DD a) { return a.hi + a.lo; }
 // is within one ulp of the exact power (it equalled it on every input tried), and narrowed the
 // way shade narrows it — (float)((double)sl * p), (float)p for the spot term — it equals the
 // same expression formed with libm's pow (DESIGN.md §19 has the counts).
+// DOMAIN: |x| <= 2^50, or NaN (which it returns).  Its argument is dot(-D, reflect(ld, N)) with
+// D and ld unit vectors (within rounding) or zero.  For a unit normal N that is |x| <= 3 (the
+// spheres', the quadrics' and most planes'); a plane's normal is used as the scene file wrote it,
+// and one of length k gives |x| <= 1 + 2 k^2 (example2's plane reaches 22).  Outside the domain
+// this is not pow: once x^20 overflows (|x| > 2^51.2) the error terms are inf - inf and the
+// result is NaN where pow gives inf — a plane normal longer than 2^25.  pown_dd below guards
+// the same thing; this one is on the hot path and is not guarded.  tests/test_shade_cases.py
+// asserts, with the oracle's values over every shading family, that shade's argument stays
+// inside the domain, and inside |x| <= 4 wherever the normals are unit ones.
 __device__ __forceinline__ double pow20(double x) {
   double x2 = x * x;                  // exact: x has 24 significant bits
   DD x4 = dd_from_prod(x2, x2);       // exact
@@ -232,7 +241,9 @@ __device__ __forceinline__ double pow20(double x) {
   return dd_round(x20);
 }
 
-// pow(a, n) for an integer spot exponent (C/raycast.c:695), a = (double)float.
+// pow(a, n) for an integer spot exponent (C/raycast.c:695), a = (double)float, |n| <= 64:
+// (float) of the value returned equals (float)pow(a, n) for EVERY such a — zero, infinite, NaN
+// and powers that overflow or underflow included (a NaN for a NaN).
 __device__ __forceinline__ double pown_dd(double a, int n) {
   if (n == 0) return 1.0;
   // a = (double)float: a and a*a are exact doubles (24 and 48 significant bits), which the
@@ -241,6 +252,27 @@ __device__ __forceinline__ double pown_dd(double a, int n) {
   if (n == 1) return a;
   if (n == 2) return a * a;
   unsigned e = n < 0 ? (unsigned)(-n) : (unsigned)n;
+  // The double-double loop below is the power only while every intermediate (a^|n| and its
+  // error term, ~2^-53 of it) stays a normal double: a zero or infinite a gives inf * 0 = NaN
+  // in its error terms, an overflowing square gives inf - inf, and a product that underflows
+  // loses the sign of its zero.  alpha is a dot product with the light's direction, which no
+  // reader normalises, so such an a is reachable (alpha == +-0 wherever P - L.pos is
+  // perpendicular to the direction and the cone is 90 degrees or wider).  With xa the unbiased
+  // exponent of a, |log2(a^n)| >= (|xa| + 1)|n| - 2|n|: above the bound it exceeds 772, far
+  // outside float's range, so (float)pow(a, n) is +-0 or +-inf there, as it is for a = +-0 and
+  // +-inf — pow's own special values (C11 F.10.4.4): magnitude inf for a big base with n > 0 or
+  // a small one with n < 0, else 0; negative for a negative base (-0 included) and odd n.  The
+  // DOUBLE returned here is that float's value, not the (tiny or huge) double power: every
+  // caller narrows it.  `pown` family of tests/test_gpu_prims.py: a = +-0, +-inf, NaN, 1e-30 ..
+  // 3e38 against every exponent, -64 and 64 included.
+  const unsigned ha = (unsigned)__double2hiint(a);
+  const int xb = (int)((ha >> 20) & 0x7ffu), xa = xb - 1023;
+  if (xb == 0 || xb == 0x7ff || (unsigned)((xa < 0 ? -xa : xa) + 1) * e > 900u) {
+    if (a != a) return a;
+    const bool big = xb == 0x7ff || (xb != 0 && xa >= 0);
+    const double mag = big == (n > 0) ? __builtin_inf() : 0.0;
+    return ((ha >> 31) & e & 1u) ? -mag : mag;
+  }
   DD base{a, 0.0}, acc{1.0, 0.0};
   while (e) {
     if (e & 1u) acc = dd_mul(acc, base);
@@ -673,16 +705,24 @@ __device__ __forceinline__ V3 shade(const Scene& sc, int idx, V3 P, V3 N, V3 D, 
     const float lin = L.r0 + L.r1 * dist;
     const float rad =
         (float)(1.0 / ((double)lin + (double)L.r2 * ((double)dist * (double)dist)));
-    // angular attenuation C/raycast.c:679-696.  v = normalize(P - L.pos): P - L.pos is -ld
-    // component for component (round-to-nearest is sign-symmetric), so v = -ld and
-    // alpha = -dot(ld, dir) exactly.  A zero-length ld (P on the light) is +0 in every
-    // component either way: then v = ld, and the reference counts a second zero event
-    // (only when the light is not shadowed: it is counted below, after the shadow test).
+    // angular attenuation C/raycast.c:679-696.  v = normalize(P - L.pos): a non-zero
+    // component of P - L.pos is the negated component of L.pos - P (round-to-nearest is
+    // sign-symmetric) and both are divided by the same dist, so v_i = -ld_i there.  A
+    // component that is exactly zero is NOT negated: x - x is +0 whichever way round, and so
+    // is (+-0) - (+-0) of equal signs; such a v_i is the difference's own zero (divided by
+    // dist it keeps its sign).  Nor is the dot product negated as a whole: products that
+    // cancel exactly sum to +0 in either sign convention.  Both matter only when alpha is +-0,
+    // which pow(alpha, odd n < 0) turns into +-inf.  A zero-length ld (P on the light) is the
+    // case of three zero components: v = P - L.pos unnormalised, and the reference counts a
+    // second zero event (only when the light is not shadowed: it is counted below, after the
+    // shadow test).
     float ang = 1.0f;
     const bool z = dist == 0.0f;
     if (L.type == RC_LIGHT_SPOT) {
-      const float a = dot(ld, v3(L.dir[0], L.dir[1], L.dir[2]));
-      const float alpha = z ? a : -a;
+      const V3 vr = v3(P.x - L.pos[0], P.y - L.pos[1], P.z - L.pos[2]);
+      const V3 v = v3(vr.x == 0.0f ? vr.x : -ld.x, vr.y == 0.0f ? vr.y : -ld.y,
+                      vr.z == 0.0f ? vr.z : -ld.z);
+      const float alpha = dot(v, v3(L.dir[0], L.dir[1], L.dir[2]));
       if (alpha < L.cos_theta) {
         ang = 0.0f;
       } else if (L.a0_kind == RC_A0_INT) {

@@ -816,6 +816,9 @@ POW20_SL = np.array([1.0, 0.5, 2.0, 0.1, 0.3, 0.7, 1.5, 4.0, 0.05, 3.3, 0.25, 0.
 POWN_EXPONENTS = list(range(-8, 0)) + list(range(3, 13)) + [20, 31]
 PROBE_EXPONENTS = [-1, -2, -3, -5, -9]      # scripts/spot_exp_probe.py's integer angular-a0 values
 PROBE_THETAS = [0.3, 0.9]
+POWN_EDGE_BASES = [0.0, INF, np.nan, 1e-30, 1e-10, 1e20, 1e30, 3e38, 1.4e-45, 1e-38, 2.0 ** -13,
+                   2.0 ** -14, 2.0 ** 13, 2.0 ** 14, 0.75, 1.0]     # and the negative of each
+POWN_EDGE_EXPONENTS = list(range(-64, 65))
 
 
 @functools.lru_cache(None)
@@ -833,7 +836,9 @@ def family_pow20():
 def family_pown():
     """(a, n): alpha = (double)float against every integer exponent of POWN_EXPONENTS, and the
     spot-exponent probe's cases (its integer exponents, alpha in [cos_theta, 1] for its thetas, with
-    the scene reader's cos_theta = (float)cos(theta * 180 / PI_f))."""
+    the scene reader's cos_theta = (float)cos(theta * 180 / PI_f)); then POWN_EDGE_BASES of both
+    signs (+-0, +-inf, NaN, 1e-30 .. 3e38, the two sides of pown_dd's range guard) against every
+    exponent -64 .. 64."""
     rng = np.random.default_rng(66)
     a = np.concatenate([rng.uniform(0.05, 1.0, 3000), rng.uniform(1.0, 2.0, 300),
                         -rng.uniform(0.05, 1.5, 300), np.ldexp(1.0, -np.arange(0, 16)),
@@ -844,12 +849,29 @@ def family_pown():
         deg = F32(F64(F32(th)) * (180.0 / F64(F32(3.141592654))))
         cos_theta = F32(np.cos(F64(deg)))
         al = np.concatenate([[cos_theta, 1.0], rng.uniform(min(cos_theta, 1.0), 1.0, 700)]).astype(F32)
-        al = al[al != 0]
         for n in PROBE_EXPONENTS:
             A.append(al), N.append(np.full(len(al), n, I32))
+    # the edges: alpha is a dot product with a direction nobody normalises, so it can be +-0 (P - L.pos
+    # perpendicular to the direction), huge, tiny, infinite or NaN — against every exponent the
+    # packer treats as an integer
+    edge = np.array(POWN_EDGE_BASES, F32)
+    edge = np.concatenate([edge, -edge])
+    ne = np.array(POWN_EDGE_EXPONENTS, I32)
+    A.append(np.repeat(edge, len(ne))), N.append(np.tile(ne, len(edge)))
     A, N = np.concatenate(A).astype(F64), np.concatenate(N)
     assert len(A) <= 1 << 17
     return A, N
+
+
+def pown_regular(a, n):
+    """Cases inside the range pown_dd states for its double-double product: a finite and non-zero,
+    (|x| + 1) |n| <= 900 for x = floor(log2 |a|), so that a^|n| and its error term are normal
+    doubles.  There the double itself is compared with the exactly rounded power.  Everywhere else
+    — zero, infinite and NaN bases, powers at least 2^772 from 1, all of which overflow or
+    underflow float — only the narrowed value is."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x = np.frexp(np.abs(a))[1] - 1
+        return np.isfinite(a) & (a != 0) & ((np.abs(x) + 1) * np.abs(n) <= 900)
 
 
 _libm = None
@@ -875,7 +897,8 @@ def exact_pow(x, n):
         k = int(k)
         fa = Fraction(float(a))
         if fa == 0:
-            out[i] = 0.0 * float(a) if k % 2 else 0.0
+            z = float(a) if k % 2 else 0.0                   # an odd power keeps the zero's sign
+            out[i] = z if k > 0 else np.copysign(INF, z)
             continue
         p = fa ** abs(k)
         p = 1 / p if k < 0 else p

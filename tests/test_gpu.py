@@ -561,6 +561,46 @@ def test_spot_exponents_beyond_references(a0, tmp_path):
                                       err_msg=f"a0={a0} {mode}")
 
 
+SPOT_ZERO_ALPHA_SCENE = (
+    "camera, width: 2.0, height: 2.03125\n"
+    "plane, normal: [0, 0, 1], diffuse_color: [0.6, 0.5, 0.4], position: [0, 0, -8], "
+    "reflectivity: 0\n"
+    "sphere, radius: 1.0, diffuse_color: [0.2, 0.7, 0.3], specular_color: [0.5, 0.5, 0.5], "
+    "position: [1.5, 0.25, -6], reflectivity: 0.3, refractivity: 0, ior: 1\n"
+    "light, color: [2e-5, 1.5e-5, 1e-5], radial-a2: 0.01, radial-a1: 0.0125, radial-a0: 0.0125, "
+    "position: [0, 0, -3], theta: 1.05, angular-a0: -3, direction: [-0, -1, -0]\n"
+    "light, color: [1.5, 1.2, 1.0], radial-a2: 0.01, radial-a1: 0.0125, radial-a0: 0.0125, "
+    "position: [5, 5, 0]\n")
+
+
+def test_spot_zero_alpha_negative_exponent(tmp_path):
+    """alpha == +-0 under a negative odd spot exponent: the reference's pow gives +-inf there
+    (white or black), which pown_dd has to give too.  The light sits at y = 0 and points straight
+    down; its cone is wider than 90 degrees (cos_theta < 0), so alpha = +-0 passes the cone test.
+    The camera's height is 65 / 32 and the image has 65 rows, so the middle row's rays have
+    d.y = +0 exactly and every hit point of that row lies in the plane through the light
+    perpendicular to its direction: v.y = P.y - L.y = +0 and alpha = (v.x * -0 + 0 * -1) + v.z * -0
+    = +0 on either side of the light (v.z < 0), so pow(+0, -3) = +inf and the wall's middle row
+    is white.  (L.y - P.y is +0 as well, not -0: negating a dot product with ld, the device's
+    earlier shortcut, gives alpha = -0 and -inf — black — where v.x < 0.)  The second light
+    gives the rest of the picture ordinary shades."""
+    path = tmp_path / "zero_alpha.scene"
+    path.write_text(SPOT_ZERO_ALPHA_SCENE)
+    s = rc.Scene.from_file(str(path))
+    light = s.js.lights_list.contents
+    assert light.cos_theta < 0 and light.a0 == -3.0
+    W, H = 64, 65
+    for mode in ("fast", "parity"):
+        want, st = oracle_render(s, W, H, 4, mode)
+        assert st["parity_defined"]
+        # the edge is in the picture: the wall's part of the middle row is saturated on both sides
+        # of the light (x < W / 2 and x > W / 2), and hardly a pixel of any other row is
+        white = (want[H // 2] == 255).all(1)
+        assert white[: W // 2].sum() >= W // 4 and white[W // 2:].sum() >= W // 8
+        assert (np.delete(want, H // 2, 0) == 255).all(2).sum() <= 4
+        np.testing.assert_array_equal(rc.render(s, W, H, depth=4, mode=mode), want, err_msg=mode)
+
+
 def test_concurrent_callers_one_device(scenes, table):
     """Host threads calling raycast()/rc_render on the same device at once (ctypes drops the
     GIL): the per-device lock serialises them on the shared workspace, the resolver's

@@ -28,7 +28,8 @@ INF = np.inf
 
 # tests/tools/prim_check.hip's enums
 OP = {n: k for k, n in enumerate(["div", "div_mut", "sqrt", "sqrt_mut", "length", "div3", "pow20",
-                                  "pown", "quot_class", "quot_class_mut", "x0_reject"])}
+                                  "pown", "quot_class", "quot_class_mut", "x0_reject", "quant",
+                                  "primary_dir", "pow_general"])}
 FORM = {n: k for k, n in enumerate(["test", "test_x0", "o0", "o0_x0", "shadow", "shadow_x0",
                                     "uni_noquad", "uni_quad", "uni_quad_x0", "cuda"])}
 LIST = {n: k for k, n in enumerate(["nearest", "primary", "shadowed", "cu_nearest", "cu_shadowed"])}
@@ -436,23 +437,29 @@ def test_pow20(hw):
 
 def test_pown(hw):
     """pown_dd(a, n), n in -8..-1, 3..12, 20, 31 and the spot-exponent probe's cases: (float)p equals
-    (float)pow(a, n) of libm; the double is within one ulp of the exactly rounded power."""
+    (float)pow(a, n) of libm; the double is within one ulp of the exactly rounded power.  The edge
+    bases (+-0, +-inf, NaN, 1e-30 .. 3e38) against every exponent -64 .. 64: (float)p equals
+    (float)pow(a, n) in every bit, the sign of a zero included (a NaN for a NaN); their doubles are
+    compared with the exact power where it is a normal double (pc.pown_regular)."""
     a, n = pc.family_pown()
     dev = np.zeros(len(a), F64)
     hw.scalar("pown", a, n, o0=dev)
     lm = pc.libm_pow(a, n.astype(F64))
-    ex = pc.exact_pow(a, n)
-    with np.errstate(over="ignore", under="ignore"):
+    reg = pc.pown_regular(a, n)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
         got, want = dev.astype(F32), lm.astype(F32)
-    bad = pc.bits32(got) != pc.bits32(want)
-    d_ex, l_ex = pc.ulp_distance(dev, ex), pc.ulp_distance(lm, ex)
-    print(f"[gpu_prims] pown: {len(a)} cases; device != exact rounding: {int((d_ex != 0).sum())}, "
-          f"libm != exact rounding: {int((l_ex != 0).sum())}, device != libm: "
-          f"{int((pc.bits64(dev) != pc.bits64(lm)).sum())}, narrowed mismatches: {int(bad.sum())}")
+    bad = ~same_bits32(got, want)
+    ex = pc.exact_pow(a[reg], n[reg])
+    d_ex, l_ex = np.zeros(len(a), np.int64), np.zeros(len(a), np.int64)
+    d_ex[reg], l_ex[reg] = pc.ulp_distance(dev[reg], ex), pc.ulp_distance(lm[reg], ex)
+    print(f"[gpu_prims] pown: {len(a)} cases, {int(reg.sum())} regular; device != exact rounding: "
+          f"{int((d_ex != 0).sum())}, libm != exact rounding: {int((l_ex != 0).sum())}, device != libm: "
+          f"{int((~same_bits64(dev, lm))[reg].sum())}, narrowed mismatches: {int(bad.sum())} "
+          f"({int(bad[~reg].sum())} of {int((~reg).sum())} edge cases)")
     for e in sorted(set(n.tolist())):
-        m = n == e
-        print(f"[gpu_prims]   n = {e}: {int(m.sum())} cases, device != exact {int((d_ex[m] != 0).sum())}, "
-              f"libm != exact {int((l_ex[m] != 0).sum())}")
+        m = (n == e) & reg
+        print(f"[gpu_prims]   n = {e}: {int(m.sum())} regular cases, device != exact "
+              f"{int((d_ex[m] != 0).sum())}, libm != exact {int((l_ex[m] != 0).sum())}")
     if bad.any():
         i = _first(bad)
         pytest.fail(f"pown_dd case {i}: a {_hex64(a[i])} n {n[i]} | device {_hex64(dev[i])} -> "

@@ -222,10 +222,31 @@ def test_pow_families():
     assert len(x) == 1 << 15 and x.min() == -1.0 and x.max() == 0.0
     a, n = pc.family_pown()
     assert len(a) <= 1 << 17
-    assert set(pc.POWN_EXPONENTS) | set(pc.PROBE_EXPONENTS) == set(n.tolist())
+    assert (set(pc.POWN_EXPONENTS) | set(pc.PROBE_EXPONENTS) | set(pc.POWN_EDGE_EXPONENTS)
+            == set(n.tolist()))
     assert set(pc.POWN_EXPONENTS) == set(list(range(-8, 0)) + list(range(3, 13)) + [20, 31])
+    assert set(pc.POWN_EDGE_EXPONENTS) == set(range(-64, 65))
     assert len(pc.POW20_SL) == 16
-    _report("pow", pow20_cases=len(x), pown_cases=len(a))
+    # the edge bases meet every exponent: +-0, +-inf, NaN, 1e-30, 1e-10, 1e20, 1e30, 3e38 and negatives
+    f = pc.F32
+    for b in (0.0, np.inf, 1e-30, 1e-10, 1e20, 1e30, 3e38):
+        for s in (1.0, -1.0):
+            m = (pc.bits64(a) == pc.bits64(np.array([f(s) * f(b)], np.float64))[0])
+            assert set(range(-64, 65)) <= set(n[m].tolist()), (s, b)
+    assert set(range(-64, 65)) <= set(n[np.isnan(a)].tolist())
+    # ... and libm says what pown_dd has to return there: overflow, underflow and signed zeros
+    reg = pc.pown_regular(a, n)
+    lm = pc.libm_pow(a[~reg], n[~reg].astype(np.float64))
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        nar = lm.astype(pc.F32)
+    kinds = dict(inf=int((nar == np.inf).sum()), neg_inf=int((nar == -np.inf).sum()),
+                 nan=int(np.isnan(nar).sum()), pos_zero=int(((nar == 0) & ~np.signbit(nar)).sum()),
+                 neg_zero=int(((nar == 0) & np.signbit(nar)).sum()))
+    assert all(v >= 100 for v in kinds.values()), kinds
+    # outside the regular cases the narrowed power is never an ordinary number but 1, +-a or a*a
+    odd = ~np.isin(n[~reg], (0, 1, 2)) & np.isfinite(nar) & (nar != 0)
+    assert not odd.any()
+    _report("pow", pow20_cases=len(x), pown_cases=len(a), pown_edge_cases=int((~reg).sum()), **kinds)
 
 
 def test_libm_pow_against_exact_rounding():

@@ -7,8 +7,12 @@
 // arrays to the device, makes ONE launch and copies the results back; it returns 0, a HIP
 // error code, or -2 for an argument it refuses (a shape index outside the scene).
 //
-// The three *_mut routines below are deliberately wrong copies of product routines:
+// The *_mut routines below are deliberately wrong copies of product routines:
 // the tests require the case lists to tell each of them from the reference.
+//
+// The hit-level entries (pc_shade, pc_shoot; tests/test_gpu_shading.py) run shade, cu_shade, the
+// bounce loops shoot<MODE> and shade_dep_cont the same way, with the scene's lights and colour
+// pairs set up as the library's upload_scene sets them up.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -17,6 +21,7 @@
 #include "raycast_hip.h"
 #include "rc_cudasem.hpp"
 #include "rc_device.hpp"
+#include "rc_pixel.hpp"
 #include "rc_scene.h"
 
 using namespace rc;
@@ -67,6 +72,11 @@ enum {
   kOpQuotClass,    // a = num, b = den (f64) -> o1 = class (i32)
   kOpQuotClassMut,
   kOpX0Reject,     // a = O (3 f32), b = D (3 f32) -> o1 = 0/1 (i32)
+  kOpQuant,        // a = c (f32) -> o1 = quant(c) (i32)
+  kOpPrimaryDir,   // a = hx, hy (2 f64), b = pw, ph (2 f32), x, y (2 i32) -> o0 = zero events (i32),
+                   //   o1 = primary_dir (3 f32)
+  kOpPowGeneral,   // a = alpha (f32), b = a0 (f32) -> o1 = (float)pow((double)alpha, (double)a0),
+                   //   the expression shade evaluates for a spot exponent that is no small integer
   kOpCount
 };
 
@@ -111,6 +121,23 @@ __global__ void k_scalar(int op, int n, const void* a, const void* b, void* o0, 
       oi[i] = x0_reject(v3(af[3 * i], af[3 * i + 1], af[3 * i + 2]),
                         v3(bf[3 * i], bf[3 * i + 1], bf[3 * i + 2])) ? 1 : 0;
       break;
+    case kOpQuant: oi[i] = (int)quant(af[i]); break;
+    case kOpPrimaryDir: {
+      Cam cam;
+      cam.hx = ad[2 * i];
+      cam.hy = ad[2 * i + 1];
+      cam.pw = bf[4 * i];
+      cam.ph = bf[4 * i + 1];
+      const int* bi = (const int*)b;
+      int ze = 0;
+      const V3 d = primary_dir(cam, bi[4 * i + 2], bi[4 * i + 3], ze);
+      ((int*)o0)[i] = ze;
+      of[3 * i] = d.x;
+      of[3 * i + 1] = d.y;
+      of[3 * i + 2] = d.z;
+      break;
+    }
+    case kOpPowGeneral: of[i] = (float)pow((double)af[i], (double)bf[i]); break;
     default: break;
   }
 }
@@ -224,6 +251,160 @@ __global__ void k_frame(Scene sc, int form, int n, const int* shape, const float
   zero[i] = ze;
 }
 
+// --------------------------------------------------------------------- shading --
+// shade with one of three deliberate mistakes (kMut: 1, 2, 3) — the arguments the product's
+// comments make, undone one at a time:
+//   1  `inert` without its two finiteness tests (an infinite or NaN attenuation times +-0 is NaN,
+//      and only the shadow ray decides whether the reference adds it)
+//   2  alpha = -dot(ld, dir): the dot product negated as a whole, zero components and all
+//   3  no second zero-normalize event for an unshadowed spot light with P on it
+template <int kMut>
+__device__ __forceinline__ V3 shade_mut(const Scene& sc, int idx, V3 P, V3 N, V3 D, int& zero_events) {
+  const rc_shape& o = sc.lshapes[idx];
+  const float opacity = o.opacity;
+  V3 out = v3(0.0f, 0.0f, 0.0f);
+  if (!(opacity > 0.0f)) return out;
+  const int skip = (idx == sc.n) ? -1 : idx;
+  const rc_shade_pair* pr = sc.lpairs + (size_t)idx * sc.m;
+  for (int l = 0; l < sc.m; ++l) {
+    const rc_light& L = sc.lights[l];
+    V3 ld = v3(L.pos[0] - P.x, L.pos[1] - P.y, L.pos[2] - P.z);
+    const float dist = length(ld);
+    if (dist == 0.0f) zero_events++;
+    else ld = div3(ld, dist);
+    const float lin = L.r0 + L.r1 * dist;
+    const float rad =
+        (float)(1.0 / ((double)lin + (double)L.r2 * ((double)dist * (double)dist)));
+    float ang = 1.0f;
+    const bool z = dist == 0.0f;
+    if (L.type == RC_LIGHT_SPOT) {
+      const V3 vr = v3(P.x - L.pos[0], P.y - L.pos[1], P.z - L.pos[2]);
+      const V3 v = v3(vr.x == 0.0f ? vr.x : -ld.x, vr.y == 0.0f ? vr.y : -ld.y,
+                      vr.z == 0.0f ? vr.z : -ld.z);
+      const V3 dir = v3(L.dir[0], L.dir[1], L.dir[2]);
+      const float alpha = kMut == 2 ? -dot(ld, dir) : dot(v, dir);
+      if (alpha < L.cos_theta) ang = 0.0f;
+      else if (L.a0_kind == RC_A0_INT) ang = (float)pown_dd((double)alpha, L.a0_int);
+      else ang = (float)pow((double)alpha, (double)L.a0);
+    }
+    const float th = dot(N, ld);
+    const bool fin = kMut == 1 || (__builtin_isfinite(rad) && __builtin_isfinite(ang));
+    const bool inert = th <= 0.0f && fin && !(z && L.type == RC_LIGHT_SPOT);
+    if (inert) continue;
+    if (shadowed(sc, P, ld, skip)) continue;
+    if (L.type == RC_LIGHT_SPOT && kMut != 3) zero_events += z ? 1 : 0;
+    float dr = 0.0f, dg = 0.0f, db = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f;
+    if (!(th <= 0.0f)) {
+      const rc_shade_pair& p = pr[l];
+      dr = p.dl[0] * th;
+      dg = p.dl[1] * th;
+      db = p.dl[2] * th;
+      const V3 view = v3(D.x * -1.0f, D.y * -1.0f, D.z * -1.0f);
+      const double angle = (double)dot(view, reflect(ld, N));
+      if (!(angle > 0.0)) {
+        const double p20 = pow20(angle);
+        sr = (float)((double)p.sl[0] * p20);
+        sg = (float)((double)p.sl[1] * p20);
+        sb = (float)((double)p.sl[2] * p20);
+      }
+    }
+    out.x = out.x + ((dr + sr) * rad) * ang;
+    out.y = out.y + ((dg + sg) * rad) * ang;
+    out.z = out.z + ((db + sb) * rad) * ang;
+  }
+  return v3(out.x * opacity, out.y * opacity, out.z * opacity);
+}
+
+enum {
+  kShade = 0,        // shade, records read from global memory
+  kShadeStaged,      // shade after stage_scene<true>: lshapes / lpairs in LDS, as the pixel kernels
+  kShadeCuda,        // cusem::cu_shade (no phantom, no events)
+  kShadeMutInert,    // shade_mut<1>
+  kShadeMutAlpha,    // shade_mut<2>
+  kShadeMutZero,     // shade_mut<3>
+  kShadeCount
+};
+
+// idx[i] == -1 is the phantom (record sc.n)
+template <bool kStage>
+__global__ void k_shade(Scene sc, int form, int n, const int* idx, const float* Pa, const float* Na,
+                        const float* Da, float* rgb, int* zero) {
+  __shared__ StageBuf<kStage> buf;
+  stage_scene<kStage>(sc, buf);   // every thread: it has a barrier
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int k = idx[i] < 0 ? sc.n : idx[i];
+  const V3 P = ld3(Pa, i), N = ld3(Na, i), D = ld3(Da, i);
+  int ze = 0;
+  V3 c = v3(0.0f, 0.0f, 0.0f);
+  switch (form) {
+    case kShade:
+    case kShadeStaged: c = shade(sc, k, P, N, D, ze); break;
+    case kShadeCuda: c = cusem::cu_shade(sc, k, P, N, D); break;
+    case kShadeMutInert: c = shade_mut<1>(sc, k, P, N, D, ze); break;
+    case kShadeMutAlpha: c = shade_mut<2>(sc, k, P, N, D, ze); break;
+    case kShadeMutZero: c = shade_mut<3>(sc, k, P, N, D, ze); break;
+    default: break;
+  }
+  rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+  zero[i] = ze;
+}
+
+enum {
+  kShootFast = 0,    // shoot<kModeFast>
+  kShootParityA,     // shoot<kModeParityA>: class; rgb and carry where the class is not DEP
+  kShootParityC,     // shoot<kModeParityC> from the case's carry-in
+  kShootClassify,    // shoot<kModeClassify>: class and carry only
+  kShootDepCont,     // shoot<kModeParityA>, then for a DEP pixel under dep_fast shade_dep_cont on
+                     //   the line phase A would have written, from the case's carry-in
+  kShootCount
+};
+
+// cls: the device's class (kClsIdent / kClsWriter / kClsDep); flag: 1 where kShootDepCont ran
+// shade_dep_cont.  carry_out: po.carry where the pixel wrote it, else the carry-in.
+__global__ void k_shoot(Scene sc, int form, int n, int maxrec, const float* da, const float* cin,
+                        float* rgb, int* cls, float* cout, int* zero, int* flag) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V3 d = ld3(da, i), c = ld3(cin, i);
+  PixelOut po;
+  po.carry = c;
+  int ze = 0, fl = 0;
+  switch (form) {
+    case kShootFast: shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, ze); break;
+    case kShootParityA: shoot<kModeParityA>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, ze); break;
+    case kShootParityC: shoot<kModeParityC>(sc, d, maxrec, c, po, ze); break;
+    case kShootClassify: shoot<kModeClassify>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, ze); break;
+    case kShootDepCont: {
+      shoot<kModeParityA>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, ze);
+      if (po.cls == kClsDep && sc.dep_fast) {
+        DepLine line;
+        line.r = po.dep;
+        line.px = po.pcol.x; line.py = po.pcol.y; line.pz = po.pcol.z;
+        line.pad3 = 0;
+        po.rgb = shade_dep_cont(sc, &line, maxrec, c, ze);
+        fl = 1;
+      }
+      break;
+    }
+    default: break;
+  }
+  const V3 co = po.cls == kClsWriter ? po.carry : c;
+  rgb[3 * i] = po.rgb.x; rgb[3 * i + 1] = po.rgb.y; rgb[3 * i + 2] = po.rgb.z;
+  cout[3 * i] = co.x; cout[3 * i + 1] = co.y; cout[3 * i + 2] = co.z;
+  cls[i] = po.cls;
+  zero[i] = ze;
+  flag[i] = fl;
+}
+
+// cusem::render_pixel takes a camera and a pixel, not a direction: pixel i = (xy[2i], xy[2i+1])
+__global__ void k_render_pixel(Scene sc, Cam cam, int n, int max_iter, const int* xy, float* rgb) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V3 c = cusem::render_pixel(sc, cam, xy[2 * i], xy[2 * i + 1], max_iter);
+  rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+}
+
 // ------------------------------------------------------------------- host side --
 struct PcScene {
   rc_packed_header* host;
@@ -258,8 +439,8 @@ struct Bufs {
     if (e_ != hipSuccess) return (int)e_; \
   } while (0)
 
-constexpr int kBlock = 256;
-inline int grid_of(int n) { return (n + kBlock - 1) / kBlock; }
+constexpr int kPcBlock = 256;
+inline int grid_of(int n) { return (n + kPcBlock - 1) / kPcBlock; }
 
 int finish() {
   PC_TRY(hipGetLastError());
@@ -279,9 +460,27 @@ Scene scene_of(const PcScene* s, int hq, int o0) {
   sc.shapes = (const rc_shape*)(s->dev + s->host->off_shapes);
   sc.lshapes = sc.shapes;
   sc.n = s->host->n;
-  sc.m = 0;   // nothing here shades: lights and pairs stay null
+  sc.m = 0;   // the intersection entries shade nothing: lights and pairs stay null
   sc.has_quadric = hq < 0 ? s->natural_hq : hq;
   sc.o0_ok = o0 < 0 ? s->host->o0_ok : o0;
+  return sc;
+}
+
+// The scene of the shading entries: lights, colour pairs, the reflectivity mask and dep_fast from
+// the packed image, restated here as upload_scene (rc_api.hip) states them.
+Scene lit_scene_of(const PcScene* s) {
+  Scene sc = scene_of(s, -1, -1);
+  const rc_packed_header* h = s->host;
+  sc.lights = (const rc_light*)(s->dev + h->off_lights);
+  sc.pairs = (const rc_shade_pair*)(s->dev + h->off_pairs);
+  sc.lpairs = sc.pairs;
+  sc.m = h->m;
+  const rc_shape* hs = (const rc_shape*)((const char*)h + h->off_shapes);
+  for (int k = 0; k < h->n && k < 64; ++k)
+    if (hs[k].refl > 0.0f) sc.refl_mask |= 1ull << k;
+  sc.dep_fast = !(hs[h->n].opacity > 0.0f);
+  for (int k = 0; k < h->n; ++k)
+    if (!(fabsf(hs[k].refl) < 1.0e5f)) sc.dep_fast = 0;
   return sc;
 }
 
@@ -336,7 +535,8 @@ int pc_scalar(int op, int n, const void* a, const void* b, void* o0, void* o1) {
   // bytes per case of a, b, o0, o1
   static const int kBytes[kOpCount][4] = {
       {8, 8, 8, 4}, {8, 8, 8, 4}, {8, 0, 8, 0}, {8, 0, 8, 0},  {12, 0, 0, 4}, {12, 4, 0, 12},
-      {8, 0, 8, 0}, {8, 4, 8, 0}, {8, 8, 0, 4}, {8, 8, 0, 4}, {12, 12, 0, 4}};
+      {8, 0, 8, 0}, {8, 4, 8, 0}, {8, 8, 0, 4}, {8, 8, 0, 4}, {12, 12, 0, 4},
+      {4, 0, 0, 4}, {16, 16, 4, 12}, {4, 4, 0, 4}};
   if (op < 0 || op >= kOpCount || n < 0) return -2;
   if (n == 0) return 0;
   const int a_bytes = kBytes[op][0], b_bytes = kBytes[op][1], o0_bytes = kBytes[op][2],
@@ -348,7 +548,7 @@ int pc_scalar(int op, int n, const void* a, const void* b, void* o0, void* o1) {
   PC_TRY(bf.get(&db, b_bytes ? b : nullptr, (size_t)n * b_bytes));
   PC_TRY(bf.get(&d0, nullptr, (size_t)n * o0_bytes));
   PC_TRY(bf.get(&d1, nullptr, (size_t)n * o1_bytes));
-  k_scalar<<<grid_of(n), kBlock>>>(op, n, da, db, d0, d1);
+  k_scalar<<<grid_of(n), kPcBlock>>>(op, n, da, db, d0, d1);
   if (int r = finish()) return r;
   if (o0_bytes) PC_TRY(hipMemcpy(o0, d0, (size_t)n * o0_bytes, hipMemcpyDeviceToHost));
   if (o1_bytes) PC_TRY(hipMemcpy(o1, d1, (size_t)n * o1_bytes, hipMemcpyDeviceToHost));
@@ -369,7 +569,7 @@ int pc_shape(const void* sp, int form, int n, const float* O, const float* D, co
   PC_TRY(bf.get(&dK, skip, (size_t)n * 4));
   PC_TRY(bf.get(&dH, nullptr, (size_t)n * 4));
   PC_TRY(bf.get(&dT, nullptr, (size_t)n * 4));
-  k_shape<<<grid_of(n), kBlock>>>((const rc_shape*)(s->dev + s->host->off_shapes), form, n,
+  k_shape<<<grid_of(n), kPcBlock>>>((const rc_shape*)(s->dev + s->host->off_shapes), form, n,
                                   (const float*)dO, (const float*)dD, (const int*)dS,
                                   (const int*)dK, (int*)dH, (float*)dT);
   if (int r = finish()) return r;
@@ -393,7 +593,7 @@ int pc_list(const void* sp, int form, int has_quadric, int o0_ok, int n, const f
   PC_TRY(bf.get(&dK, skip, (size_t)n * 4));
   PC_TRY(bf.get(&dI, nullptr, (size_t)n * 4));
   PC_TRY(bf.get(&dT, nullptr, (size_t)n * 4));
-  k_list<<<grid_of(n), kBlock>>>(scene_of(s, has_quadric, o0_ok), form, n, (const float*)dO,
+  k_list<<<grid_of(n), kPcBlock>>>(scene_of(s, has_quadric, o0_ok), form, n, (const float*)dO,
                                  (const float*)dD, (const int*)dK, (int*)dI, (float*)dT);
   if (int r = finish()) return r;
   PC_TRY(hipMemcpy(idx, dI, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -416,7 +616,7 @@ int pc_frame(const void* sp, int form, int n, const int* shape, const float* O, 
   PC_TRY(bf.get(&dP, nullptr, (size_t)n * 12));
   PC_TRY(bf.get(&dN, nullptr, (size_t)n * 12));
   PC_TRY(bf.get(&dZ, nullptr, (size_t)n * 4));
-  k_frame<<<grid_of(n), kBlock>>>(scene_of(s, -1, -1), form, n, (const int*)dS, (const float*)dO,
+  k_frame<<<grid_of(n), kPcBlock>>>(scene_of(s, -1, -1), form, n, (const int*)dS, (const float*)dO,
                                   (const float*)dD, (const float*)dT, (float*)dP, (float*)dN,
                                   (int*)dZ);
   if (int r = finish()) return r;
@@ -424,6 +624,105 @@ int pc_frame(const void* sp, int form, int n, const int* shape, const float* O, 
   PC_TRY(hipMemcpy(N, dN, (size_t)n * 12, hipMemcpyDeviceToHost));
   PC_TRY(hipMemcpy(zero, dZ, (size_t)n * 4, hipMemcpyDeviceToHost));
   return 0;
+}
+
+// One shading form (kShade*) for n hits: shape index (-1: the phantom), hit point, normal and ray
+// direction (3 floats each) -> the colour (3 floats) and the zero-normalize events.  -2: an index
+// outside the scene, the phantom under kShadeCuda, or kShadeStaged for a scene the pixel kernels
+// would not stage (stage_fits).
+int pc_shade(const void* sp, int form, int n, const int* idx, const float* P, const float* N,
+             const float* D, float* rgb, int* zero) {
+  const PcScene* s = (const PcScene*)sp;
+  if (!s || form < 0 || form >= kShadeCount || n < 0) return -2;
+  for (int i = 0; i < n; ++i)
+    if (idx[i] < (form == kShadeCuda ? 0 : -1) || idx[i] >= s->host->n) return -2;
+  const rc_packed_header* h = s->host;
+  if (form == kShadeStaged && !(h->n + 1 <= kStageShapes && (h->n + 1) * h->m <= kStagePairs))
+    return -2;
+  if (n == 0) return 0;
+  Bufs bf;
+  void *dI, *dP, *dN, *dD, *dC, *dZ;
+  PC_TRY(bf.get(&dI, idx, (size_t)n * 4));
+  PC_TRY(bf.get(&dP, P, (size_t)n * 12));
+  PC_TRY(bf.get(&dN, N, (size_t)n * 12));
+  PC_TRY(bf.get(&dD, D, (size_t)n * 12));
+  PC_TRY(bf.get(&dC, nullptr, (size_t)n * 12));
+  PC_TRY(bf.get(&dZ, nullptr, (size_t)n * 4));
+  if (form == kShadeStaged)
+    k_shade<true><<<grid_of(n), kPcBlock>>>(lit_scene_of(s), form, n, (const int*)dI, (const float*)dP,
+                                          (const float*)dN, (const float*)dD, (float*)dC, (int*)dZ);
+  else
+    k_shade<false><<<grid_of(n), kPcBlock>>>(lit_scene_of(s), form, n, (const int*)dI,
+                                           (const float*)dP, (const float*)dN, (const float*)dD,
+                                           (float*)dC, (int*)dZ);
+  if (int r = finish()) return r;
+  PC_TRY(hipMemcpy(rgb, dC, (size_t)n * 12, hipMemcpyDeviceToHost));
+  PC_TRY(hipMemcpy(zero, dZ, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// One bounce-loop form (kShoot*) for n primary directions d (3 floats) with carry-ins (3 floats):
+// the colour before quantisation, the device's class, the carry after the pixel, the
+// zero-normalize events and kShootDepCont's flag.  dep_fast: -1 = as the library derives it from
+// the scene, 0 = off.  maxrec: 1 .. 64.
+int pc_shoot(const void* sp, int form, int dep_fast, int n, int maxrec, const float* d,
+             const float* carry_in, float* rgb, int* cls, float* carry_out, int* zero, int* flag) {
+  const PcScene* s = (const PcScene*)sp;
+  if (!s || form < 0 || form >= kShootCount || n < 0 || maxrec < 1 || maxrec > 64 ||
+      dep_fast < -1 || dep_fast > 0)
+    return -2;
+  if (n == 0) return 0;
+  Scene sc = lit_scene_of(s);
+  if (dep_fast == 0) sc.dep_fast = 0;
+  Bufs bf;
+  void *dD, *dI, *dC, *dK, *dO, *dZ, *dF;
+  PC_TRY(bf.get(&dD, d, (size_t)n * 12));
+  PC_TRY(bf.get(&dI, carry_in, (size_t)n * 12));
+  PC_TRY(bf.get(&dC, nullptr, (size_t)n * 12));
+  PC_TRY(bf.get(&dK, nullptr, (size_t)n * 4));
+  PC_TRY(bf.get(&dO, nullptr, (size_t)n * 12));
+  PC_TRY(bf.get(&dZ, nullptr, (size_t)n * 4));
+  PC_TRY(bf.get(&dF, nullptr, (size_t)n * 4));
+  k_shoot<<<grid_of(n), kPcBlock>>>(sc, form, n, maxrec, (const float*)dD, (const float*)dI,
+                                  (float*)dC, (int*)dK, (float*)dO, (int*)dZ, (int*)dF);
+  if (int r = finish()) return r;
+  PC_TRY(hipMemcpy(rgb, dC, (size_t)n * 12, hipMemcpyDeviceToHost));
+  PC_TRY(hipMemcpy(cls, dK, (size_t)n * 4, hipMemcpyDeviceToHost));
+  PC_TRY(hipMemcpy(carry_out, dO, (size_t)n * 12, hipMemcpyDeviceToHost));
+  PC_TRY(hipMemcpy(zero, dZ, (size_t)n * 4, hipMemcpyDeviceToHost));
+  PC_TRY(hipMemcpy(flag, dF, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// cusem::render_pixel for n pixels (x, y) of the scene's W x H camera (the launchers' make_cam):
+// the colour before quantisation.  max_iter: 0 .. 64.
+int pc_render_pixel(const void* sp, int W, int H, int max_iter, int n, const int* xy, float* rgb) {
+  const PcScene* s = (const PcScene*)sp;
+  if (!s || W < 1 || H < 1 || max_iter < 0 || max_iter > 64 || n < 0) return -2;
+  if (n == 0) return 0;
+  Cam cam;
+  cam.hx = 0.0 - (double)s->host->cam_w / 2.0;
+  cam.hy = 0.0 + (double)s->host->cam_h / 2.0;
+  cam.pw = s->host->cam_w / (float)W;
+  cam.ph = s->host->cam_h / (float)H;
+  Bufs bf;
+  void *dX, *dC;
+  PC_TRY(bf.get(&dX, xy, (size_t)n * 8));
+  PC_TRY(bf.get(&dC, nullptr, (size_t)n * 12));
+  k_render_pixel<<<grid_of(n), kPcBlock>>>(lit_scene_of(s), cam, n, max_iter, (const int*)dX,
+                                           (float*)dC);
+  if (int r = finish()) return r;
+  PC_TRY(hipMemcpy(rgb, dC, (size_t)n * 12, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// m lights, dep_fast as lit_scene_of derives it, and whether the pixel kernels would stage the scene
+void pc_scene_lit_info(const void* sp, int* m, int* dep_fast, int* staged) {
+  const PcScene* s = (const PcScene*)sp;
+  const rc_packed_header* h = s->host;
+  *m = h->m;
+  *dep_fast = lit_scene_of(s).dep_fast;
+  *staged = h->n + 1 <= kStageShapes && (h->n + 1) * h->m <= kStagePairs;
 }
 
 }  // extern "C"
