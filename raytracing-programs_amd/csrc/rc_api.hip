@@ -72,7 +72,9 @@ rc_tuning default_tuning() {
   t.resolve_clean = 1;
   t.shard_lone = 1;
   t.team_cscan = 1;
-  t.pipe_order = 0;
+  // one phase C stream and each resolver lane beside an idle placeholder: 2.47 against 2.53-2.54
+  // ms per step at quadric 4096^2 with either phase C (profiles/pinned_ab.txt)
+  t.pipe_order = 4;
   t.pipe_helpers = 4;   // round 4: frames in flight 6.70-6.81e9 -> 6.83-6.90e9 at C4, C5 / C3 /
                         // simple 1024^2 +0.8 / +1.2 / +2.3 % (profiles/r04q_pipe_helpers_*.txt)
   t.patch_host = 2;   // round 4: rc_render end to end 5.39-5.47 (0) -> 5.29-5.33 (1) -> 5.02-5.07 ms
@@ -90,6 +92,7 @@ rc_tuning default_tuning() {
   t.pipe_last_whole = 1;
   t.ssaa_fused = 1;
   t.adaptive_blocks = 0;
+  t.pin = 1;
   return t;
 }
 rc_tuning g_tune = default_tuning();
@@ -733,7 +736,7 @@ int rc_set_tuning(const rc_tuning* t) {
       in(t->resolve_clean, 1, 64) && in(t->shard_lone, 0, 1) && in(t->team_cscan, 0, 1) &&
       in(t->pipe_order, 0, 4) && in(t->pipe_helpers, 0, rc::kDenseSlots) &&
       in(t->patch_host, 0, 2) && in(t->share_device, 0, 1) && in(t->headb_first, 0, 1 << 16) && in(t->pipe_last_whole, 0, 1) &&
-      in(t->ssaa_fused, 0, 1) && in(t->adaptive_blocks, 0, 4096) &&
+      in(t->ssaa_fused, 0, 1) && in(t->adaptive_blocks, 0, 4096) && in(t->pin, 0, 3) &&
       !(t->split_shade && !t->side);
   if (!ok) {
     std::fprintf(stderr, "Error: rc_set_tuning: a field is out of range\n");
@@ -865,6 +868,8 @@ int upload_scene(FrameBufs& b, hipStream_t stream, const rc_scene* s, rc::Launch
   ls.dep_fast = !(hs[h->n].opacity > 0.0f) && tune().dep_fast;
   for (int k = 0; k < h->n; ++k)
     if (!(std::fabs(hs[k].refl) < 1.0e5f)) ls.dep_fast = 0;
+  // the carry-point table of phase C (rc_device.hpp pin_build): dep_fast scenes it has rows for
+  ls.pin = ls.dep_fast && RC_PIN_FITS(h->n, h->m) ? (tune().pin & 1) : 0;
   return 0;
 }
 
@@ -1265,7 +1270,7 @@ int enqueue_render_ws(DevCtx& c, const rc_scene* s, int W, int H, int row0, int 
     std::fprintf(stderr, "Error: out of device memory for the parity workspace\n");
     return -1;
   }
-  if (w.split_shade) ls.dep_fast = 0;   // k_classify leaves no primary shade
+  if (w.split_shade) ls.dep_fast = ls.pin = 0;   // k_classify leaves no primary shade
   // phase C inside the resolver needs a resolver long enough to hide it: at depth 1 (two
   // levels) the chains are short and the resolver's one wave per SIMD shades more slowly than
   // k_dep_chunks' full occupancy (simple 1024^2 d1 0.143 -> 0.175 ms; from depth 2 it gains:
@@ -1726,7 +1731,11 @@ int pipe_init(DevCtx& c, long long pixels) {
         HIP_TRY(hipExtStreamCreateWithCUMask(&p.pix[k], (uint32_t)words, mb.data()));
     return 0;
   };
-  if (tu.pipe_order == 0) {   // lane by lane (resolver, its phase C), then the pixel streams
+  // order 4 is the default, and its layout exists for two lanes on slot-less streams only: any
+  // other layout under it is order 0's, as it was while 0 was the default; so is an image large
+  // enough for the lanes' compaction streams (`comp`), which order 4 does not create
+  const bool order4 = tu.pipe_order == 4 && p.fifo && p.lanes == 2 && !comp;
+  if (tu.pipe_order == 0 || (tu.pipe_order == 4 && !order4)) {   // lane by lane (resolver, its phase C), then the pixel streams
     for (int r = 0; r < p.lanes; ++r) {
       HIP_TRY(hipExtStreamCreateWithCUMask(&p.res[r], (uint32_t)words, ma.data()));
       if (r < 2 && comp) {
@@ -1750,7 +1759,7 @@ int pipe_init(DevCtx& c, long long pixels) {
       HIP_TRY(hipExtStreamCreateWithCUMask(&p.spare[r], (uint32_t)words, ma.data()));
     HIP_TRY(hipExtStreamCreateWithCUMask(&p.pix[1], (uint32_t)words, mb.data()));
     HIP_TRY(hipExtStreamCreateWithCUMask(&p.pc[1], (uint32_t)words, mb.data()));
-  } else if (tu.pipe_order == 4 && p.fifo && p.lanes == 2) {
+  } else if (order4) {
     // one phase C stream for both lanes (consecutive frames' phase C never overlap: a lane's
     // resolver ends half a frame period after the other's), so with the device stream created
     // first and four hardware queues dealt in creation order each resolver lane shares its

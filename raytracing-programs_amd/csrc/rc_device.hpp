@@ -50,6 +50,9 @@ struct Scene {
   // A's primary shade: set when every level's shade of such an entry is exactly zero (black
   // phantom, finite reflectivities; host check in upload_scene).
   int dep_fast;
+  // Phase C builds a per-wave table of the carry point where a wave's carry-ins are all the
+  // same (pin_build; host: dep_fast scenes that fit the table, rc_tuning.pin bit 0).
+  int pin;
 };
 
 // refl[obj] > 0 (C/raycast.c:352) from a register bitmask when n <= 64
@@ -947,6 +950,360 @@ __device__ __forceinline__ V3 carry_path(const Scene& sc, const DepRec& r, int m
     S = i;
   }
   return C;
+}
+
+// -------------------------------------------------------------- pinned carry point --
+// Phase C of a wave whose 64 DEP entries all have the same carry-in c.  The
+// stale point re-hits its own surface at t ~ 0, so almost every level of such an entry starts
+// at c and almost every hit lands on c again, bit for bit.  Whatever depends on (c, shape),
+// (c, light) or (c, light, skipped shape) alone is then one value for the whole wave: it is
+// computed once, by the operations the per-lane code uses on the same bits, into a per-wave
+// LDS table, and the lanes read it instead of recomputing it at every level.  "Same point" is
+// always same_bits, never ==: -0 and +0, and NaN payloads, give different results downstream.
+__device__ __forceinline__ bool same_bits(V3 a, V3 b) {
+  return __float_as_uint(a.x) == __float_as_uint(b.x) &&
+         __float_as_uint(a.y) == __float_as_uint(b.y) &&
+         __float_as_uint(a.z) == __float_as_uint(b.z);
+}
+
+constexpr int kPinShapes = RC_PIN_SHAPES;   // the table's shape rows (Scene::pin is 0 for larger scenes)
+constexpr int kPinLights = RC_PIN_LIGHTS;   // its light rows; n * m <= 64: one lane per shadow pair
+
+struct PinShape {   // shape k at O = P = c
+  double b[3];      // quadric: 2.0 * A * (double)c.x, .. B .. c.y, .. C .. c.z (quad_abc's b)
+  float o;          // quadric: cq of quad_abc; sphere: c of hit_sphere; plane: num of hit_plane
+  float tv[3];      // sphere: c - centre
+  float n[3];       // hit_frame's normal at P = c, before the quadric's dot(N, D) > 0 flip
+  int nev;          // that normal's zero-normalize events (0 or 1)
+};
+struct PinLight {   // light l seen from P = c: shade's per-light set-up
+  float ld[3];
+  float dist, rad, ang;
+  int z;            // dist == 0: the counted zero-normalize event(s)
+  int spot;
+};
+struct PinTable {
+  PinShape s[kPinShapes];
+  PinLight l[kPinLights];
+};
+
+// Builds the table of carry point c.  EVERY lane of the wave must be active (lane k fills shape
+// row k, lane l light row l, lane l * n + k tests the shadow ray of light l with shape k
+// skipped); c is wave-uniform.  Returns the shadow bits: bit l * n + k = shadowed(sc, c, ld_l, k).
+__device__ __forceinline__ unsigned long long pin_build(const Scene& sc, V3 c, PinTable& tb) {
+  const int lane = (int)(threadIdx.x & 63);
+  if (lane < sc.n) {
+    const rc_shape& s = sc.lshapes[lane];
+    PinShape e;
+    e.b[0] = e.b[1] = e.b[2] = 0.0;
+    e.o = 0.0f;
+    e.tv[0] = e.tv[1] = e.tv[2] = 0.0f;
+    e.nev = 0;
+    V3 N = v3(0.0f, 0.0f, 0.0f);
+    const int type = s.type;
+    if (type == RC_SHAPE_SPHERE) {
+      const V3 tv = v3(c.x - s.p[0], c.y - s.p[1], c.z - s.p[2]);
+      e.tv[0] = tv.x;
+      e.tv[1] = tv.y;
+      e.tv[2] = tv.z;
+      e.o = (float)((double)dot(tv, tv) - s.r2);
+      const float inv = s.inv_r;
+      N = normalize(v3((c.x - s.p[0]) * inv, (c.y - s.p[1]) * inv, (c.z - s.p[2]) * inv), e.nev);
+    } else if (type == RC_SHAPE_PLANE) {
+      N = v3(s.n[0], s.n[1], s.n[2]);
+      e.o = dot(v3(c.x - s.p[0], c.y - s.p[1], c.z - s.p[2]), N);
+    } else if (type == RC_SHAPE_QUADRIC) {
+      double acc;
+      acc = s.A * ((double)c.x * (double)c.x);
+      acc = acc + s.B * ((double)c.y * (double)c.y);
+      acc = acc + s.C * ((double)c.z * (double)c.z);
+      if (!quad_x0(sc)) {
+        acc = acc + (double)(s.qd * c.x * c.y);
+        acc = acc + (double)(s.qe * c.x * c.z);
+        acc = acc + (double)(s.qf * c.y * c.z);
+      }
+      acc = acc + (double)(s.qg * c.x);
+      acc = acc + (double)(s.qh * c.y);
+      acc = acc + (double)(s.qi * c.z);
+      acc = acc + (double)s.qj;
+      e.o = (float)acc;
+      e.b[0] = 2.0 * s.A * (double)c.x;
+      e.b[1] = 2.0 * s.B * (double)c.y;
+      e.b[2] = 2.0 * s.C * (double)c.z;
+      double n0 = 2.0 * s.A * (double)c.x;
+      n0 = n0 + (double)(s.qd * c.y);
+      n0 = n0 + (double)(s.qe * c.z);
+      n0 = n0 + (double)s.qg;
+      double n1 = 2.0 * s.B * (double)c.y;
+      n1 = n1 + (double)(s.qd * c.x);
+      n1 = n1 + (double)(s.qf * c.z);
+      n1 = n1 + (double)s.qh;
+      double n2 = 2.0 * s.C * (double)c.z;
+      n2 = n2 + (double)(s.qe * c.x);
+      n2 = n2 + (double)(s.qf * c.y);
+      n2 = n2 + (double)s.qi;
+      N = normalize(v3((float)n0, (float)n1, (float)n2), e.nev);
+    }
+    e.n[0] = N.x;
+    e.n[1] = N.y;
+    e.n[2] = N.z;
+    tb.s[lane] = e;
+  }
+  if (lane < sc.m) {
+    const rc_light& L = sc.lights[lane];
+    V3 ld = v3(L.pos[0] - c.x, L.pos[1] - c.y, L.pos[2] - c.z);
+    const float dist = length(ld);
+    const bool z = dist == 0.0f;
+    if (!z) ld = div3(ld, dist);
+    const float lin = L.r0 + L.r1 * dist;
+    const float rad = (float)(1.0 / ((double)lin + (double)L.r2 * ((double)dist * (double)dist)));
+    float ang = 1.0f;
+    if (L.type == RC_LIGHT_SPOT) {
+      const V3 vr = v3(c.x - L.pos[0], c.y - L.pos[1], c.z - L.pos[2]);
+      const V3 v = v3(vr.x == 0.0f ? vr.x : -ld.x, vr.y == 0.0f ? vr.y : -ld.y,
+                      vr.z == 0.0f ? vr.z : -ld.z);
+      const float alpha = dot(v, v3(L.dir[0], L.dir[1], L.dir[2]));
+      if (alpha < L.cos_theta) {
+        ang = 0.0f;
+      } else if (L.a0_kind == RC_A0_INT) {
+        ang = (float)pown_dd((double)alpha, L.a0_int);
+      } else {
+        ang = (float)pow((double)alpha, (double)L.a0);
+      }
+    }
+    PinLight e;
+    e.ld[0] = ld.x;
+    e.ld[1] = ld.y;
+    e.ld[2] = ld.z;
+    e.dist = dist;
+    e.rad = rad;
+    e.ang = ang;
+    e.z = z ? 1 : 0;
+    e.spot = L.type == RC_LIGHT_SPOT ? 1 : 0;
+    tb.l[lane] = e;
+  }
+  // the rows are read by other lanes of this wave only: LDS operations of one wave complete
+  // in order, the fence keeps the compiler from moving the reads above the writes
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  bool sh = false;
+  if (lane < sc.n * sc.m) {
+    const int l = lane / sc.n, k = lane - l * sc.n;
+    const PinLight& e = tb.l[l];
+    sh = shadowed(sc, c, v3(e.ld[0], e.ld[1], e.ld[2]), k);
+  }
+  return __ballot(sh);
+}
+
+// nearest(sc, c, D, skip, tbest) with every origin-only term read from c's table: the same
+// operations on the same bits, in the tests' own order.
+__device__ __forceinline__ int nearest_pin(const Scene& sc, V3 c, V3 D, int skip,
+                                           const PinTable& tb, float& tbest) {
+  const RayK rk = ray_consts(D);
+  const bool x0 = quad_x0(sc), rej = x0 && x0_reject(c, D);
+  float best = __builtin_inff();
+  int idx = -1;
+  for (int k = 0; k < sc.n; ++k) {
+    const rc_shape& s = sc.shapes[k];
+    const PinShape& e = tb.s[k];
+    const int type = s.type;
+    float t = 0.0f;
+    bool hit = false;
+    if (type == RC_SHAPE_SPHERE) {   // hit_sphere
+      const V3 tv = v3(e.tv[0], e.tv[1], e.tv[2]);
+      const float b = 2.0f * dot(D, tv);
+      const float fac = rk.a4 * e.o;
+      const float disc = (float)__builtin_fma((double)b, (double)b, -(double)fac);
+      if (!(disc < 0.0f)) {
+        const double sq = sqrt_ns((double)disc);
+        const float t1 = pin(tquot((double)(-b) - sq, rk.den, rk.yden));
+        const float t2 = pin(tquot((double)(-b) + sq, rk.den, rk.yden));
+        t = t1 < 0.0f ? t2 : t1;
+        hit = true;
+      }
+    } else if (type == RC_SHAPE_PLANE) {   // hit_plane
+      const float den = dot(D, v3(s.n[0], s.n[1], s.n[2]));
+      if (!(den == 0.0f)) {
+        const float tt = (-e.o) / den;
+        if (!(tt < 0.0f)) {
+          t = tt;
+          hit = true;
+        }
+      }
+    } else if (type == RC_SHAPE_QUADRIC) {   // quad_abc, hit_quadric, test_shape's z rule
+      double acc;
+      acc = s.A * ((double)D.x * (double)D.x);
+      acc = acc + s.B * ((double)D.y * (double)D.y);
+      acc = acc + s.C * ((double)D.z * (double)D.z);
+      if (!x0) {
+        acc = acc + (double)(s.qd * D.x * D.y);
+        acc = acc + (double)(s.qe * D.x * D.z);
+        acc = acc + (double)(s.qf * D.y * D.z);
+      }
+      const float aq = (float)acc;
+      acc = e.b[0] * (double)D.x;
+      acc = acc + e.b[1] * (double)D.y;
+      acc = acc + e.b[2] * (double)D.z;
+      if (!x0) {
+        acc = acc + (double)(s.qd * (c.x * D.y + c.y * D.x));
+        acc = acc + (double)(s.qe * (c.x * D.z + c.z * D.x));
+        acc = acc + (double)(s.qf * (c.y * D.z + c.z * D.y));
+      }
+      acc = acc + (double)(s.qg * D.x);
+      acc = acc + (double)(s.qh * D.y);
+      acc = acc + (double)(s.qi * D.z);
+      const float bq = (float)acc;
+      const float cq = e.o;
+      if (!rej) {
+        if ((double)aq == 0.0) {
+          t = tquot(-1.0 * (double)cq, (double)bq, RC_NRDIV ? recip_nr((double)bq) : 0.0);
+          hit = true;
+        } else {
+          const float disc =
+              (float)__builtin_fma((double)bq, (double)bq, -(4.0 * (double)aq * (double)cq));
+          if (!((double)disc < 0.0)) {
+            const double den = 2.0 * (double)aq;
+            const double sq = sqrt_ns((double)disc);
+            const double y = RC_NRDIV ? recip_nr(den) : 0.0;
+            const float t1 = pin(tquot((double)(-bq) - sq, den, y));
+            const float t2 = pin(tquot((double)(-bq) + sq, den, y));
+            t = t1 <= 0.0f ? t2 : t1;
+            hit = true;
+          }
+        }
+      }
+      if (hit && skip != -1 && (c.z + t * D.z) < c.z) hit = false;
+    }
+    if (hit && k != skip && best > t && t > 0.0f) {
+      best = t;
+      idx = k;
+    }
+  }
+  tbest = best;
+  return idx;
+}
+
+// shade(sc, idx, c, N, D, zero_events) for a hit that landed on c (idx < n): the per-light
+// set-up and the shadow test come from c's table, the rest is shade's own code.  The events
+// are counted where shade counts them: dist == 0 before the inert test, the spot light's
+// second one after the shadow test.
+__device__ __forceinline__ V3 shade_pin(const Scene& sc, int idx, V3 N, V3 D, const PinTable& tb,
+                                        unsigned long long shadow, int& zero_events) {
+  const rc_shape& o = sc.lshapes[idx];
+  const float opacity = o.opacity;
+  V3 out = v3(0.0f, 0.0f, 0.0f);
+  if (!(opacity > 0.0f)) return out;
+  const rc_shade_pair* pr = sc.lpairs + (size_t)idx * sc.m;
+  for (int l = 0; l < sc.m; ++l) {
+    const PinLight& L = tb.l[l];
+    const V3 ld = v3(L.ld[0], L.ld[1], L.ld[2]);
+    const bool z = L.z != 0, spot = L.spot != 0;
+    if (z) zero_events++;
+    const float rad = L.rad, ang = L.ang;
+    const float th = dot(N, ld);
+    const bool inert = th <= 0.0f && __builtin_isfinite(rad) && __builtin_isfinite(ang) &&
+                       !(z && spot);
+    if (inert) continue;
+    if ((shadow >> (l * sc.n + idx)) & 1ull) continue;
+    if (spot) zero_events += z ? 1 : 0;
+    float dr = 0.0f, dg = 0.0f, db = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f;
+    if (!(th <= 0.0f)) {
+      const rc_shade_pair& p = pr[l];
+      dr = p.dl[0] * th;
+      dg = p.dl[1] * th;
+      db = p.dl[2] * th;
+      const V3 view = v3(D.x * -1.0f, D.y * -1.0f, D.z * -1.0f);
+      const double angle = (double)dot(view, reflect(ld, N));
+      if (!(angle > 0.0)) {
+        const double p20 = pow20(angle);
+        sr = (float)((double)p.sl[0] * p20);
+        sg = (float)((double)p.sl[1] * p20);
+        sb = (float)((double)p.sl[2] * p20);
+      }
+    }
+    out.x = out.x + ((dr + sr) * rad) * ang;
+    out.y = out.y + ((dg + sg) * rad) * ang;
+    out.z = out.z + ((db + sb) * rad) * ang;
+  }
+  return v3(out.x * opacity, out.y * opacity, out.z * opacity);
+}
+
+// shade_dep_cont for the active lanes of a wave whose carry-ins all have c's bits (c is
+// wave-uniform, `tb` / `shadow` are pin_build's for it).  A level at which every active lane
+// still starts at c searches with the table (a wave-uniform branch around the whole search);
+// a hit that lands on c takes the table's normal, light terms and shadow bits; any other
+// level or hit runs shade_dep_cont's own code.  Lanes may be inactive (a partial wave, lanes
+// that left the loop): the ballot sees active lanes only and nothing here reads another lane.
+__device__ __forceinline__ V3 shade_dep_cont_pin(const Scene& sc, const DepLine* __restrict__ rp,
+                                                 int maxrec, V3 c, const PinTable& tb,
+                                                 unsigned long long shadow, int& zero_events) {
+  const DepRec& r = rp->r;
+  int obj = r.obj0, S = -1;
+  const float T0 = sc.lshapes[obj].refl;
+  float T = T0 * sc.lshapes[obj].refl;
+  V3 O = c, C = c, D = v3(r.ax, r.ay, r.az), N = v3(r.n0x, r.n0y, r.n0z);
+  V3 out = v3(0.0f, 0.0f, 0.0f);
+  for (int lvl = 2; lvl < maxrec; ++lvl) {
+    if (!reflective(sc, obj)) break;
+    if (lvl > 2) D = normalize(reflect(D, N), zero_events);
+    float t;
+    int i;
+    if (__ballot(!same_bits(O, c)) == 0ull) i = nearest_pin(sc, c, D, S, tb, t);
+    else i = nearest(sc, O, D, S, t);
+    V3 col;
+    if (i >= 0) {
+      const V3 P = v3(O.x + D.x * t, O.y + D.y * t, O.z + D.z * t);
+      if (same_bits(P, c)) {   // hit_frame and shade at P = c
+        const PinShape& e = tb.s[i];
+        N = v3(e.n[0], e.n[1], e.n[2]);
+        zero_events += e.nev;
+        const int type = sc.lshapes[i].type;
+        if (type != RC_SHAPE_SPHERE && type != RC_SHAPE_PLANE && dot(N, D) > 0.0f)
+          N = v3(N.x * -1.0f, N.y * -1.0f, N.z * -1.0f);
+        C = P;
+        col = shade_pin(sc, i, N, D, tb, shadow, zero_events);
+      } else {
+        hit_frame(sc, i, O, D, t, C, N, zero_events);
+        col = shade(sc, i, C, N, D, zero_events);
+      }
+      obj = i;
+    } else {
+      col = shade(sc, sc.n, C, N, D, zero_events);
+    }
+    out.x = out.x + col.x * T;
+    out.y = out.y + col.y * T;
+    out.z = out.z + col.z * T;
+    T = T * sc.lshapes[obj].refl;
+    O = C;
+    S = i;
+  }
+  const V3 k = dep_pcol(rp);
+  return v3(out.x + k.x, out.y + k.y, out.z + k.z);
+}
+
+// One wave's trip of phase C under dep_fast with Scene::pin: EVERY lane of the wave calls this;
+// `act` lanes hold an entry (line rp, carry-in c), the first lane is one of them.  When every
+// active lane's carry-in has the first lane's bits the wave builds that point's table in `tb`
+// (its own LDS slice) and shades from it; otherwise each lane runs shade_dep_cont.  Returns the
+// lane's colour (zero for a lane without an entry); `took`: the wave went the table's way.
+__device__ __forceinline__ V3 shade_dep_wave(const Scene& sc, const DepLine* __restrict__ rp,
+                                             int maxrec, V3 c, bool act, PinTable& tb,
+                                             int& zero_events, bool& took) {
+  const V3 c0 = v3(__uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(c.x))),
+                   __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(c.y))),
+                   __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(c.z))));
+  V3 rgb = v3(0.0f, 0.0f, 0.0f);
+  took = __ballot(act && !same_bits(c, c0)) == 0ull;
+  if (took) {
+    const unsigned long long shadow = pin_build(sc, c0, tb);
+    if (act) rgb = shade_dep_cont_pin(sc, rp, maxrec, c0, tb, shadow, zero_events);
+    // the next trip's table must not overtake this trip's reads (one wave: LDS in order)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  } else if (act) {
+    rgb = shade_dep_cont(sc, rp, maxrec, c, zero_events);
+  }
+  return rgb;
 }
 
 }  // namespace rc

@@ -22,6 +22,7 @@ struct LaunchScene {
   int has_quadric;                // the scene has a quadric (2: none with cross terms, quad_x0)
   int o0_ok;                      // primary rays may use rc_shape::o0
   int dep_fast;                   // clean DEP entries take phase A's primary shade (Scene)
+  int pin;                        // phase C's carry-point table (Scene::pin)
 };
 
 // Parity-mode workspace (device pointers), sized for W*H pixels.

@@ -623,12 +623,6 @@ constexpr int kResolveBlock = 256;
 constexpr int kTeamMax = 256;
 constexpr int kLdsShapes = kLdsShapesMax;
 
-__device__ __forceinline__ bool same_bits(V3 a, V3 b) {
-  return __float_as_uint(a.x) == __float_as_uint(b.x) &&
-         __float_as_uint(a.y) == __float_as_uint(b.y) &&
-         __float_as_uint(a.z) == __float_as_uint(b.z);
-}
-
 __device__ __forceinline__ V3 seg_init_carry(const long long* __restrict__ seg_key,
                                              const float4* __restrict__ wcarry, int s) {
   const long long key = seg_key[s];
@@ -2534,7 +2528,9 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
 // full waves (levels 2.. with shading, shade_dep_cont; the whole pixel again when the scene
 // is not dep_fast).  Entries are independent once their carry-ins are known, so the list order
 // is free; the point is full waves of heavy work (~35 % of the entries are clean at quadric
-// 4096^2) without a second kernel or global atomics.
+// 4096^2) without a second kernel or global atomics.  Under Scene::pin a wave of pass 2 whose
+// carry-ins all have the same bits (88 % of them at quadric 4096^2) shades from a per-wave
+// table of that point (shade_dep_wave, rc_device.hpp).
 #ifndef RC_CHUNK
 #define RC_CHUNK 1024
 #endif
@@ -2555,6 +2551,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
   __shared__ int s_j[kChunk];
   __shared__ float s_c[kChunk][3];
   __shared__ int s_n;
+  __shared__ PinTable s_pin[kFast ? kBlock / 64 : 1];   // one carry-point table per wave
   stage_scene<kStage>(sc, stage);
   // limit: a row shard's fixed-size exchange delivered carry-ins for its first `limit` entries
   // only (the frame is rendered again when the count exceeds it, rc_shard.hip)
@@ -2592,6 +2589,31 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
     }
     __syncthreads();
     const int n = s_n;
+    if constexpr (kFast) {
+      if (sc.pin) {
+        // Whole waves walk the list (the trip count is wave-uniform, so every lane is there
+        // when the table is built); a wave whose active lanes all carry the first lane's bits
+        // shades from that carry point's table, any other wave as below.  No barrier in here.
+        for (int q0 = __builtin_amdgcn_readfirstlane(wave) * 64; q0 < n; q0 += kBlock) {
+          const int q = q0 + lane;
+          const bool act = q < n;
+          int j = 0;
+          long long p = 0;
+          V3 c = v3(0.0f, 0.0f, 0.0f);
+          if (act) {
+            j = s_j[q];
+            c = v3(s_c[q][0], s_c[q][1], s_c[q][2]);
+            p = dep_pix[j];
+          }
+          bool took;
+          const V3 rgb = shade_dep_wave(sc, deprec + p, maxrec, c, act,
+                                        s_pin[__builtin_amdgcn_readfirstlane(wave)], zero, took);
+          if (act) store_dep(out, patch, tag, p, j, rgb);
+        }
+        __syncthreads();   // the list is rebuilt for the next chunk
+        continue;
+      }
+    }
     for (int q = threadIdx.x; q < n; q += kBlock) {
       const int j = s_j[q];
       const V3 c = v3(s_c[q][0], s_c[q][1], s_c[q][2]);

@@ -202,6 +202,7 @@ static Scene make_scene(const LaunchScene& s) {
   sc.has_quadric = s.has_quadric;
   sc.o0_ok = s.o0_ok;
   sc.dep_fast = s.dep_fast;
+  sc.pin = s.pin;
   return sc;
 }
 static bool stage_fits(const LaunchScene& s) {

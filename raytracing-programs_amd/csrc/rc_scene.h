@@ -33,6 +33,13 @@
 #define RC_A0_INT 0      /* a0 is an integer with |a0| <= 64: exact-product power */
 #define RC_A0_GENERAL 1  /* any other value: double-double exp/log power          */
 
+/* rows of phase C's per-wave carry-point table (rc_device.hpp pin_build): scenes with more
+ * shapes or lights, or more than 64 (light, shape) pairs, keep the per-lane code */
+#define RC_PIN_SHAPES 8
+#define RC_PIN_LIGHTS 16
+#define RC_PIN_FITS(n, m) \
+  ((n) >= 1 && (n) <= RC_PIN_SHAPES && (m) <= RC_PIN_LIGHTS && (n) * (m) <= 64)
+
 /* 128 B per shape: geometry fields are read in the intersection loop. */
 typedef struct rc_shape {
   int32_t type;        /* RC_SHAPE_*                                   */
