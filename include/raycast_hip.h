@@ -698,7 +698,89 @@ int rc_accum_scroll_device(const rc_scene *scene, const rc_window *win, int widt
                            rc_accum_px *d_acc_dst, uint8_t *d_out_dst,
                            void *stream, rc_timing *timing);
 
-/* Frames in flight (an extension for rendering frame sequences; no reference
+/* The primary-visibility G-buffer: object id, depth, hit point and normal per pixel
+ * (rc_render_gbuffer, rc_render_gbuffer_device, rc_pick, rc_pick_device, rc_id_edge_rates_device;
+ * fast, parity and cuda mode).  Every other entry returns colours.  These return what the pixel
+ * kernels know about a pixel before they shade it: which shape the primary ray hits, how far away,
+ * where and with which normal.  That is picking (what is under the cursor), depth and id planes for
+ * compositing and debugging, and a geometric edge criterion for anti-aliasing: the boundary between
+ * two equally coloured shapes has no colour contrast, but it has two ids.
+ * Values.  For virtual pixel (X, Y) = (x0 + x, y0 + y) of the full_w x full_h image let d be the
+ *     reference's primary ray, pixel size cam / (float)full_w and cam / (float)full_h as for a
+ *     window at s = 1 (above).  In fast and parity mode (the C port's arithmetic, C/raycast.c)
+ *     (id, t, P, N) is what its scan accepts from the origin with no shape skipped, the hit point
+ *     O + D*t and the normal of C/raycast.c:461-523: the oracle's rco_prim_nearest(O = 0, D = d,
+ *     skip = -1, shadow = 0).  In cuda mode id and t are the CUDA port's (rco_prim_nearest_cuda;
+ *     its direction is normalised with a float sum, so t differs in bits on most pixels while the
+ *     ids agree).  Every stored float is bit-identical to the oracle's.  id indexes the scene's
+ *     shape list in file order.  On a miss id = -1 and everything else is +0.0f.
+ * Parity mode is accepted: the primary hit does not involve the scan-order carry, so its planes
+ *     are fast mode's, byte for byte.  These are the first window-taking entries that parity mode
+ *     does not refuse.
+ * P and N in cuda mode (rc_gbuffer.P or .N non-null, frame = 1 in rc_pick*) are refused: the oracle
+ *     exports no CUDA-port hit frame, so they could not be pinned.
+ * max_recursion is ignored: nothing bounces.
+ * rc_render_gbuffer*: win = NULL is the whole W x H image (full = (W, H), origin (0, 0)).  Any
+ *     plane pointer may be null (the plane is not wanted and costs nothing), at least one is not.
+ *     rc_render_gbuffer takes host planes, is synchronous and runs on opt->device;
+ *     rc_render_gbuffer_device takes device planes (the struct itself is host memory), runs on the
+ *     current device and the caller's stream (NULL: the library's) and is asynchronous unless
+ *     timing is requested.  One kernel, one lane per pixel, k_window's grid at s = 1.
+ * rc_pick*: point k is the virtual pixel (xy[2k], xy[2k + 1]) of the full_w x full_h image (any
+ *     size up to 2^31 - 1: no grid is laid over it) and hits[k] is its record; duplicates are fine;
+ *     n in 1 .. 2^24.  frame = 0 stores +0.0f in P and N.  rc_pick (host arrays) validates the
+ *     points before any device work and refuses one outside the image, leaving hits untouched.
+ *     rc_pick_device cannot see the points: it shoots no ray for an outside point and stores
+ *     id = -2 with everything else +0.0f.  d_hits is 16-byte aligned (a record leaves as two
+ *     16-byte stores).
+ * rc_id_edge_rates_device: rates[y][x] = s if any pixel of the 3 x 3 neighbourhood of (x, y),
+ *     clipped to the image, has an id different from id[y][x], else base; s in {2, 4, 8}, base in
+ *     {0, 1}.  One memory-bound kernel on the caller's stream, outside the workspace, like
+ *     rc_filter_image_device.  The output is exactly the map rc_render_rates_device takes, so
+ *     "anti-alias the object boundaries" is three enqueues on one stream with no host wait:
+ *     rc_render_gbuffer_device (id), rc_id_edge_rates_device, rc_render_rates_device; the image is
+ *     the rate-map contract's under that map.
+ * rc_timing: kernel_ms is the one kernel's span; zero_normalize counts the zero-length
+ *     normalisations of the directions and, with P or N (frame = 1), of the normals, as the oracle
+ *     counts them (cuda mode counts none, as everywhere); everything parity-specific is 0.
+ * rc_gbuffer_phase_ms: ms[0] = the kernel span of the last G-buffer or pick frame enqueued on the
+ *     current device (it waits for it); -1 when there is none or another frame has reused its
+ *     events.  A G-buffer frame touches no other feature's record: their stats survive it.
+ * Refused, each with one message and -1, from the arguments alone (before any device work), in
+ * this order: a null scene, options, planes struct or (pick) array; all four planes null; hits not
+ * 16-byte aligned (rc_pick_device); a factor outside 0, 1, 2, 4, 8; a threshold in opt->ssaa or a
+ * factor above 1 (a G-buffer of the s x s image is a window of the s*full_w x s*full_h image);
+ * num_gpus > 1; P, N or frame in cuda mode; whatever rc_window_check(win, W, H, 1) refuses (for
+ * pick: a side of the image below 1); for pick, n outside 1 .. 2^24, then (rc_pick) the first point
+ * outside the image.  rc_id_edge_rates_device: a null pointer; s not 2, 4 or 8; base not 0 or 1; W
+ * or H below 1; W * H >= 2^32.
+ * Out of scope: a RAYCAST_* variable or a CLI format for the planes; G-buffers in
+ * rc_render_sharded; any criterion beyond the id edge (depth or normal discontinuities are the
+ * caller's own map, from the planes it now has). */
+typedef struct rc_gbuffer {   /* any pointer may be NULL (plane not wanted); at least one is not */
+  int32_t *id;                /* W*H   : index into the scene's shape list, -1 = no primary hit    */
+  float   *t;                 /* W*H   : the accepted hit's distance, +0.0f on a miss              */
+  float   *P;                 /* W*H*3 : hit point,  +0.0f x 3 on a miss                           */
+  float   *N;                 /* W*H*3 : hit normal, +0.0f x 3 on a miss                           */
+} rc_gbuffer;                 /* row-major, top row first                                          */
+typedef struct rc_hit { int32_t id; float t; float P[3]; float N[3]; } rc_hit;
+_Static_assert(sizeof(rc_gbuffer) == 32, "rc_gbuffer layout (ctypes binding)");
+_Static_assert(sizeof(rc_hit) == 32, "rc_hit layout (ctypes binding, the kernel's two stores)");
+int rc_render_gbuffer(const rc_scene *scene, const rc_window *win /* NULL: the whole image */,
+                      int width, int height, const rc_options *opt,
+                      const rc_gbuffer *planes /* host */, rc_timing *timing);
+int rc_render_gbuffer_device(const rc_scene *scene, const rc_window *win, int width, int height,
+                             const rc_options *opt, const rc_gbuffer *d_planes, void *stream,
+                             rc_timing *timing);
+int rc_pick(const rc_scene *scene, int full_w, int full_h, const rc_options *opt, int frame,
+            int64_t n, const int32_t *xy /* n pairs */, rc_hit *hits);
+int rc_pick_device(const rc_scene *scene, int full_w, int full_h, const rc_options *opt, int frame,
+                   int64_t n, const int32_t *d_xy, rc_hit *d_hits, void *stream);
+int rc_id_edge_rates_device(const int32_t *d_id, int width, int height, int s, int base,
+                            uint8_t *d_rates, void *stream);
+int rc_gbuffer_phase_ms(double ms[1]);
+
+/* Frames in flight(an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out
  * (W*H*3 bytes, device memory, ready for use: synchronise the stream that produced it
  * first) and returns.  It is byte-identical to rc_render_device's.  In parity mode up to

@@ -150,6 +150,28 @@ class RcWindow(ctypes.Structure):
                 ("x0", ctypes.c_int32), ("y0", ctypes.c_int32)]
 
 
+class RcGbuffer(ctypes.Structure):
+    """rc_gbuffer (32 bytes): the four plane pointers, null for a plane that is not wanted."""
+    _fields_ = [("id", ctypes.c_void_p), ("t", ctypes.c_void_p), ("P", ctypes.c_void_p),
+                ("N", ctypes.c_void_p)]
+
+
+class RcHit(ctypes.Structure):
+    """rc_hit (32 bytes): one picked point's record."""
+    _fields_ = [("id", ctypes.c_int32), ("t", ctypes.c_float), ("P", ctypes.c_float * 3),
+                ("N", ctypes.c_float * 3)]
+
+
+# the planes of a G-buffer in rc_gbuffer's order: name -> (dtype, components)
+GBUFFER_PLANES = {"id": (np.int32, 1), "t": (np.float32, 1), "P": (np.float32, 3),
+                  "N": (np.float32, 3)}
+# rc_hit as a numpy record; id -1: no primary hit, -2 (pick_device only): a point outside the image
+HIT_DTYPE = np.dtype([("id", np.int32), ("t", np.float32), ("P", np.float32, 3),
+                      ("N", np.float32, 3)])
+assert HIT_DTYPE.itemsize == ctypes.sizeof(RcHit) == ctypes.sizeof(RcGbuffer) == 32
+PICK_MAX_POINTS = 1 << 24
+
+
 def _hier_points(g):
     """hier<g> (include/raycast_hip.h, rc_sample_seq): point k is the bit-reversal r of k over
     2 * log2 g bits; x takes r's even bits and y its odd bits."""
@@ -248,7 +270,9 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_sample_seq_builtin", "rc_sample_seq_check", "rc_accum_pass_device",
                "rc_accum_resolve_device", "rc_render_accum", "rc_accum_stats_get",
                "rc_accum_phase_ms", "rc_window_check", "rc_window_env", "rc_render_window",
-               "rc_render_window_device", "rc_accum_pass_window_device"]
+               "rc_render_window_device", "rc_accum_pass_window_device",
+               "rc_render_gbuffer", "rc_render_gbuffer_device", "rc_pick", "rc_pick_device",
+               "rc_id_edge_rates_device", "rc_gbuffer_phase_ms"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -440,6 +464,22 @@ def _hip_lib_locked():
                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.POINTER(RcTiming)]
+    lib.rc_render_gbuffer.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcWindow), ctypes.c_int,
+                                      ctypes.c_int, ctypes.POINTER(RcOptions),
+                                      ctypes.POINTER(RcGbuffer), ctypes.POINTER(RcTiming)]
+    lib.rc_render_gbuffer_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcWindow),
+                                             ctypes.c_int, ctypes.c_int, ctypes.POINTER(RcOptions),
+                                             ctypes.POINTER(RcGbuffer), ctypes.c_void_p,
+                                             ctypes.POINTER(RcTiming)]
+    lib.rc_pick.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RcOptions),
+                            ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+    lib.rc_pick_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                   ctypes.POINTER(RcOptions), ctypes.c_int, ctypes.c_int64,
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.rc_id_edge_rates_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_void_p]
+    lib.rc_gbuffer_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
     _hip = lib
     return lib
 
@@ -1402,6 +1442,113 @@ def accum_scroll_device(scene, window, width, height, seq, count, dx, dy, d_acc_
               ctypes.c_void_p(d_acc_src_ptr), ctypes.c_void_p(d_out_src_ptr),
               ctypes.c_void_p(d_acc_dst_ptr), ctypes.c_void_p(d_out_dst_ptr),
               _stream(stream_ptr), t)
+
+
+def _plane_names(planes):
+    """The requested planes as a tuple of GBUFFER_PLANES' names, in that order, at least one."""
+    names = (planes,) if isinstance(planes, str) else tuple(planes)
+    for p in names:
+        if p not in GBUFFER_PLANES:
+            raise ValueError(f"gbuffer: plane {p!r} is not one of {tuple(GBUFFER_PLANES)}")
+    if not names:
+        raise ValueError("gbuffer: no plane asked for")
+    return tuple(p for p in GBUFFER_PLANES if p in names)
+
+
+def id_edge_rates(ids, s, base=1):
+    """The geometric edge criterion (include/raycast_hip.h, rc_id_edge_rates_device) in numpy: the
+    [H, W] uint8 rate map that is s where a pixel of the 3 x 3 neighbourhood, clipped to the image,
+    has another id than the pixel itself, and base elsewhere; s in 2, 4, 8 and base in 0, 1."""
+    ids = np.asarray(ids)
+    if ids.dtype != np.int32 or ids.ndim != 2 or ids.size == 0:
+        raise ValueError(f"id_edge_rates: a non-empty int32 [H, W] plane, got {ids.dtype} {ids.shape}")
+    if int(s) not in (2, 4, 8) or int(base) not in (0, 1):
+        raise ValueError(f"id_edge_rates: s {s} is not 2, 4 or 8 or base {base} is not 0 or 1")
+    h, w = ids.shape
+    pad = np.pad(ids, 1, mode="edge")      # a clipped neighbour is one of the pixel's own 3 x 3
+    edge = np.zeros((h, w), bool)
+    for dy in range(3):
+        for dx in range(3):
+            edge |= pad[dy:dy + h, dx:dx + w] != ids
+    return np.where(edge, np.uint8(s), np.uint8(base)).astype(np.uint8)
+
+
+def render_gbuffer(scene, width, height, planes=("id", "t"), window=None, mode="fast", device=0,
+                   timing=None):
+    """rc_render_gbuffer: the primary hit of every pixel of the width x height window at window =
+    (full_w, full_h, x0, y0) (None: the whole image) as a dict of numpy arrays, one per requested
+    plane: "id" [H, W] int32 (the shape's index in the scene, -1: no hit), "t" [H, W] float32,
+    "P" and "N" [H, W, 3] float32 (zeros on a miss; fast and parity mode only)."""
+    names = _plane_names(planes)
+    out = {p: np.empty((height, width) + ((3,) if GBUFFER_PLANES[p][1] == 3 else ()),
+                       dtype=GBUFFER_PLANES[p][0]) for p in names}
+    g = RcGbuffer(**{p: a.ctypes.data for p, a in out.items()})
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    opt = options(0, mode, 1, device)
+    with _timed(timing) as (t, _):
+        _call("rc_render_gbuffer", scene.packed(), win, width, height, ctypes.byref(opt),
+              ctypes.byref(g), ctypes.byref(t))
+    return out
+
+
+def render_gbuffer_device(scene, width, height, window=None, d_id_ptr=None, d_t_ptr=None,
+                          d_p_ptr=None, d_n_ptr=None, stream_ptr=None, mode="fast", timing=None):
+    """rc_render_gbuffer_device: the planes are device memory (W*H int32, W*H float32, W*H*3
+    float32 twice), None for a plane that is not wanted; enqueued on the stream and asynchronous
+    unless `timing` is given."""
+    g = RcGbuffer(d_id_ptr or None, d_t_ptr or None, d_p_ptr or None, d_n_ptr or None)
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    opt = options(0, mode)
+    with _timed(timing) as (_, t):
+        _call("rc_render_gbuffer_device", scene.packed(), win, width, height, ctypes.byref(opt),
+              ctypes.byref(g), _stream(stream_ptr), t)
+
+
+def _pick_points(xy):
+    xy = np.asarray(xy)
+    if xy.ndim != 2 or xy.shape[1] != 2 or xy.dtype.kind not in "iu":
+        raise ValueError(f"pick: xy is an integer [n, 2] array of (x, y) pairs, got {xy.dtype} "
+                         f"{xy.shape}")
+    if not 1 <= len(xy) <= PICK_MAX_POINTS:
+        raise ValueError(f"pick: {len(xy)} points, not 1 .. {PICK_MAX_POINTS}")
+    if xy.size and (xy.min() < -2 ** 31 or xy.max() > 2 ** 31 - 1):
+        raise ValueError("pick: a coordinate outside int32")
+    return np.ascontiguousarray(xy, dtype=np.int32)
+
+
+def pick(scene, full_w, full_h, xy, frame=False, mode="fast", device=0):
+    """rc_pick: what is under the pixels xy ([n, 2] integers, (x, y) pairs) of the full_w x full_h
+    image, as a structured array of HIT_DTYPE ("id", "t", "P", "N"; frame: P and N too, zeros
+    without).  A point outside the image is refused."""
+    pts = _pick_points(xy)
+    hits = np.zeros(len(pts), dtype=HIT_DTYPE)
+    opt = options(0, mode, 1, device)
+    _call("rc_pick", scene.packed(), int(full_w), int(full_h), ctypes.byref(opt), int(bool(frame)),
+          len(pts), _host_ptr(pts), _host_ptr(hits))
+    return hits
+
+
+def pick_device(scene, full_w, full_h, n, d_xy_ptr, d_hits_ptr, frame=False, stream_ptr=None,
+                mode="fast"):
+    """rc_pick_device: n (x, y) int32 pairs and n 32-byte records (HIT_DTYPE, 16-byte aligned) in
+    device memory, enqueued on the stream; a point outside the image gets id = -2 and zeros."""
+    opt = options(0, mode)
+    _call("rc_pick_device", scene.packed(), int(full_w), int(full_h), ctypes.byref(opt),
+          int(bool(frame)), int(n), ctypes.c_void_p(d_xy_ptr), ctypes.c_void_p(d_hits_ptr),
+          _stream(stream_ptr))
+
+
+def id_edge_rates_device(d_id_ptr, width, height, s, d_rates_ptr, base=1, stream_ptr=None):
+    """rc_id_edge_rates_device (id_edge_rates): the map of a device id plane (W*H int32) into
+    W*H bytes of device memory, the map render_rates_device takes; one kernel on the stream."""
+    _call("rc_id_edge_rates_device", ctypes.c_void_p(d_id_ptr), int(width), int(height), int(s),
+          int(base), ctypes.c_void_p(d_rates_ptr), _stream(stream_ptr))
+
+
+def gbuffer_phase_ms():
+    """The kernel span of the last G-buffer or pick frame (rc_gbuffer_phase_ms), in ms."""
+    return _phase_ms("rc_gbuffer_phase_ms", ("kernel",),
+                     "rc_gbuffer_phase_ms: no G-buffer frame on this device")
 
 
 def window_from_env(width, height, mode="fast", ssaa=1, adaptive=0, gpus=1):

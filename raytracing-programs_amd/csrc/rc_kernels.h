@@ -267,6 +267,30 @@ hipError_t launch_accum_exposed(const LaunchScene& s, const Window& w, int W, in
 // want > 0: that many; else from the CU count, at most the wave steps `exposed` pixels can need
 int accum_exposed_blocks(unsigned exposed, int cus, int want);
 
+// The primary-visibility G-buffer (rc_render_gbuffer*, rc_pick*, rc_id_edge_rates_device; fast,
+// parity and cuda modes): the primary hit of every pixel of a window, or of n points of the
+// full_w x full_h image, and the rate map of an id plane's edges.
+//   launch_gbuffer         one lane per pixel over launch_window's grid at s = 1; a null plane is
+//                          not stored (at least one is not null); P and N (three floats a pixel)
+//                          not in cuda mode;
+//   launch_gbuffer_points  one lane per point, n in 1 .. 2^24; xy: n (x, y) pairs; hits: n 32-byte
+//                          rc_hit records, 16-byte aligned; frame: P and N too (not in cuda mode);
+//                          a point outside the image gets id = -2 and zeros;
+//   launch_id_edge_rates   rates = s where the clipped 3 x 3 neighbourhood of `id` holds another
+//                          value, else base; no scene, no workspace.
+// The launchers return hipErrorInvalidValue for what window_supported(w, W, H, 1) or
+// id_edge_rates_supported refuses and for the rules above.
+hipError_t launch_gbuffer(const LaunchScene& s, const Window& w, int W, int H, int32_t* id,
+                          float* t, float* P, float* N, unsigned long long* zcount,
+                          hipStream_t stream, bool cuda_sem);
+hipError_t launch_gbuffer_points(const LaunchScene& s, int full_w, int full_h, bool frame,
+                                 long long n, const int32_t* xy, void* hits,
+                                 unsigned long long* zcount, hipStream_t stream, bool cuda_sem);
+// s in {2, 4, 8}, base in {0, 1}, both sides at least 1, W * H below 2^32
+int id_edge_rates_supported(int W, int H, int s, int base);
+hipError_t launch_id_edge_rates(const int32_t* id, int W, int H, int s, int base, uint8_t* rates,
+                                hipStream_t stream);
+
 // ------------------- defined in rc_kernels.hip: the renderer, the parity pipeline, row shards --
 // cuda_sem: RC_MODE_CUDA (the CUDA port's arithmetic, rc_cudasem.hpp) instead of fast mode
 hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_step, int nrows,

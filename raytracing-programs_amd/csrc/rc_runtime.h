@@ -165,7 +165,8 @@ struct Pipe {
 
 // The sampling features whose frames leave phase spans behind (DevCtx::span_ev).
 enum SpanOwner {
-  kSpanAdaptive, kSpanRates, kSpanFilter, kSpanPattern, kSpanAccum, kSpanWindow, kSpanOwners
+  kSpanAdaptive, kSpanRates, kSpanFilter, kSpanPattern, kSpanAccum, kSpanWindow, kSpanGbuffer,
+  kSpanOwners
 };
 
 // The sampling features' frame records.  Each documents the events its rc_*_phase_ms reads out
@@ -231,6 +232,14 @@ struct AccumFrame {
   bool ev_listed = false;
 };
 
+// The primary-visibility G-buffer (rc_render_gbuffer*, rc_pick*): the host entries' device copies
+// of the planes they were asked for, of the points and of the records; the *_device entries use
+// the caller's memory and nothing of this.  Spans: [0] start, [1] end of the one kernel.
+struct GbufFrame {
+  DevBuf id, t, P, N;   // rc_render_gbuffer's planes
+  DevBuf xy, hits;      // rc_pick's points and records
+};
+
 struct DevCtx {
   bool init = false;
   int device = 0;
@@ -261,10 +270,11 @@ struct DevCtx {
   // caller's); a masked pass's edge list lives in aa_list; `acc` is the last call's record
   DevBuf accum_px;
   AccumFrame acc;
+  GbufFrame gbuf;      // the G-buffer's host entries
   // The event set whose spans each sampling feature's rc_*_phase_ms may still read, null once
   // another frame has recorded that set anew (claim_event_set).  Which events of the set a
   // feature reads is documented at its record above; window (rc_render_window*): [0] start,
-  // [1] end.
+  // [1] end; the G-buffer and pick frames likewise.
   hipEvent_t* span_ev[kSpanOwners] = {};
   uint8_t* stage[2] = {nullptr, nullptr};   // pinned bounce buffers of copy_to_host
   hipEvent_t stage_ev[2] = {nullptr, nullptr};

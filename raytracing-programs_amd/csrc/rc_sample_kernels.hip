@@ -27,6 +27,10 @@
 //   k_accum_move / k_accum_exposed
 //                 scrolling an accumulated view: the kept rectangle's records and bytes moved,
 //                 then samples for the exposed pixels only.
+//   k_gbuffer / k_gbuffer_points / k_id_edge_rates
+//                 the primary-visibility G-buffer (fast, parity and cuda modes): the primary hit's
+//                 shape, distance, point and normal per pixel of a window or per picked point,
+//                 nothing shaded; and the rate map of the id plane's 3 x 3 edges.
 #include "rc_cudasem.hpp"
 #include "rc_pixel.hpp"
 
@@ -1317,6 +1321,194 @@ hipError_t launch_accum_exposed(const LaunchScene& s, const Window& w, int W, in
                        dim3(kBlock), 0, stream, sc, cam, W, r, w.x0, w.y0, lg, count, pat,
                        reset ? 1 : 0, maxrec, (uint2*)acc, out, zcount);
   });
+  return hipGetLastError();
+}
+
+// --------------------- the primary-visibility G-buffer (fast, parity, cuda) --
+// rc_render_gbuffer*, rc_pick* (include/raycast_hip.h, rc_gbuffer): what the pixel kernels know
+// about a pixel's primary hit before they shade it.  No new arithmetic: the direction is
+// primary_dir's (cuda: render_pixel's first lines), the scan nearest_primary's (cu_nearest's), the
+// frame hit_frame's, the routines tests/test_gpu_prims.py and tests/test_gpu_shading.py pin ray by
+// ray.  shade, shoot and the bounce loop are not instantiated: without kFrame a pixel costs the
+// scan alone.  The primary hit does not involve the scan-order carry, so parity mode's planes are
+// fast mode's.  A miss leaves id = -1 and +0 everywhere else.  The events of the C port's
+// normalisations go to `zero` (the direction's, with kFrame the normal's); the CUDA port counts
+// none, as in every cuda kernel.
+template <bool kCuda, bool kFrame>
+__device__ __forceinline__ void gbuf_pixel(const Scene& sc, const Cam& cam, int X, int Y, int& id,
+                                           float& t, V3& P, V3& N, int& zero) {
+  static_assert(!(kCuda && kFrame), "no reference pins the CUDA port's hit frame");
+  V3 d;
+  if constexpr (kCuda) {
+    d.x = (float)(cam.hx + (double)cam.pw * ((double)X + 0.5));
+    d.y = (float)(cam.hy - (double)cam.ph * ((double)Y + 0.5));
+    d.z = -1.0f;
+    d = cusem::cu_normalize(d);
+    id = cusem::cu_nearest(sc, v3(0.0f, 0.0f, 0.0f), d, -1, t);
+  } else {
+    d = primary_dir(cam, X, Y, zero);
+    id = nearest_primary(sc, d, t);
+  }
+  P = N = v3(0.0f, 0.0f, 0.0f);
+  if (id < 0) {
+    t = 0.0f;
+    return;
+  }
+  if constexpr (kFrame) hit_frame(sc, id, v3(0.0f, 0.0f, 0.0f), d, t, P, N, zero);
+}
+
+// The planes' device pointers, null: the plane is not wanted (a kernel argument, so the tests
+// below are wave-uniform and a null plane costs nothing).
+struct GbufPlanes {
+  int32_t* id;
+  float* t;
+  float* P;
+  float* N;
+};
+
+// k_gbuffer: k_window's grid at s = 1 (a workgroup owns 16 x 16 pixels, a wave an 8 x 8 block),
+// one lane per pixel of the W x H window whose origin in the virtual image is (ox, oy).  The
+// stores are the straightforward ones: a dword per lane for id and t (eight 32-byte runs a wave),
+// three dwords at a 12-byte stride for P and N (eight 96-byte runs).  kStage (the divergent record
+// reads of hit_frame from LDS) goes with kFrame only: the scan reads the records uniformly.
+template <bool kCuda, bool kFrame, bool kStage>
+__global__ void __launch_bounds__(kBlock) k_gbuffer(Scene sc, Cam cam, int W, int H, int ox,
+                                                    int oy, GbufPlanes g,
+                                                    unsigned long long* __restrict__ zcount) {
+  static_assert(kFrame || !kStage, "the staged scene serves hit_frame");
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  stage_scene<kStage>(sc, stage);
+  int lx, ly;
+  tile_pixel(lx, ly);
+  int bx, by;
+  xcd_tile<0>(bx, by);
+  // unsigned: k_window's reasoning for the last tile's columns
+  const unsigned x = (unsigned)bx * kTileW + (unsigned)lx, y = (unsigned)by * kTileH + (unsigned)ly;
+  if (x >= (unsigned)W || y >= (unsigned)H) return;
+  int id, zero = 0;
+  float t;
+  V3 P, N;
+  gbuf_pixel<kCuda, kFrame>(sc, cam, ox + (int)x, oy + (int)y, id, t, P, N, zero);
+  const size_t i = (size_t)y * (size_t)W + x;
+  if (g.id) g.id[i] = id;
+  if (g.t) g.t[i] = t;
+  if constexpr (kFrame) {
+    if (g.P) {
+      float* q = g.P + 3 * i;
+      q[0] = P.x, q[1] = P.y, q[2] = P.z;
+    }
+    if (g.N) {
+      float* q = g.N + 3 * i;
+      q[0] = N.x, q[1] = N.y, q[2] = N.z;
+    }
+  }
+  if (!kCuda) flush_events(zero, zcount);
+}
+
+// k_gbuffer_points: one lane per point of rc_pick*: the lane reads its (X, Y) pair and stores its
+// 32-byte rc_hit as two 16-byte vector stores (hits is 16-byte aligned).  A point outside the
+// full_w x full_h image shoots no ray: id = -2, everything else +0.  The points are scattered, so
+// the scene is not staged.
+template <bool kCuda, bool kFrame>
+__global__ void __launch_bounds__(256) k_gbuffer_points(Scene sc, Cam cam, int full_w, int full_h,
+                                                        unsigned n, const int2* __restrict__ xy,
+                                                        float4* __restrict__ hits,
+                                                        unsigned long long* __restrict__ zcount) {
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;
+  const unsigned k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= n) return;
+  const int2 p = xy[k];
+  int id = -2, zero = 0;
+  float t = 0.0f;
+  V3 P = v3(0.0f, 0.0f, 0.0f), N = P;
+  if (p.x >= 0 && p.x < full_w && p.y >= 0 && p.y < full_h)
+    gbuf_pixel<kCuda, kFrame>(sc, cam, p.x, p.y, id, t, P, N, zero);
+  hits[2 * (size_t)k] = make_float4(__int_as_float(id), t, P.x, P.y);
+  hits[2 * (size_t)k + 1] = make_float4(P.z, N.x, N.y, N.z);
+  if (!kCuda) flush_events(zero, zcount);
+}
+
+// k_id_edge_rates: rates[y][x] = s where a pixel of the 3 x 3 neighbourhood, clipped to the image,
+// has another id than id[y][x], else base.  One lane per pixel in row-major order, nine clipped
+// loads (a wave's three rows of them are three runs of at most 66 dwords, served by the caches: the
+// kernel reads each id once from memory), one byte out.  pixels = W * H < 2^32.
+__global__ void __launch_bounds__(256) k_id_edge_rates(const int32_t* __restrict__ id, unsigned W,
+                                                       unsigned H, unsigned pixels, uint8_t s,
+                                                       uint8_t base, uint8_t* __restrict__ rates) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= pixels) return;
+  const unsigned y = i / W, x = i - y * W;
+  const unsigned x0 = x > 0u ? x - 1u : 0u, x1 = x + 1u < W ? x + 1u : x;
+  const unsigned y0 = y > 0u ? y - 1u : 0u, y1 = y + 1u < H ? y + 1u : y;
+  const int32_t me = id[i];
+  bool edge = false;
+  for (unsigned yy = y0; yy <= y1; ++yy) {
+    const int32_t* row = id + (size_t)yy * W;
+    for (unsigned xx = x0; xx <= x1; ++xx) edge = edge || row[xx] != me;
+  }
+  rates[i] = edge ? s : base;
+}
+
+// the pick image: both sides at least 1 (any size up to int: no grid is laid over it)
+static bool pick_image(int full_w, int full_h) { return full_w >= 1 && full_h >= 1; }
+
+hipError_t launch_gbuffer(const LaunchScene& s, const Window& w, int W, int H, int32_t* id,
+                          float* t, float* P, float* N, unsigned long long* zcount,
+                          hipStream_t stream, bool cuda_sem) {
+  const bool frame = P || N;
+  if (!window_supported(w, W, H, 1) || (!id && !t && !frame) || (cuda_sem && frame))
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((W + kTileW - 1) / kTileW), (unsigned)((H + kTileH - 1) / kTileH));
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, w.full_w, w.full_h);
+  const GbufPlanes g{id, t, P, N};
+  if (cuda_sem) {
+    hipLaunchKernelGGL((k_gbuffer<true, false, false>), grid, dim3(kBlock), 0, stream, sc, cam, W,
+                       H, w.x0, w.y0, g, zcount);
+  } else if (!frame) {
+    hipLaunchKernelGGL((k_gbuffer<false, false, false>), grid, dim3(kBlock), 0, stream, sc, cam, W,
+                       H, w.x0, w.y0, g, zcount);
+  } else {
+    dispatch(stage_fits(s), [&](auto st) {
+      hipLaunchKernelGGL((k_gbuffer<false, true, st.value>), grid, dim3(kBlock), 0, stream, sc,
+                         cam, W, H, w.x0, w.y0, g, zcount);
+    });
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_gbuffer_points(const LaunchScene& s, int full_w, int full_h, bool frame,
+                                 long long n, const int32_t* xy, void* hits,
+                                 unsigned long long* zcount, hipStream_t stream, bool cuda_sem) {
+  if (!pick_image(full_w, full_h) || n < 1 || n > (1ll << 24) || !xy || !hits ||
+      ((uintptr_t)hits & 15u) || (cuda_sem && frame))
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, full_w, full_h);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, sc, cam, full_w, full_h, (unsigned)n,
+                       (const int2*)xy, (float4*)hits, zcount);
+  };
+  if (cuda_sem) go(k_gbuffer_points<true, false>);
+  else if (frame) go(k_gbuffer_points<false, true>);
+  else go(k_gbuffer_points<false, false>);
+  return hipGetLastError();
+}
+
+int id_edge_rates_supported(int W, int H, int s, int base) {
+  return (s == 2 || s == 4 || s == 8) && (base == 0 || base == 1) && W >= 1 && H >= 1 &&
+         (unsigned long long)W * (unsigned long long)H < (1ull << 32);
+}
+
+hipError_t launch_id_edge_rates(const int32_t* id, int W, int H, int s, int base, uint8_t* rates,
+                                hipStream_t stream) {
+  if (!id || !rates || !id_edge_rates_supported(W, H, s, base)) return hipErrorInvalidValue;
+  const unsigned long long pixels = (unsigned long long)W * (unsigned long long)H;
+  hipLaunchKernelGGL(k_id_edge_rates, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, stream,
+                     id, (unsigned)W, (unsigned)H, (unsigned)pixels, (uint8_t)s, (uint8_t)base,
+                     rates);
   return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // rc_sampling.hip — the sampling features of libraycast_hip.so's C-ABI (include/raycast_hip.h):
-// rate maps, reconstruction filters, sparse sample patterns, progressive accumulation and windows
-// of a virtual image, with adaptive supersampling's getters.  Host code only: the kernels are
+// rate maps, reconstruction filters, sparse sample patterns, progressive accumulation, windows of a
+// virtual image and the primary-visibility G-buffer, with adaptive supersampling's getters.  Host code only: the kernels are
 // rc_sample_kernels.hip's and rc_filter.hip's (the one-ray image is rc_kernels.hip's k_render), the device context and the frame scaffold (enter,
 // ws_frame, claim_event_set, finish_device, finish_host) are rc_api.hip's, through rc_runtime.h.
 //
@@ -168,6 +168,27 @@ static int window_refused(const char* who, const rc_options* opt, int W, int H,
                           const rc_window* win) {
   return refused(kWindowRefusal, who, opt, W, H, 0, 0, false,
                  [&](int ss) { return rc_window_check(win, W, H, ss); }, no_check);
+}
+
+static const Refusal kGbufferRefusal = {
+    "Error: %s: ssaa %d carries an adaptive threshold: a G-buffer holds one primary hit a pixel; "
+    "the planes of the s x s image are a window of the s*full_w x s*full_h image\n",
+    1, "Error: %s: ssaa %d in the options: a G-buffer of the s x s image is a window of the "
+    "s*full_w x s*full_h image, leave ssaa at 0 or 1\n",
+    nullptr,   // parity mode is accepted: the primary hit does not involve the carry
+    "Error: %s: num_gpus %d: the row shards render no G-buffer\n",
+    nullptr};   // rc_window_check tests the sizes
+
+// frame: P or N is asked for.  image(): the entry's own test of its sizes (rc_window_check for the
+// planes, the image's sides for pick), which prints its own message.
+template <class Image>
+static int gbuffer_refused(const char* who, const rc_options* opt, bool frame, Image image) {
+  return refused(kGbufferRefusal, who, opt, 0, 0, 0, 0, false, [&](int) {
+    if (frame && opt->mode == RC_MODE_CUDA)
+      return say("Error: %s: the hit point and the normal (P, N, frame = 1) are for fast and parity "
+                 "mode: no reference pins the CUDA port's hit frame; ask for id and t\n", who);
+    return image();
+  }, no_check);
 }
 
 static int rates_refused(const char* who, const rc_options* opt, int W, int H) {
@@ -835,6 +856,33 @@ static int enqueue_window(DevCtx& c, const rc_scene* s, const rc_window* win, in
   });
 }
 
+// One G-buffer frame on `stream` through the device's one-frame workspace (the caller holds c.mu
+// and has passed gbuffer_refused): one launch of k_gbuffer for the window's pixels (pts null) or of
+// k_gbuffer_points for the n points.  It uses the workspace's scene and zero-normalize counter and
+// no other feature's record.
+struct GbufPoints {
+  int frame;
+  long long n;
+  const int32_t* xy;
+  rc_hit* hits;
+};
+static int enqueue_gbuffer(DevCtx& c, const rc_scene* s, const rc::Window& vw, int W, int H,
+                           const rc_options* opt, const rc_gbuffer* planes, const GbufPoints* pts,
+                           hipStream_t stream) {
+  return ws_frame(c, stream, [] { return 0; }, [&]() -> int {
+    SampleFrame f{c, stream, kSpanGbuffer};
+    if (f.begin(s, nullptr, 0)) return -1;
+    const bool cuda = opt->mode == RC_MODE_CUDA;
+    if (pts)
+      HIP_TRY(rc::launch_gbuffer_points(f.ls, vw.full_w, vw.full_h, pts->frame != 0, pts->n,
+                                        pts->xy, pts->hits, f.zc, stream, cuda));
+    else
+      HIP_TRY(rc::launch_gbuffer(f.ls, vw, W, H, planes->id, planes->t, planes->P, planes->N, f.zc,
+                                 stream, cuda));
+    return f.end();
+  });
+}
+
 // -------------------------------------------------------------- the two entry shapes --
 // A *_device entry behind its null checks and its refusal: on the current device, on the
 // caller's stream or the context's, enqueue(c, st), then finish_device.  plain: the frame goes
@@ -871,7 +919,9 @@ static int host_entry(const rc_options* opt, int W, int H, uint8_t* pixmap, rc_t
   Entered e;
   if (enter_host(opt, e)) return -1;
   DevCtx& c = *e.c;
-  const size_t bytes = (size_t)W * H * 3;
+  // a null pixmap: the call has no image (the G-buffer's entries); what ensure_more allocated is
+  // copied back by enqueue on c.stream, in front of finish_host's wait
+  const size_t bytes = pixmap ? (size_t)W * H * 3 : 0;
   if (c.out.ensure(bytes) || ensure_more(c)) return oom ? say(oom, W, H) : -1;
   const long long own = plain ? c.lone_log.head : kNoLog;
   if (enqueue(c)) return -1;
@@ -1038,6 +1088,160 @@ int rc_render_window(const rc_scene* s, const rc_window* win, int W, int H, cons
   return host_entry(opt, W, H, pixmap, timing, t0, kImageOom, false, nothing_more, [&](DevCtx& c) {
     return enqueue_window(c, s, win, W, H, opt, (uint8_t*)c.out.p, c.stream);
   });
+}
+
+// ------------------------------------------------ the primary-visibility G-buffer --
+// The tail's options of a G-buffer frame: one kernel between ev[0] and ev[1] whatever the mode, so
+// the timing record is filled as a fast frame's (everything parity-specific stays 0).
+static rc_options gbuffer_tail(const rc_options* opt) {
+  rc_options o = *opt;
+  o.mode = RC_MODE_FAST;
+  return o;
+}
+
+// rc_render_gbuffer and rc_render_gbuffer_device behind their null checks: the refusal and the
+// window the frame is shot through (win null: the whole W x H image)
+static int gbuffer_planes_refused(const char* who, const rc_options* opt, const rc_window* win,
+                                  int W, int H, const rc_gbuffer* planes, rc_window* vw) {
+  if (!planes->id && !planes->t && !planes->P && !planes->N)
+    return say("Error: %s: all four planes are null: ask for at least one of id, t, P and N\n",
+               who);
+  *vw = win ? *win : rc_window{W, H, 0, 0};
+  return gbuffer_refused(who, opt, planes->P || planes->N,
+                         [&] { return rc_window_check(vw, W, H, 1); });
+}
+
+int rc_render_gbuffer_device(const rc_scene* s, const rc_window* win, int W, int H,
+                             const rc_options* opt, const rc_gbuffer* d_planes, void* stream,
+                             rc_timing* timing) {
+  const char* who = "rc_render_gbuffer_device";
+  if (!s || !opt || !d_planes) return say("Error: %s: a null pointer\n", who);
+  rc_window vw;
+  if (gbuffer_planes_refused(who, opt, win, W, H, d_planes, &vw)) return -1;
+  const rc_options tail = gbuffer_tail(opt);
+  return device_entry(&tail, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_gbuffer(c, s, rc::Window{vw.full_w, vw.full_h, vw.x0, vw.y0}, W, H, opt,
+                           d_planes, nullptr, st);
+  });
+}
+
+int rc_render_gbuffer(const rc_scene* s, const rc_window* win, int W, int H, const rc_options* opt,
+                      const rc_gbuffer* planes, rc_timing* timing) {
+  const char* who = "rc_render_gbuffer";
+  if (!s || !opt || !planes) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  rc_window vw;
+  if (gbuffer_planes_refused(who, opt, win, W, H, planes, &vw)) return -1;
+  const rc_options tail = gbuffer_tail(opt);
+  const size_t px = (size_t)W * H * sizeof(float);
+  return host_entry(
+      &tail, W, H, nullptr, timing, t0,
+      "Error: out of device memory for the G-buffer's planes (%d x %d)\n", false,
+      [&](DevCtx& c) {   // device copies of the planes asked for
+        GbufFrame& g = c.gbuf;
+        return (planes->id && g.id.ensure(px)) || (planes->t && g.t.ensure(px)) ||
+               (planes->P && g.P.ensure(3 * px)) || (planes->N && g.N.ensure(3 * px));
+      },
+      [&](DevCtx& c) -> int {
+        const GbufFrame& g = c.gbuf;
+        const rc_gbuffer d{planes->id ? (int32_t*)g.id.p : nullptr,
+                           planes->t ? (float*)g.t.p : nullptr,
+                           planes->P ? (float*)g.P.p : nullptr,
+                           planes->N ? (float*)g.N.p : nullptr};
+        if (enqueue_gbuffer(c, s, rc::Window{vw.full_w, vw.full_h, vw.x0, vw.y0}, W, H, opt, &d,
+                            nullptr, c.stream))
+          return -1;
+        // behind the kernel on c.stream, in front of finish_host's wait
+        auto back = [&](void* host, const void* dev, size_t bytes) -> int {
+          if (host) HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c.stream));
+          return 0;
+        };
+        return back(planes->id, d.id, px) || back(planes->t, d.t, px) ||
+               back(planes->P, d.P, 3 * px) || back(planes->N, d.N, 3 * px);
+      });
+}
+
+// rc_pick and rc_pick_device behind their null checks
+static int pick_refused(const char* who, const rc_options* opt, int full_w, int full_h, int frame,
+                        int64_t n) {
+  if (gbuffer_refused(who, opt, frame != 0, [&] {
+        if (full_w >= 1 && full_h >= 1) return 0;
+        return say("Error: %s: a %d x %d image: both sides must be at least 1\n", who, full_w,
+                   full_h);
+      }))
+    return -1;
+  if (n < 1 || n > ((int64_t)1 << 24))
+    return say("Error: %s: n %lld is not 1 .. 2^24 points\n", who, (long long)n);
+  return 0;
+}
+
+int rc_pick_device(const rc_scene* s, int full_w, int full_h, const rc_options* opt, int frame,
+                   int64_t n, const int32_t* d_xy, rc_hit* d_hits, void* stream) {
+  const char* who = "rc_pick_device";
+  if (!s || !opt || !d_xy || !d_hits) return say("Error: %s: a null pointer\n", who);
+  if ((uintptr_t)d_hits & 15u)
+    return say("Error: %s: the records are not 16-byte aligned\n", who);
+  if (pick_refused(who, opt, full_w, full_h, frame, n)) return -1;
+  const rc_options tail = gbuffer_tail(opt);
+  const GbufPoints pts{frame, n, d_xy, d_hits};
+  return device_entry(&tail, stream, nullptr, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_gbuffer(c, s, rc::Window{full_w, full_h, 0, 0}, 0, 0, opt, nullptr, &pts, st);
+  });
+}
+
+int rc_pick(const rc_scene* s, int full_w, int full_h, const rc_options* opt, int frame, int64_t n,
+            const int32_t* xy, rc_hit* hits) {
+  const char* who = "rc_pick";
+  if (!s || !opt || !xy || !hits) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  if (pick_refused(who, opt, full_w, full_h, frame, n)) return -1;
+  for (int64_t k = 0; k < n; ++k) {
+    const int x = xy[2 * k], y = xy[2 * k + 1];
+    if (x < 0 || x >= full_w || y < 0 || y >= full_h)
+      return say("Error: %s: point %lld at (%d, %d) is outside the %d x %d image\n", who,
+                 (long long)k, x, y, full_w, full_h);
+  }
+  const rc_options tail = gbuffer_tail(opt);
+  const size_t nxy = (size_t)n * 2 * sizeof(int32_t), nhits = (size_t)n * sizeof(rc_hit);
+  return host_entry(
+      &tail, 0, 0, nullptr, nullptr, t0, "Error: out of device memory for the picked points\n",
+      false, [&](DevCtx& c) { return c.gbuf.xy.ensure(nxy) || c.gbuf.hits.ensure(nhits); },
+      [&](DevCtx& c) -> int {
+        const GbufPoints pts{frame, n, (const int32_t*)c.gbuf.xy.p, (rc_hit*)c.gbuf.hits.p};
+        HIP_TRY(hipMemcpyAsync(c.gbuf.xy.p, xy, nxy, hipMemcpyHostToDevice, c.stream));
+        if (enqueue_gbuffer(c, s, rc::Window{full_w, full_h, 0, 0}, 0, 0, opt, nullptr, &pts,
+                            c.stream))
+          return -1;
+        HIP_TRY(hipMemcpyAsync(hits, c.gbuf.hits.p, nhits, hipMemcpyDeviceToHost, c.stream));
+        return 0;
+      });
+}
+
+// No frame of the workspace: the edge map of an id plane alone, on the current device.
+int rc_id_edge_rates_device(const int32_t* d_id, int W, int H, int s, int base, uint8_t* d_rates,
+                            void* stream) {
+  const char* who = "rc_id_edge_rates_device";
+  if (!d_id || !d_rates) return say("Error: %s: a null pointer\n", who);
+  if (s != 2 && s != 4 && s != 8) return say("Error: %s: s %d is not 2, 4 or 8\n", who, s);
+  if (base != 0 && base != 1) return say("Error: %s: base %d is not 0 or 1\n", who, base);
+  if (W < 1 || H < 1)
+    return say("Error: %s: %d x %d: both sides must be at least 1\n", who, W, H);
+  if ((unsigned long long)W * (unsigned long long)H >= (1ull << 32))
+    return say("Error: %s: %d x %d is too large (32-bit pixel indices)\n", who, W, H);
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  HIP_TRY(rc::launch_id_edge_rates(d_id, W, H, s, base, d_rates,
+                                   stream ? (hipStream_t)stream : c->stream));
+  return 0;
+}
+
+int rc_gbuffer_phase_ms(double ms[1]) {
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanGbuffer];
+  return ev ? read_spans({ev[0], ev[1]}, ms) : -1;
 }
 
 // No frame of the workspace: the resolve of an accumulator alone, on the current device.
