@@ -780,6 +780,83 @@ int rc_id_edge_rates_device(const int32_t *d_id, int width, int height, int s, i
                             uint8_t *d_rates, void *stream);
 int rc_gbuffer_phase_ms(double ms[1]);
 
+/* Rotated camera views and caller-supplied ray batches (rc_render_view, rc_render_view_device,
+ * rc_trace_rays, rc_trace_rays_device; fast and cuda mode).  Every other entry shoots the
+ * reference camera's rays: eye at the origin, looking down -z, one ray per pixel of a regular
+ * grid.  A view turns that camera about the eye; a ray batch shoots whatever directions the caller
+ * supplies (a fisheye or equirectangular probe, a cube-map face, a stereo pair, the ray under the
+ * cursor of a turned view).
+ * The view contract.  rc_view.m is a 3 x 3 matrix M, row-major.  For virtual pixel (X, Y) of the
+ *     full_w x full_h image (with ssaa = s: subsample (X, Y) of the s*full_w x s*full_h image, as
+ *     for a window) let p = (px, py, -1) be the reference's unnormalised primary vector,
+ *         px = (float)(hx + (double)pw * ((double)X + 0.5)),
+ *         py = (float)(hy - (double)ph * ((double)Y + 0.5)),
+ *     hx = 0.0 - cam_w / 2.0, hy = 0.0 + cam_h / 2.0 in double, pw = cam_w / (float)full_w and
+ *     ph = cam_h / (float)full_h in float (C/raycast.c:109-118).  Then
+ *         q_i = (m[3i] * p.x + m[3i + 1] * p.y) + m[3i + 2] * p.z      (i = 0, 1, 2)
+ *     in float, every operation rounded once and nothing contracted, and the ray's direction D is
+ *     the mode's own normalize of q: the C port's (double sum of squares, a zero length leaves q
+ *     as it is and counts a zero_normalize event) in fast mode, the CUDA port's (float sum, no
+ *     guard) in cuda mode.  The matrix is applied before the single normalisation, so M need not
+ *     be orthonormal: an anamorphic or a mirrored view is legal, and M = identity gives the plain
+ *     camera's direction bit for bit.  The pixel's colour is the mode's bounce loop for D from the
+ *     origin, the oracle's rco_prim_shoot(D) / rco_prim_shoot_cuda(D); ssaa, the window and the
+ *     byte rounding are the window contract's: out = crop(box_s(view image at s*full)).
+ * The eye stays at the origin.  A moved eye is a translated scene: subtract the eye from every
+ *     position of the scene description (and fold the move into each quadric) and render that.
+ * rc_view_check: 0 when every entry of m is finite; otherwise (or for a null view) a message and
+ *     -1.  Nothing else is refused: a singular M gives zero or repeated directions, not an error.
+ * rc_render_view*: win = NULL is the whole W x H image, otherwise the W x H window of rc_window
+ *     (rc_window_check at the options' factor).  opt->ssaa is 0, 1, 2, 4 or 8.  rc_render_view
+ *     takes a host pixmap, is synchronous and runs on opt->device; rc_render_view_device takes
+ *     device memory (W*H*3 bytes), runs on the current device and the caller's stream (NULL: the
+ *     library's) and is asynchronous unless timing is requested.  One kernel, k_window's grid.
+ * rc_trace_rays*: ray k leaves the origin along (dirs[3k], dirs[3k + 1], dirs[3k + 2]), USED AS
+ *     GIVEN: it is not normalised, because the oracle's export does not normalise either; n in
+ *     1 .. 2^24.  rc_ray_out: any pointer may be null, at least one is not.  rgb (n x 3 floats) is
+ *     the colour before quantisation, rco_prim_shoot's bit for bit (what tone mapping and
+ *     compositing need); rgb8 (n x 3 bytes) is its quantisation, the bytes a frame stores; hits (n
+ *     records) is the G-buffer's rc_hit for that direction, rco_prim_nearest(O = 0, D, skip = -1):
+ *     id and t, and with frame = 1 P and N (+0.0f without; refused in cuda mode, as for rc_pick).
+ *     Picking in a turned view is rc_trace_rays of the cursor pixel's view direction.
+ *     rc_trace_rays takes host arrays; rc_trace_rays_device device arrays (the struct itself is
+ *     host memory, d_hits 16-byte aligned) and is asynchronous.
+ * rc_timing / zero_normalize: the events of the directions' normalisations and of the rays, as
+ *     the oracle counts them (cuda mode counts none).
+ * rc_view_phase_ms: ms[0] = the kernel span of the last view or ray frame enqueued on the current
+ *     device (it waits for it); -1 when there is none or another frame has reused its events.  A
+ *     view or ray frame touches no other feature's record: their stats survive it.
+ * Refused, each with one message and -1, from the arguments alone, in this order.  rc_render_view*:
+ *     a null scene, view, options or image; a factor outside 0, 1, 2, 4, 8; an adaptive threshold;
+ *     parity mode (its image is defined by the scan-order carry of the reference's own camera);
+ *     num_gpus > 1; what rc_view_check refuses; what rc_window_check refuses.  rc_trace_rays*: a
+ *     null scene, options, dirs or out; all three outputs null; d_hits not 16-byte aligned; a bad
+ *     factor; a threshold or a factor above 1 (a ray is one sample); parity mode; num_gpus > 1;
+ *     frame in cuda mode; n outside 1 .. 2^24.
+ * Out of scope: accumulation and scrolling through a view (a rotation is not a pan); a RAYCAST_*
+ *     variable or a CLI option for the view; a translated eye; parity mode; multi-GPU. */
+typedef struct rc_view { float m[9]; } rc_view;   /* row-major: q = M p */
+_Static_assert(sizeof(rc_view) == 36, "rc_view layout (ctypes binding)");
+typedef struct rc_ray_out {   /* any pointer may be NULL (not wanted); at least one is not */
+  uint8_t *rgb8;              /* n*3 : the quantised colour                                 */
+  float   *rgb;               /* n*3 : the colour before quantisation                       */
+  rc_hit  *hits;              /* n   : the primary hit's record                             */
+  int32_t  frame;             /* 1: P and N in the records too (fast mode only)             */
+} rc_ray_out;
+_Static_assert(sizeof(rc_ray_out) == 32, "rc_ray_out layout (ctypes binding)");
+int rc_view_check(const rc_view *view);
+int rc_render_view(const rc_scene *scene, const rc_view *view,
+                   const rc_window *win /* NULL: the whole image */, int width, int height,
+                   const rc_options *opt, uint8_t *pixmap, rc_timing *timing);
+int rc_render_view_device(const rc_scene *scene, const rc_view *view, const rc_window *win,
+                          int width, int height, const rc_options *opt, uint8_t *d_out,
+                          void *stream, rc_timing *timing);
+int rc_trace_rays(const rc_scene *scene, const rc_options *opt, int64_t n,
+                  const float *dirs /* n x 3 */, const rc_ray_out *out /* host */);
+int rc_trace_rays_device(const rc_scene *scene, const rc_options *opt, int64_t n,
+                         const float *d_dirs, const rc_ray_out *d_out, void *stream);
+int rc_view_phase_ms(double ms[1]);
+
 /* Frames in flight(an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out
  * (W*H*3 bytes, device memory, ready for use: synchronise the stream that produced it

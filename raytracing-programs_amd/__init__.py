@@ -172,6 +172,24 @@ assert HIT_DTYPE.itemsize == ctypes.sizeof(RcHit) == ctypes.sizeof(RcGbuffer) ==
 PICK_MAX_POINTS = 1 << 24
 
 
+class RcView(ctypes.Structure):
+    """rc_view (36 bytes): the 3 x 3 view matrix, row-major."""
+    _fields_ = [("m", ctypes.c_float * 9)]
+
+
+class RcRayOut(ctypes.Structure):
+    """rc_ray_out (32 bytes): the three output pointers of a ray batch, null for one that is not
+    wanted, and the frame flag (P and N in the records)."""
+    _fields_ = [("rgb8", ctypes.c_void_p), ("rgb", ctypes.c_void_p), ("hits", ctypes.c_void_p),
+                ("frame", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(RcView) == 36 and ctypes.sizeof(RcRayOut) == 32
+RAYS_MAX = 1 << 24
+# the outputs of a ray batch in rc_ray_out's order: name -> (dtype, trailing shape)
+RAY_OUTPUTS = {"rgb8": (np.uint8, (3,)), "rgb": (np.float32, (3,)), "hits": (HIT_DTYPE, ())}
+
+
 def _hier_points(g):
     """hier<g> (include/raycast_hip.h, rc_sample_seq): point k is the bit-reversal r of k over
     2 * log2 g bits; x takes r's even bits and y its odd bits."""
@@ -272,7 +290,9 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_accum_phase_ms", "rc_window_check", "rc_window_env", "rc_render_window",
                "rc_render_window_device", "rc_accum_pass_window_device",
                "rc_render_gbuffer", "rc_render_gbuffer_device", "rc_pick", "rc_pick_device",
-               "rc_id_edge_rates_device", "rc_gbuffer_phase_ms"]
+               "rc_id_edge_rates_device", "rc_gbuffer_phase_ms", "rc_view_check",
+               "rc_render_view", "rc_render_view_device", "rc_trace_rays",
+               "rc_trace_rays_device", "rc_view_phase_ms"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -480,6 +500,21 @@ def _hip_lib_locked():
                                             ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                             ctypes.c_void_p]
     lib.rc_gbuffer_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    lib.rc_view_check.argtypes = [ctypes.POINTER(RcView)]
+    lib.rc_render_view.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcView),
+                                   ctypes.POINTER(RcWindow), ctypes.c_int, ctypes.c_int,
+                                   ctypes.POINTER(RcOptions), ctypes.c_void_p,
+                                   ctypes.POINTER(RcTiming)]
+    lib.rc_render_view_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcView),
+                                          ctypes.POINTER(RcWindow), ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(RcOptions), ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.POINTER(RcTiming)]
+    lib.rc_trace_rays.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcOptions), ctypes.c_int64,
+                                  ctypes.c_void_p, ctypes.POINTER(RcRayOut)]
+    lib.rc_trace_rays_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcOptions),
+                                         ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.POINTER(RcRayOut), ctypes.c_void_p]
+    lib.rc_view_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
     _hip = lib
     return lib
 
@@ -1549,6 +1584,163 @@ def gbuffer_phase_ms():
     """The kernel span of the last G-buffer or pick frame (rc_gbuffer_phase_ms), in ms."""
     return _phase_ms("rc_gbuffer_phase_ms", ("kernel",),
                      "rc_gbuffer_phase_ms: no G-buffer frame on this device")
+
+
+def view_identity():
+    """The view that changes nothing: rc_render_view with it is rc_render_window, byte for byte."""
+    return np.eye(3, dtype=np.float32)
+
+
+def view_euler(yaw, pitch, roll=0.0):
+    """Ry(yaw) . Rx(pitch) . Rz(roll), radians, right-handed rotations about +y, +x and +z, computed
+    in double and rounded to float: the camera looks down -z, so a positive yaw turns it to the left
+    ("look right 30 degrees" is yaw = -pi / 6), a positive pitch up, and a positive roll rolls it
+    counter-clockwise.  A convenience: the contract takes the nine floats as given, the
+    trigonometry is not part of it."""
+    cy, sy = np.cos(np.float64(yaw)), np.sin(np.float64(yaw))
+    cx, sx = np.cos(np.float64(pitch)), np.sin(np.float64(pitch))
+    cz, sz = np.cos(np.float64(roll)), np.sin(np.float64(roll))
+    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]], np.float64)
+    rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]], np.float64)
+    rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]], np.float64)
+    return ((ry @ rx @ rz) + 0.0).astype(np.float32)     # + 0.0: no -0 entries
+
+
+def _view_matrix(m):
+    m = np.asarray(m)
+    if m.size != 9:
+        raise ValueError(f"view: a 3 x 3 matrix (or nine floats, row-major), got shape {m.shape}")
+    return np.ascontiguousarray(m, dtype=np.float32).reshape(3, 3)
+
+
+def _rc_view(m):
+    return RcView((ctypes.c_float * 9)(*_view_matrix(m).ravel().tolist()))
+
+
+def view_check(m):
+    """rc_view_check: True when the library takes that matrix (every entry finite; its message
+    goes to stderr otherwise)."""
+    return hip_lib().rc_view_check(ctypes.byref(_rc_view(m))) == 0
+
+
+def view_dirs(camera_w, camera_h, full, xy, m, cuda=False):
+    """The view contract (include/raycast_hip.h, rc_view) in numpy, operation for operation: the
+    [n, 3] float32 directions of the virtual pixels xy ([n, 2] integers, (X, Y) pairs) of the full
+    = (full_w, full_h) image of a camera_w x camera_h view plane under the matrix m.  With ssaa = s
+    pass the subsamples' coordinates and full = (s * full_w, s * full_h).  p = (px, py, -1) is the
+    reference's unnormalised primary vector, q = m p in float with every operation rounded once,
+    and the direction is the mode's normalize of q: the C port's (a double sum of squares, a zero
+    length leaves q as it is) or with cuda the CUDA port's (a float sum, no guard)."""
+    f32, f64 = np.float32, np.float64
+    m = _view_matrix(m)
+    xy = np.asarray(xy)
+    if xy.ndim != 2 or xy.shape[1] != 2 or xy.dtype.kind not in "iu":
+        raise ValueError(f"view_dirs: xy is an integer [n, 2] array of (X, Y) pairs, got {xy.dtype} "
+                         f"{xy.shape}")
+    fw, fh = (int(v) for v in full)
+    cw, ch = f32(camera_w), f32(camera_h)
+    pw, ph = cw / f32(fw), ch / f32(fh)
+    px = ((0.0 - f64(cw) / 2.0) + f64(pw) * (xy[:, 0].astype(f64) + 0.5)).astype(f32)
+    py = ((0.0 + f64(ch) / 2.0) - f64(ph) * (xy[:, 1].astype(f64) + 0.5)).astype(f32)
+    pz = np.full(len(px), -1.0, f32)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        q = np.stack([(m[i, 0] * px + m[i, 1] * py) + m[i, 2] * pz for i in range(3)], 1)
+        assert q.dtype == f32
+        if cuda:
+            s = q[:, 0] * q[:, 0]
+            s = s + q[:, 1] * q[:, 1]
+            s = s + q[:, 2] * q[:, 2]
+            ln = np.sqrt(s.astype(f64)).astype(f32)
+            return (q / ln[:, None]).astype(f32)
+        d = q.astype(f64)
+        s = d[:, 0] * d[:, 0]
+        s = s + d[:, 1] * d[:, 1]
+        s = s + d[:, 2] * d[:, 2]
+        ln = np.sqrt(s).astype(f32)
+        zero = ln == 0.0
+        out = (q / np.where(zero, f32(1.0), ln)[:, None]).astype(f32)
+        out[zero] = q[zero]
+        return out
+
+
+def view_grid(width, height, x0=0, y0=0):
+    """The (X, Y) pairs of a width x height block of pixels at (x0, y0), row-major: view_dirs' xy
+    for a whole image or a window."""
+    ys, xs = np.mgrid[y0:y0 + height, x0:x0 + width]
+    return np.stack([xs.ravel(), ys.ravel()], 1).astype(np.int64)
+
+
+def render_view(scene, m, width, height, window=None, ssaa=1, depth=6, mode="fast", device=0,
+                timing=None, out=None):
+    """rc_render_view: the width x height image (or, with window = (full_w, full_h, x0, y0), that
+    window of the virtual image) of the camera turned by the view matrix m: pixel colours are the
+    bounce loop along view_dirs' directions, box-filtered at ssaa.  Fast and cuda mode."""
+    view = _rc_view(m)
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    out = _pixmap(out, width, height)
+    opt = options(depth, mode, 1, device, ssaa)
+    with _timed(timing) as (t, _):
+        _call("rc_render_view", scene.packed(), ctypes.byref(view), win, width, height,
+              ctypes.byref(opt), _host_ptr(out), ctypes.byref(t))
+    return out
+
+
+def render_view_device(scene, m, width, height, d_out_ptr, window=None, ssaa=1, stream_ptr=None,
+                       depth=6, mode="fast", timing=None):
+    """rc_render_view_device: the image (W*H*3 bytes) is device memory; enqueued on the stream and
+    asynchronous unless `timing` is given."""
+    view = _rc_view(m)
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    opt = options(depth, mode, ssaa=ssaa)
+    with _timed(timing) as (_, t):
+        _call("rc_render_view_device", scene.packed(), ctypes.byref(view), win, width, height,
+              ctypes.byref(opt), ctypes.c_void_p(d_out_ptr), _stream(stream_ptr), t)
+
+
+def _ray_dirs(dirs):
+    dirs = np.asarray(dirs)
+    if dirs.ndim != 2 or dirs.shape[1] != 3:
+        raise ValueError(f"trace_rays: dirs is an [n, 3] array of directions, got {dirs.shape}")
+    if not 1 <= len(dirs) <= RAYS_MAX:
+        raise ValueError(f"trace_rays: {len(dirs)} rays, not 1 .. {RAYS_MAX}")
+    return np.ascontiguousarray(dirs, dtype=np.float32)
+
+
+def trace_rays(scene, dirs, outputs=("rgb8",), frame=False, depth=6, mode="fast", device=0):
+    """rc_trace_rays: the rays from the origin along dirs ([n, 3] float32, used as given: not
+    normalised), as a dict of numpy arrays, one per requested output: "rgb" [n, 3] float32 (the
+    colour before quantisation), "rgb8" [n, 3] uint8 (its bytes) and "hits" [n] HIT_DTYPE (the
+    primary hit; frame: P and N too, fast mode only).  Any projection is its directions; picking
+    in a turned view is trace_rays(view_dirs(cursor pixel), ("hits",))."""
+    d = _ray_dirs(dirs)
+    names = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    for p in names:
+        if p not in RAY_OUTPUTS:
+            raise ValueError(f"trace_rays: output {p!r} is not one of {tuple(RAY_OUTPUTS)}")
+    out = {p: np.zeros((len(d),) + RAY_OUTPUTS[p][1], dtype=RAY_OUTPUTS[p][0])
+           for p in RAY_OUTPUTS if p in names}
+    ro = RcRayOut(frame=int(bool(frame)), **{p: a.ctypes.data for p, a in out.items()})
+    opt = options(depth, mode, 1, device)
+    _call("rc_trace_rays", scene.packed(), ctypes.byref(opt), len(d), _host_ptr(d),
+          ctypes.byref(ro))
+    return out
+
+
+def trace_rays_device(scene, n, d_dirs_ptr, d_rgb8_ptr=None, d_rgb_ptr=None, d_hits_ptr=None,
+                      frame=False, stream_ptr=None, depth=6, mode="fast"):
+    """rc_trace_rays_device: n directions (n x 3 float32) and the outputs (n x 3 bytes, n x 3
+    float32, n 32-byte HIT_DTYPE records 16-byte aligned; None: not wanted) in device memory,
+    enqueued on the stream."""
+    ro = RcRayOut(d_rgb8_ptr or None, d_rgb_ptr or None, d_hits_ptr or None, int(bool(frame)))
+    opt = options(depth, mode)
+    _call("rc_trace_rays_device", scene.packed(), ctypes.byref(opt), int(n),
+          ctypes.c_void_p(d_dirs_ptr), ctypes.byref(ro), _stream(stream_ptr))
+
+
+def view_phase_ms():
+    """The kernel span of the last view or ray frame (rc_view_phase_ms), in ms."""
+    return _phase_ms("rc_view_phase_ms", ("kernel",),
+                     "rc_view_phase_ms: no view or ray frame on this device")
 
 
 def window_from_env(width, height, mode="fast", ssaa=1, adaptive=0, gpus=1):

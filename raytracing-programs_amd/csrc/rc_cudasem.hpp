@@ -269,5 +269,43 @@ __device__ __forceinline__ V3 render_pixel(const Scene& sc, const Cam& cam, int 
   return v3(out.x + prim.x, out.y + prim.y, out.z + prim.z);
 }
 
+// iterative_shoot (CUDA/raycast.cu:183-246) for a primary direction d from the origin, used as
+// given: render_pixel behind its first five lines, the oracle's rco_prim_shoot_cuda
+// (rc_render_view*, rc_trace_rays*).  The loop is stated twice on purpose: with render_pixel
+// written as its direction and a call of this routine (d by value or by reference) rc_kernels.o
+// was no longer the parent's byte for byte, and the existing kernels must not move (DESIGN.md
+// §23).  tests/test_gpu_view.py holds the two together: the identity view's cuda image
+// is rc_render_window's, byte for byte.
+__device__ __forceinline__ V3 shoot_dir(const Scene& sc, V3 d, int max_iter) {
+  float t0;
+  const int i0 = cu_nearest(sc, v3(0.0f, 0.0f, 0.0f), d, -1, t0);
+  if (i0 < 0) return v3(0.0f, 0.0f, 0.0f);
+  V3 P0, N0;
+  cu_hit_frame(sc, i0, v3(0.0f, 0.0f, 0.0f), d, t0, P0, N0);
+  const V3 prim = cu_shade(sc, i0, P0, N0, d);   // added last, as in render_pixel
+  int obj = i0, S = i0;
+  V3 O = P0, D = d, N = N0;
+  float T = sc.lshapes[i0].refl;
+  V3 out = v3(0.0f, 0.0f, 0.0f);
+  for (int it = 0; it < max_iter; ++it) {
+    if (!reflective(sc, obj)) break;
+    D = cu_normalize(reflect(D, N));
+    float t;
+    const int i = cu_nearest(sc, O, D, S, t);
+    if (i < 0) break;
+    V3 P;
+    cu_hit_frame(sc, i, O, D, t, P, N);
+    obj = i;
+    const V3 col = cu_shade(sc, i, P, N, D);
+    out.x = out.x + col.x * T;
+    out.y = out.y + col.y * T;
+    out.z = out.z + col.z * T;
+    T = T * sc.lshapes[obj].refl;
+    O = P;
+    S = i;
+  }
+  return v3(out.x + prim.x, out.y + prim.y, out.z + prim.z);
+}
+
 }  // namespace cusem
 }  // namespace rc

@@ -291,6 +291,26 @@ int id_edge_rates_supported(int W, int H, int s, int base);
 hipError_t launch_id_edge_rates(const int32_t* id, int W, int H, int s, int base, uint8_t* rates,
                                 hipStream_t stream);
 
+// Rotated camera views and caller-supplied ray batches (rc_render_view*, rc_trace_rays*; fast and
+// cuda modes): rays from the origin whose directions are not the pinhole grid's.
+//   launch_view  launch_window with the view matrix m (rc_view::m, row-major) applied to the
+//                unnormalised primary vector of every subsample before the one normalisation;
+//                the same grid, lanes and limits (window_supported);
+//   launch_rays  one lane per direction, n in 1 .. 2^24; dirs: n x 3 floats used as given; any of
+//                rgb8 (n x 3 bytes), rgb (n x 3 floats, the colour before quantisation) and hits
+//                (n 32-byte rc_hit records, 16-byte aligned) may be null, one is not; frame: P and
+//                N in the records (not in cuda mode).
+// The launchers return hipErrorInvalidValue for what breaks these rules.
+struct View {
+  float m[9];
+};
+hipError_t launch_view(const LaunchScene& s, const View& v, const Window& w, int W, int H,
+                       int ssaa, int maxrec, uint8_t* out, unsigned long long* zcount,
+                       hipStream_t stream, bool cuda_sem);
+hipError_t launch_rays(const LaunchScene& s, long long n, const float* dirs, int maxrec,
+                       uint8_t* rgb8, float* rgb, void* hits, bool frame,
+                       unsigned long long* zcount, hipStream_t stream, bool cuda_sem);
+
 // ------------------- defined in rc_kernels.hip: the renderer, the parity pipeline, row shards --
 // cuda_sem: RC_MODE_CUDA (the CUDA port's arithmetic, rc_cudasem.hpp) instead of fast mode
 hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_step, int nrows,

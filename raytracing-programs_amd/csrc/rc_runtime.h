@@ -166,7 +166,7 @@ struct Pipe {
 // The sampling features whose frames leave phase spans behind (DevCtx::span_ev).
 enum SpanOwner {
   kSpanAdaptive, kSpanRates, kSpanFilter, kSpanPattern, kSpanAccum, kSpanWindow, kSpanGbuffer,
-  kSpanOwners
+  kSpanView, kSpanOwners
 };
 
 // The sampling features' frame records.  Each documents the events its rc_*_phase_ms reads out
@@ -240,6 +240,13 @@ struct GbufFrame {
   DevBuf xy, hits;      // rc_pick's points and records
 };
 
+// Rotated views and ray batches (rc_render_view*, rc_trace_rays*): the host entry's device copies
+// of the directions and of the outputs it was asked for; rc_render_view uses DevCtx::out and the
+// *_device entries the caller's memory.  Spans: [0] start, [1] end of the one kernel.
+struct ViewFrame {
+  DevBuf dirs, rgb8, rgb, hits;   // rc_trace_rays' arrays
+};
+
 struct DevCtx {
   bool init = false;
   int device = 0;
@@ -271,10 +278,11 @@ struct DevCtx {
   DevBuf accum_px;
   AccumFrame acc;
   GbufFrame gbuf;      // the G-buffer's host entries
+  ViewFrame view;      // rc_trace_rays' arrays
   // The event set whose spans each sampling feature's rc_*_phase_ms may still read, null once
   // another frame has recorded that set anew (claim_event_set).  Which events of the set a
   // feature reads is documented at its record above; window (rc_render_window*): [0] start,
-  // [1] end; the G-buffer and pick frames likewise.
+  // [1] end; the G-buffer and pick frames and the view and ray frames likewise.
   hipEvent_t* span_ev[kSpanOwners] = {};
   uint8_t* stage[2] = {nullptr, nullptr};   // pinned bounce buffers of copy_to_host
   hipEvent_t stage_ev[2] = {nullptr, nullptr};

@@ -31,6 +31,10 @@
 //                 the primary-visibility G-buffer (fast, parity and cuda modes): the primary hit's
 //                 shape, distance, point and normal per pixel of a window or per picked point,
 //                 nothing shaded; and the rate map of the id plane's 3 x 3 edges.
+//   k_view / k_rays
+//                 rays that are not the pinhole grid's (fast and cuda modes): k_window through a
+//                 view matrix, and a batch of the caller's own directions, one lane each, with
+//                 the colour before quantisation, its bytes and the primary hit's record.
 #include "rc_cudasem.hpp"
 #include "rc_pixel.hpp"
 
@@ -1509,6 +1513,166 @@ hipError_t launch_id_edge_rates(const int32_t* id, int W, int H, int s, int base
   hipLaunchKernelGGL(k_id_edge_rates, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, stream,
                      id, (unsigned)W, (unsigned)H, (unsigned)pixels, (uint8_t)s, (uint8_t)base,
                      rates);
+  return hipGetLastError();
+}
+
+// ------------------- rotated camera views and ray batches (fast, cuda) --
+// rc_render_view*, rc_trace_rays* (include/raycast_hip.h, rc_view): rays from the origin whose
+// directions are not the pinhole grid's.  No new intersection or shading arithmetic: a direction
+// goes through shoot<kModeFast> (cuda: cusem::shoot_dir, render_pixel's loop) and through
+// nearest_primary / hit_frame (cu_nearest) exactly as a primary ray does.
+//
+// view_dir: primary_dir with the view matrix between the unnormalised vector p = (px, py, -1) and
+// the one normalisation: q_i = dot(row_i, p) (two products and two sums, each rounded once), then
+// the mode's own normalize of q.  v is a kernel argument, so its nine floats are scalar registers
+// and the nine products take them as scalar operands.
+template <bool kCuda>
+__device__ __forceinline__ V3 view_dir(const Cam& cam, const View& v, int x, int y,
+                                       int& zero_events) {
+  V3 p;
+  p.x = (float)(cam.hx + (double)cam.pw * ((double)x + 0.5));
+  p.y = (float)(cam.hy - (double)cam.ph * ((double)y + 0.5));
+  p.z = -1.0f;
+  const V3 q = v3(dot(v3(v.m[0], v.m[1], v.m[2]), p), dot(v3(v.m[3], v.m[4], v.m[5]), p),
+                  dot(v3(v.m[6], v.m[7], v.m[8]), p));
+  if constexpr (kCuda) return cusem::cu_normalize(q);
+  else return normalize(q, zero_events);
+}
+
+// The colour of the ray from the origin along d, used as given: the mode's bounce loop
+// (sample_shoot's two branches behind their directions).
+template <bool kCuda>
+__device__ __forceinline__ V3 dir_shoot(const Scene& sc, V3 d, int maxrec, int& zero_events) {
+  if constexpr (kCuda) {
+    return cusem::shoot_dir(sc, d, maxrec - 1);
+  } else {
+    PixelOut po;
+    shoot<kModeFast>(sc, d, maxrec, v3(0.0f, 0.0f, 0.0f), po, zero_events);
+    return po.rgb;
+  }
+}
+
+// k_view: k_window (its grid, lane layout, bounds test, reduction and stores, line for line) with
+// view_dir in primary_dir's place.  A kernel of its own: k_window sits at the 128-register edge
+// and must not move.
+template <bool kCuda, bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_view(
+    Scene sc, Cam cam, View v, int W, int H, int ls, int ox, int oy, int maxrec,
+    uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount) {
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  stage_scene<kStage>(sc, stage);
+  int bx, by;
+  xcd_tile<0>(bx, by);
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const unsigned sub = lane & ((1u << (2 * ls)) - 1u);
+  const unsigned grp = lane >> (2 * ls);
+  const int lgw = 3 - ls;
+  const unsigned xs = (unsigned)bx * kTileW + (wave % (kTileW / 8)) * 8u +
+                      ((grp & ((1u << lgw) - 1u)) << ls) + (sub & ((1u << ls) - 1u));
+  const unsigned rs = (unsigned)by * kTileH + (wave / (kTileW / 8)) * 8u + ((grp >> lgw) << ls) +
+                      (sub >> ls);
+  const bool inside = (xs >> ls) < (unsigned)W && (rs >> ls) < (unsigned)H;
+  unsigned rg = 0u, b = 0u;
+  if (inside) {
+    int zero = 0;
+    const V3 d = view_dir<kCuda>(cam, v, ox + (int)xs, oy + (int)rs, zero);
+    const V3 c = dir_shoot<kCuda>(sc, d, maxrec, zero);
+    rg = (unsigned)quant(c.x) | ((unsigned)quant(c.y) << 16);
+    b = quant(c.z);
+    if (!kCuda) flush_events(zero, zcount);
+  }
+  sample_reduce(rg, b, 2 * ls);
+  if (inside && sub == 0u) {   // the group's first lane
+    uint8_t* q = out + ((size_t)(rs >> ls) * W + (xs >> ls)) * 3;
+    if (ls == 0) {
+      q[0] = (uint8_t)(rg & 0xffffu);
+      q[1] = (uint8_t)(rg >> 16);
+      q[2] = (uint8_t)b;
+    } else {
+      sample_store(q, rg, b, 2 * ls);
+    }
+  }
+}
+
+// The outputs of a ray batch, null: not wanted (a kernel argument, so the tests are wave-uniform).
+struct RayOut {
+  uint8_t* rgb8;
+  float* rgb;
+  float4* hits;
+};
+
+// k_rays: one lane per direction of rc_trace_rays*, read as three dwords at a 12-byte stride and
+// used as given.  The colour (when rgb or rgb8 is wanted) is dir_shoot's; the record (when hits is)
+// is the primary hit's, gbuf_pixel's scan and frame for that direction, stored as
+// k_gbuffer_points' two 16-byte stores.  The directions are arbitrary, so the scene is not staged.
+template <bool kCuda, bool kFrame>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_rays(
+    Scene sc, unsigned n, const float* __restrict__ dirs, int maxrec, RayOut o,
+    unsigned long long* __restrict__ zcount) {
+  static_assert(!(kCuda && kFrame), "no reference pins the CUDA port's hit frame");
+  if (!kCuda && !RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;
+  const unsigned k = blockIdx.x * (unsigned)kBlock + threadIdx.x;
+  if (k >= n) return;
+  const float* p = dirs + 3 * (size_t)k;
+  const V3 d = v3(p[0], p[1], p[2]);
+  int zero = 0;
+  // the record first: nothing of it stays live across the bounce loop, which then holds only k
+  if (o.hits) {
+    int id;
+    float t;
+    V3 P = v3(0.0f, 0.0f, 0.0f), N = P;
+    if constexpr (kCuda) id = cusem::cu_nearest(sc, v3(0.0f, 0.0f, 0.0f), d, -1, t);
+    else id = nearest_primary(sc, d, t);
+    if (id < 0) t = 0.0f;
+    if constexpr (kFrame)
+      if (id >= 0) hit_frame(sc, id, v3(0.0f, 0.0f, 0.0f), d, t, P, N, zero);
+    o.hits[2 * (size_t)k] = make_float4(__int_as_float(id), t, P.x, P.y);
+    o.hits[2 * (size_t)k + 1] = make_float4(P.z, N.x, N.y, N.z);
+  }
+  if (o.rgb || o.rgb8) {
+    const V3 c = dir_shoot<kCuda>(sc, d, maxrec, zero);
+    if (o.rgb) {
+      float* q = o.rgb + 3 * (size_t)k;
+      q[0] = c.x, q[1] = c.y, q[2] = c.z;
+    }
+    if (o.rgb8) store_rgb(o.rgb8 + 3 * (size_t)k, c);
+  }
+  if (!kCuda) flush_events(zero, zcount);
+}
+
+hipError_t launch_view(const LaunchScene& s, const View& v, const Window& w, int W, int H,
+                       int ssaa, int maxrec, uint8_t* out, unsigned long long* zcount,
+                       hipStream_t stream, bool cuda_sem) {
+  if (!window_supported(w, W, H, ssaa)) return hipErrorInvalidValue;
+  const int ls = ssaa == 1 ? 0 : ssaa_log2(ssaa);
+  dim3 grid((unsigned)(((unsigned long long)W * ssaa + kTileW - 1) / kTileW),
+            (unsigned)(((unsigned long long)H * ssaa + kTileH - 1) / kTileH));
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, w.full_w * ssaa, w.full_h * ssaa);   // of the s*full_w x s*full_h image
+  dispatch(cuda_sem, stage_fits(s), [&](auto cuda, auto st) {
+    hipLaunchKernelGGL((k_view<cuda.value, st.value>), grid, dim3(kBlock), 0, stream, sc, cam, v,
+                       W, H, ls, w.x0 * ssaa, w.y0 * ssaa, maxrec, out, zcount);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_rays(const LaunchScene& s, long long n, const float* dirs, int maxrec,
+                       uint8_t* rgb8, float* rgb, void* hits, bool frame,
+                       unsigned long long* zcount, hipStream_t stream, bool cuda_sem) {
+  if (n < 1 || n > (1ll << 24) || !dirs || (!rgb8 && !rgb && !hits) ||
+      ((uintptr_t)hits & 15u) || (cuda_sem && frame && hits))   // frame says nothing without hits
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+  const Scene sc = make_scene(s);
+  const RayOut o{rgb8, rgb, (float4*)hits};
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, stream, sc, (unsigned)n, dirs, maxrec, o,
+                       zcount);
+  };
+  if (cuda_sem) go(k_rays<true, false>);
+  else if (frame && hits) go(k_rays<false, true>);
+  else go(k_rays<false, false>);
   return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // rc_sampling.hip — the sampling features of libraycast_hip.so's C-ABI (include/raycast_hip.h):
 // rate maps, reconstruction filters, sparse sample patterns, progressive accumulation, windows of a
-// virtual image and the primary-visibility G-buffer, with adaptive supersampling's getters.  Host code only: the kernels are
+// virtual image, the primary-visibility G-buffer and rotated views and ray batches, with adaptive
+// supersampling's getters.  Host code only: the kernels are
 // rc_sample_kernels.hip's and rc_filter.hip's (the one-ray image is rc_kernels.hip's k_render), the device context and the frame scaffold (enter,
 // ws_frame, claim_event_set, finish_device, finish_host) are rc_api.hip's, through rc_runtime.h.
 //
@@ -188,6 +189,40 @@ static int gbuffer_refused(const char* who, const rc_options* opt, bool frame, I
       return say("Error: %s: the hit point and the normal (P, N, frame = 1) are for fast and parity "
                  "mode: no reference pins the CUDA port's hit frame; ask for id and t\n", who);
     return image();
+  }, no_check);
+}
+
+static const Refusal kViewRefusal = {
+    "Error: %s: ssaa %d carries an adaptive threshold: a view is shot at a plain factor\n",
+    0, nullptr,
+    "Error: %s: views are for fast and cuda mode: a parity image is defined by the scan-order "
+    "carry of the reference's own camera\n",
+    "Error: %s: num_gpus %d: the row shards take no view\n",
+    nullptr};   // rc_window_check tests the sizes
+
+static int view_refused(const char* who, const rc_options* opt, int W, int H, const rc_view* view,
+                        const rc_window* vw) {
+  return refused(kViewRefusal, who, opt, W, H, 0, 0, false, [&](int ss) {
+    return rc_view_check(view) || rc_window_check(vw, W, H, ss);
+  }, no_check);
+}
+
+static const Refusal kRaysRefusal = {
+    "Error: %s: ssaa %d carries an adaptive threshold: a ray is one sample, leave ssaa at 0 or 1\n",
+    1, "Error: %s: ssaa %d in the options: a ray is one sample, leave ssaa at 0 or 1\n",
+    "Error: %s: ray batches are for fast and cuda mode: a parity colour is defined by the "
+    "scan-order carry of the reference's own camera\n",
+    "Error: %s: num_gpus %d: the row shards trace no ray batch\n",
+    nullptr};
+
+static int rays_refused(const char* who, const rc_options* opt, int64_t n, const rc_ray_out* out) {
+  return refused(kRaysRefusal, who, opt, 0, 0, 0, 0, false, [&](int) {
+    if (out->frame && out->hits && opt->mode == RC_MODE_CUDA)
+      return say("Error: %s: the hit point and the normal (frame = 1) are for fast mode: no "
+                 "reference pins the CUDA port's hit frame; ask for id and t\n", who);
+    if (n < 1 || n > ((int64_t)1 << 24))
+      return say("Error: %s: n %lld is not 1 .. 2^24 rays\n", who, (long long)n);
+    return 0;
   }, no_check);
 }
 
@@ -575,6 +610,16 @@ int rc_window_env(const rc_options* opt, int W, int H, rc_window* out) {
   return 1;
 }
 
+// ------------------------------------------------------------- rotated camera views --
+int rc_view_check(const rc_view* v) {
+  const char* who = "rc_view_check";
+  if (!v) return say("Error: %s: a null view\n", who);
+  for (int k = 0; k < 9; ++k)
+    if (!__builtin_isfinite(v->m[k]))
+      return say("Error: %s: m[%d] (row %d, column %d) is not finite\n", who, k, k / 3, k % 3);
+  return 0;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ enqueue bodies --
@@ -879,6 +924,37 @@ static int enqueue_gbuffer(DevCtx& c, const rc_scene* s, const rc::Window& vw, i
     else
       HIP_TRY(rc::launch_gbuffer(f.ls, vw, W, H, planes->id, planes->t, planes->P, planes->N, f.zc,
                                  stream, cuda));
+    return f.end();
+  });
+}
+
+// One view frame or one ray batch on `stream` through the device's one-frame workspace (the caller
+// holds c.mu and has passed view_refused or rays_refused): one launch of k_view at the options'
+// factor for the window's pixels (rays null), or of k_rays for the n directions.  It uses the
+// workspace's scene and zero-normalize counter and no other feature's record.
+struct RayBatch {
+  long long n;
+  const float* dirs;
+  rc_ray_out out;
+};
+static int enqueue_view(DevCtx& c, const rc_scene* s, const rc_view* view, const rc_window* vw,
+                        int W, int H, const rc_options* opt, uint8_t* d_out, const RayBatch* rays,
+                        hipStream_t stream) {
+  return ws_frame(c, stream, [] { return 0; }, [&]() -> int {
+    SampleFrame f{c, stream, kSpanView};
+    if (f.begin(s, nullptr, 0)) return -1;
+    const bool cuda = opt->mode == RC_MODE_CUDA;
+    if (rays) {
+      HIP_TRY(rc::launch_rays(f.ls, rays->n, rays->dirs, opt->max_recursion, rays->out.rgb8,
+                              rays->out.rgb, rays->out.hits, rays->out.frame != 0, f.zc, stream,
+                              cuda));
+    } else {
+      rc::View v;
+      std::memcpy(v.m, view->m, sizeof v.m);
+      HIP_TRY(rc::launch_view(f.ls, v, rc::Window{vw->full_w, vw->full_h, vw->x0, vw->y0}, W, H,
+                              ssaa_factor(opt, "rc_render_view"), opt->max_recursion, d_out, f.zc,
+                              stream, cuda));
+    }
     return f.end();
   });
 }
@@ -1241,6 +1317,95 @@ int rc_gbuffer_phase_ms(double ms[1]) {
   Entered e;
   if (!ms || enter(kCurrentDevice, false, e)) return -1;
   hipEvent_t* ev = e.c->span_ev[kSpanGbuffer];
+  return ev ? read_spans({ev[0], ev[1]}, ms) : -1;
+}
+
+// ------------------------------------------- rotated camera views and ray batches --
+int rc_render_view_device(const rc_scene* s, const rc_view* view, const rc_window* win, int W,
+                          int H, const rc_options* opt, uint8_t* d_out, void* stream,
+                          rc_timing* timing) {
+  const char* who = "rc_render_view_device";
+  if (!s || !view || !opt || !d_out) return say("Error: %s: a null pointer\n", who);
+  const rc_window vw = win ? *win : rc_window{W, H, 0, 0};
+  if (view_refused(who, opt, W, H, view, &vw)) return -1;
+  return device_entry(opt, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_view(c, s, view, &vw, W, H, opt, d_out, nullptr, st);
+  });
+}
+
+int rc_render_view(const rc_scene* s, const rc_view* view, const rc_window* win, int W, int H,
+                   const rc_options* opt, uint8_t* pixmap, rc_timing* timing) {
+  const char* who = "rc_render_view";
+  if (!s || !view || !opt || !pixmap) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  const rc_window vw = win ? *win : rc_window{W, H, 0, 0};
+  if (view_refused(who, opt, W, H, view, &vw)) return -1;
+  return host_entry(opt, W, H, pixmap, timing, t0, kImageOom, false, nothing_more, [&](DevCtx& c) {
+    return enqueue_view(c, s, view, &vw, W, H, opt, (uint8_t*)c.out.p, nullptr, c.stream);
+  });
+}
+
+// rc_trace_rays and rc_trace_rays_device behind their null checks
+static int rays_out_refused(const char* who, const rc_ray_out* out) {
+  if (out->rgb8 || out->rgb || out->hits) return 0;
+  return say("Error: %s: all three outputs are null: ask for at least one of rgb8, rgb and hits\n",
+             who);
+}
+
+int rc_trace_rays_device(const rc_scene* s, const rc_options* opt, int64_t n, const float* d_dirs,
+                         const rc_ray_out* d_out, void* stream) {
+  const char* who = "rc_trace_rays_device";
+  if (!s || !opt || !d_dirs || !d_out) return say("Error: %s: a null pointer\n", who);
+  if (rays_out_refused(who, d_out)) return -1;
+  if ((uintptr_t)d_out->hits & 15u)
+    return say("Error: %s: the records are not 16-byte aligned\n", who);
+  if (rays_refused(who, opt, n, d_out)) return -1;
+  const RayBatch rays{n, d_dirs, *d_out};
+  return device_entry(opt, stream, nullptr, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_view(c, s, nullptr, nullptr, 0, 0, opt, nullptr, &rays, st);
+  });
+}
+
+int rc_trace_rays(const rc_scene* s, const rc_options* opt, int64_t n, const float* dirs,
+                  const rc_ray_out* out) {
+  const char* who = "rc_trace_rays";
+  if (!s || !opt || !dirs || !out) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  if (rays_out_refused(who, out)) return -1;
+  if (rays_refused(who, opt, n, out)) return -1;
+  const size_t n3 = (size_t)n * 3, nhits = (size_t)n * sizeof(rc_hit);
+  return host_entry(
+      opt, 0, 0, nullptr, nullptr, t0, "Error: out of device memory for the ray batch\n", false,
+      [&](DevCtx& c) {   // device copies of the directions and of the outputs asked for
+        ViewFrame& v = c.view;
+        return v.dirs.ensure(n3 * sizeof(float)) || (out->rgb8 && v.rgb8.ensure(n3)) ||
+               (out->rgb && v.rgb.ensure(n3 * sizeof(float))) ||
+               (out->hits && v.hits.ensure(nhits));
+      },
+      [&](DevCtx& c) -> int {
+        const ViewFrame& v = c.view;
+        const RayBatch rays{n, (const float*)v.dirs.p,
+                            rc_ray_out{out->rgb8 ? (uint8_t*)v.rgb8.p : nullptr,
+                                       out->rgb ? (float*)v.rgb.p : nullptr,
+                                       out->hits ? (rc_hit*)v.hits.p : nullptr, out->frame}};
+        HIP_TRY(hipMemcpyAsync(v.dirs.p, dirs, n3 * sizeof(float), hipMemcpyHostToDevice,
+                               c.stream));
+        if (enqueue_view(c, s, nullptr, nullptr, 0, 0, opt, nullptr, &rays, c.stream)) return -1;
+        // behind the kernel on c.stream, in front of finish_host's wait
+        auto back = [&](void* host, const void* dev, size_t bytes) -> int {
+          if (host) HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c.stream));
+          return 0;
+        };
+        return back(out->rgb8, rays.out.rgb8, n3) ||
+               back(out->rgb, rays.out.rgb, n3 * sizeof(float)) ||
+               back(out->hits, rays.out.hits, nhits);
+      });
+}
+
+int rc_view_phase_ms(double ms[1]) {
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanView];
   return ev ? read_spans({ev[0], ev[1]}, ms) : -1;
 }
 
