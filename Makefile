@@ -108,6 +108,16 @@ $(OBJ)/pa6_kernels.o: $(SRC)/rc_kernels.hip $(HIP_HDRS)
 $(LIB)/libraycast_hip_%.so: $(OBJ)/%_kernels.o $(OBJ)/rc_api.o $(PLAIN_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ $(HIPLIBS)
 
+# measurement variants of k_camera (scripts/camera_ab.py): the eye's LDS table (camtable) against
+# the general nearest with O = eye (camgen); every other kernel of both is the product's
+camera-variants: $(LIB)/libraycast_hip_camtable.so $(LIB)/libraycast_hip_camgen.so
+$(OBJ)/camtable_sample_kernels.o: $(SRC)/rc_sample_kernels.hip $(HIP_HDRS)
+	$(HIPCC) $(HIPFLAGS) -DRC_CAMERA_TABLE=1 -c $< -o $@
+$(OBJ)/camgen_sample_kernels.o: $(SRC)/rc_sample_kernels.hip $(HIP_HDRS)
+	$(HIPCC) $(HIPFLAGS) -DRC_CAMERA_TABLE=0 -c $< -o $@
+$(LIB)/libraycast_hip_cam%.so: $(OBJ)/rc_kernels.o $(OBJ)/rc_api.o $(OBJ)/cam%_sample_kernels.o $(filter-out $(OBJ)/rc_sample_kernels.o,$(PLAIN_OBJS))
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ $(HIPLIBS)
+
 # ASan + UBSan builds of the host C (tests/test_sanitize.py; SURVEY.md §5: the CPU restatement
 # must not rely on UB): the oracle's CLI and the front end (parse / lists / P3 writer) driven
 # by tests/tools/front_check.c.  Host code only; no GPU code is sanitized.

@@ -802,8 +802,7 @@ int rc_gbuffer_phase_ms(double ms[1]);
  *     camera's direction bit for bit.  The pixel's colour is the mode's bounce loop for D from the
  *     origin, the oracle's rco_prim_shoot(D) / rco_prim_shoot_cuda(D); ssaa, the window and the
  *     byte rounding are the window contract's: out = crop(box_s(view image at s*full)).
- * The eye stays at the origin.  A moved eye is a translated scene: subtract the eye from every
- *     position of the scene description (and fold the move into each quadric) and render that.
+ * The eye stays at the origin here; rc_render_camera (below) moves it.
  * rc_view_check: 0 when every entry of m is finite; otherwise (or for a null view) a message and
  *     -1.  Nothing else is refused: a singular M gives zero or repeated directions, not an error.
  * rc_render_view*: win = NULL is the whole W x H image, otherwise the W x H window of rc_window
@@ -834,7 +833,7 @@ int rc_gbuffer_phase_ms(double ms[1]);
  *     factor; a threshold or a factor above 1 (a ray is one sample); parity mode; num_gpus > 1;
  *     frame in cuda mode; n outside 1 .. 2^24.
  * Out of scope: accumulation and scrolling through a view (a rotation is not a pan); a RAYCAST_*
- *     variable or a CLI option for the view; a translated eye; parity mode; multi-GPU. */
+ *     variable or a CLI option for the view; parity mode; multi-GPU. */
 typedef struct rc_view { float m[9]; } rc_view;   /* row-major: q = M p */
 _Static_assert(sizeof(rc_view) == 36, "rc_view layout (ctypes binding)");
 typedef struct rc_ray_out {   /* any pointer may be NULL (not wanted); at least one is not */
@@ -856,6 +855,62 @@ int rc_trace_rays(const rc_scene *scene, const rc_options *opt, int64_t n,
 int rc_trace_rays_device(const rc_scene *scene, const rc_options *opt, int64_t n,
                          const float *d_dirs, const rc_ray_out *d_out, void *stream);
 int rc_view_phase_ms(double ms[1]);
+
+/* A free camera and rays with origins (rc_render_camera, rc_render_camera_device,
+ * rc_trace_rays_from, rc_trace_rays_from_device; fast mode).  The view family with an origin: a
+ * fly-through camera, a stereo pair with a real baseline, a thin-lens bundle, and secondary rays
+ * of the caller's own that leave the hit points rc_render_gbuffer and rc_trace_rays hand out.
+ * The camera contract.  rc_camera is an eye and a view.  The direction of every ray is the view
+ *     contract's D for cam->view (above), unchanged: moving the eye does not touch the direction
+ *     arithmetic.  The origin of every ray is cam->eye, used as given (a -0 component stays -0).
+ *     The ray's colour is the fast-mode bounce loop from (eye, D): with the oracle's exports,
+ *         (i, t) = rco_prim_nearest(eye, D, skip = -1); a miss is black;
+ *         (P, N) = the hit frame of i at eye + t D; obj = S = i; T = refl[i]; out = 0;
+ *         for level 1 .. max_recursion - 1: stop unless refl[obj] > 0;
+ *             D = normalize(reflect(D, N))      (float; the length is (float)sqrt of the double
+ *                                                sum of squares, a zero length leaves D);
+ *             (i, t) = rco_prim_nearest(P, D, skip = S); stop at a miss; (P, N) = its frame;
+ *             out += rco_prim_shade(i, P, N, D) * T; T *= refl[i]; obj = S = i;
+ *         colour = out + rco_prim_shade of the primary hit.
+ *     At eye = +0 this is rco_prim_shoot(D) bit for bit (tests/test_camera.py), so eye = 0 with
+ *     the matrix M is rc_render_view(M), and with the identity the plain fast-mode image.  ssaa,
+ *     the window and the byte rounding are the window contract's.
+ * rc_camera_check: 0 when every component of eye and every entry of view.m is finite; otherwise
+ *     (or for a null camera) one message and -1.
+ * rc_render_camera*: the arguments, the stream semantics, rc_timing and the spans are
+ *     rc_render_view*'s.  One kernel, k_window's grid.  Nothing is kept between calls and nothing
+ *     is shared between two calls in flight: the eye is a kernel argument, and no scratch buffer
+ *     in device memory holds anything derived from it.
+ * rc_trace_rays_from*: rc_trace_rays* with ray k leaving (origins[3k], origins[3k + 1],
+ *     origins[3k + 2]).  rc_ray_out as there; hits is rco_prim_nearest(O, D, skip = -1), with
+ *     frame = 1 P and N too.  Origins are data (device data for the _device entry) and are not
+ *     checked: a non-finite origin gives what the oracle gives, a miss.
+ * rc_view_phase_ms also reads the span of the last camera or origin-ray frame: the four entries
+ *     record the view family's event set.
+ * Refused, each with one message and -1, before any device work.  rc_render_camera*: a null
+ *     scene, camera, options or image; what rc_render_view refuses, in its order, with cuda mode
+ *     refused after num_gpus (the oracle exports no hit frame for the CUDA port, so nothing could
+ *     pin a colour there); what rc_camera_check refuses; what rc_window_check refuses.
+ *     rc_trace_rays_from*: a null scene, options, origins, dirs or out; then what rc_trace_rays
+ *     refuses, with cuda mode refused after num_gpus.
+ * Out of scope: cuda and parity mode; accumulation and scrolling with a camera; a G-buffer plane
+ *     entry for cameras (rc_trace_rays_from with hits alone is the pick); any-hit queries with a
+ *     distance bound; multi-GPU. */
+typedef struct rc_camera { float eye[3]; rc_view view; } rc_camera;
+_Static_assert(sizeof(rc_camera) == 48, "rc_camera layout (ctypes binding)");
+int rc_camera_check(const rc_camera *cam);
+int rc_render_camera(const rc_scene *scene, const rc_camera *cam,
+                     const rc_window *win /* NULL: the whole image */, int width, int height,
+                     const rc_options *opt, uint8_t *pixmap, rc_timing *timing);
+int rc_render_camera_device(const rc_scene *scene, const rc_camera *cam, const rc_window *win,
+                            int width, int height, const rc_options *opt, uint8_t *d_out,
+                            void *stream, rc_timing *timing);
+int rc_trace_rays_from(const rc_scene *scene, const rc_options *opt, int64_t n,
+                       const float *origins /* n x 3 */, const float *dirs /* n x 3 */,
+                       const rc_ray_out *out /* host */);
+int rc_trace_rays_from_device(const rc_scene *scene, const rc_options *opt, int64_t n,
+                              const float *d_origins, const float *d_dirs,
+                              const rc_ray_out *d_out, void *stream);
 
 /* Frames in flight(an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out

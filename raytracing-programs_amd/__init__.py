@@ -184,7 +184,13 @@ class RcRayOut(ctypes.Structure):
                 ("frame", ctypes.c_int32)]
 
 
+class RcCamera(ctypes.Structure):
+    """rc_camera (48 bytes): the eye and the view."""
+    _fields_ = [("eye", ctypes.c_float * 3), ("view", RcView)]
+
+
 assert ctypes.sizeof(RcView) == 36 and ctypes.sizeof(RcRayOut) == 32
+assert ctypes.sizeof(RcCamera) == 48
 RAYS_MAX = 1 << 24
 # the outputs of a ray batch in rc_ray_out's order: name -> (dtype, trailing shape)
 RAY_OUTPUTS = {"rgb8": (np.uint8, (3,)), "rgb": (np.float32, (3,)), "hits": (HIT_DTYPE, ())}
@@ -292,7 +298,9 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_render_gbuffer", "rc_render_gbuffer_device", "rc_pick", "rc_pick_device",
                "rc_id_edge_rates_device", "rc_gbuffer_phase_ms", "rc_view_check",
                "rc_render_view", "rc_render_view_device", "rc_trace_rays",
-               "rc_trace_rays_device", "rc_view_phase_ms"]
+               "rc_trace_rays_device", "rc_view_phase_ms", "rc_camera_check",
+               "rc_render_camera", "rc_render_camera_device", "rc_trace_rays_from",
+               "rc_trace_rays_from_device"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -515,6 +523,20 @@ def _hip_lib_locked():
                                          ctypes.c_int64, ctypes.c_void_p,
                                          ctypes.POINTER(RcRayOut), ctypes.c_void_p]
     lib.rc_view_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    lib.rc_camera_check.argtypes = [ctypes.POINTER(RcCamera)]
+    lib.rc_render_camera.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcCamera),
+                                     ctypes.POINTER(RcWindow), ctypes.c_int, ctypes.c_int,
+                                     ctypes.POINTER(RcOptions), ctypes.c_void_p,
+                                     ctypes.POINTER(RcTiming)]
+    lib.rc_render_camera_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcCamera),
+                                            ctypes.POINTER(RcWindow), ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(RcOptions), ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.POINTER(RcTiming)]
+    lib.rc_trace_rays_from.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcOptions), ctypes.c_int64,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(RcRayOut)]
+    lib.rc_trace_rays_from_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcOptions),
+                                              ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.POINTER(RcRayOut), ctypes.c_void_p]
     _hip = lib
     return lib
 
@@ -1738,9 +1760,94 @@ def trace_rays_device(scene, n, d_dirs_ptr, d_rgb8_ptr=None, d_rgb_ptr=None, d_h
 
 
 def view_phase_ms():
-    """The kernel span of the last view or ray frame (rc_view_phase_ms), in ms."""
+    """The kernel span of the last view, camera or ray frame (rc_view_phase_ms), in ms: the camera
+    entries and the rays with origins record the view family's spans."""
     return _phase_ms("rc_view_phase_ms", ("kernel",),
                      "rc_view_phase_ms: no view or ray frame on this device")
+
+
+def camera(eye, m=None):
+    """(eye, m): the three eye floats and the nine matrix floats (3 x 3, row-major) of an rc_camera
+    as float32 arrays, used as given; m = None is the identity.  The directions of the camera are
+    view_dirs(..., m), unchanged by the eye, and every ray's origin is eye."""
+    e = np.asarray(eye)
+    if e.size != 3:
+        raise ValueError(f"camera: eye is three floats, got shape {e.shape}")
+    return (np.ascontiguousarray(e, dtype=np.float32).reshape(3),
+            view_identity() if m is None else _view_matrix(m))
+
+
+def _rc_camera(eye, m):
+    e, m = camera(eye, m)
+    return RcCamera((ctypes.c_float * 3)(*e.tolist()), RcView((ctypes.c_float * 9)(*m.ravel().tolist())))
+
+
+def camera_check(eye, m=None):
+    """rc_camera_check: True when the library takes that camera (every eye component and matrix
+    entry finite; its message goes to stderr otherwise)."""
+    return hip_lib().rc_camera_check(ctypes.byref(_rc_camera(eye, m))) == 0
+
+
+def render_camera(scene, eye, m, width, height, window=None, ssaa=1, depth=6, device=0,
+                  mode="fast", timing=None, out=None):
+    """rc_render_camera: render_view with the eye moved to `eye`: the width x height image (or that
+    window of the virtual image) whose pixel colours are the fast-mode bounce loop from eye along
+    view_dirs' directions (m = None: the identity), box-filtered at ssaa.  Fast mode only."""
+    cam = _rc_camera(eye, m)
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    out = _pixmap(out, width, height)
+    opt = options(depth, mode, 1, device, ssaa)
+    with _timed(timing) as (t, _):
+        _call("rc_render_camera", scene.packed(), ctypes.byref(cam), win, width, height,
+              ctypes.byref(opt), _host_ptr(out), ctypes.byref(t))
+    return out
+
+
+def render_camera_device(scene, eye, m, width, height, d_out_ptr, window=None, ssaa=1,
+                         stream_ptr=None, depth=6, mode="fast", timing=None):
+    """rc_render_camera_device: the image (W*H*3 bytes) is device memory; enqueued on the stream
+    and asynchronous unless `timing` is given."""
+    cam = _rc_camera(eye, m)
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    opt = options(depth, mode, ssaa=ssaa)
+    with _timed(timing) as (_, t):
+        _call("rc_render_camera_device", scene.packed(), ctypes.byref(cam), win, width, height,
+              ctypes.byref(opt), ctypes.c_void_p(d_out_ptr), _stream(stream_ptr), t)
+
+
+def trace_rays_from(scene, origins, dirs, outputs=("rgb8",), frame=False, depth=6, mode="fast",
+                    device=0):
+    """rc_trace_rays_from: trace_rays with ray k leaving origins[k] ([n, 3] float32, used as given
+    and not checked: a non-finite origin is a miss, as in the oracle): the rays an occlusion or a
+    gather pass shoots from the hit points of a G-buffer.  Fast mode only."""
+    d = _ray_dirs(dirs)
+    o = np.asarray(origins)
+    if o.shape != d.shape:
+        raise ValueError(f"trace_rays_from: origins is an [n, 3] array like dirs {d.shape}, got "
+                         f"{o.shape}")
+    o = np.ascontiguousarray(o, dtype=np.float32)
+    names = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    for p in names:
+        if p not in RAY_OUTPUTS:
+            raise ValueError(f"trace_rays_from: output {p!r} is not one of {tuple(RAY_OUTPUTS)}")
+    out = {p: np.zeros((len(d),) + RAY_OUTPUTS[p][1], dtype=RAY_OUTPUTS[p][0])
+           for p in RAY_OUTPUTS if p in names}
+    ro = RcRayOut(frame=int(bool(frame)), **{p: a.ctypes.data for p, a in out.items()})
+    opt = options(depth, mode, 1, device)
+    _call("rc_trace_rays_from", scene.packed(), ctypes.byref(opt), len(d), _host_ptr(o),
+          _host_ptr(d), ctypes.byref(ro))
+    return out
+
+
+def trace_rays_from_device(scene, n, d_origins_ptr, d_dirs_ptr, d_rgb8_ptr=None, d_rgb_ptr=None,
+                           d_hits_ptr=None, frame=False, stream_ptr=None, depth=6, mode="fast"):
+    """rc_trace_rays_from_device: n origins and n directions (n x 3 float32 each) and the outputs
+    (as trace_rays_device's; None: not wanted) in device memory, enqueued on the stream."""
+    ro = RcRayOut(d_rgb8_ptr or None, d_rgb_ptr or None, d_hits_ptr or None, int(bool(frame)))
+    opt = options(depth, mode)
+    _call("rc_trace_rays_from_device", scene.packed(), ctypes.byref(opt), int(n),
+          ctypes.c_void_p(d_origins_ptr), ctypes.c_void_p(d_dirs_ptr), ctypes.byref(ro),
+          _stream(stream_ptr))
 
 
 def window_from_env(width, height, mode="fast", ssaa=1, adaptive=0, gpus=1):

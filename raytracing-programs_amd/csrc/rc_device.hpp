@@ -891,6 +891,177 @@ __device__ __forceinline__ void shoot(const Scene& sc, V3 d, int maxrec, V3 carr
   po.carry = C;
 }
 
+// ------------------------------------------------------------- rays with an origin --
+// rc_render_camera*, rc_trace_rays_from*: the primary ray leaves O0 instead of the origin.
+//
+// The eye of a camera frame is one point for every ray of the frame, so each shape test's
+// origin-only term is a per-shape constant, as rc_shape::o0 is for the eye at +0.  EyeShape holds
+// them, computed by hit_sphere's, hit_plane's and quad_abc's own operations in their own order
+// (eye_shape), so a test that reads them (nearest_eye) gives the general test's bits:
+//   sphere   tv = O - p and c = (float)((double)dot(tv, tv) - r2);
+//   plane    num = dot(O - p, n);
+//   quadric  cq whole (cross terms included unless x0), and b's three leading double products
+//            (2.0 * A) * O.x, (2.0 * B) * O.y, (2.0 * C) * O.z: `2.0 * q.A * (double)O.x *
+//            (double)D.x` associates left to right, so the prefix is a value of the expression.
+// No term is dropped (unlike the o0 forms), so the signs of zeros and a -0 eye come out as in
+// nearest and no o0_ok-style condition is needed.
+struct EyeShape {
+  float tv[3];   // sphere: O - p
+  float c;       // sphere: c; plane: num; quadric: cq
+  double b[3];   // quadric: b's prefixes
+};
+
+__device__ __forceinline__ EyeShape eye_shape(const rc_shape& s, V3 O, bool x0) {
+  EyeShape e;
+  e.tv[0] = e.tv[1] = e.tv[2] = e.c = 0.0f;
+  e.b[0] = e.b[1] = e.b[2] = 0.0;
+  if (s.type == RC_SHAPE_SPHERE) {
+    const V3 tv = v3(O.x - s.p[0], O.y - s.p[1], O.z - s.p[2]);
+    e.tv[0] = tv.x, e.tv[1] = tv.y, e.tv[2] = tv.z;
+    e.c = (float)((double)dot(tv, tv) - s.r2);
+  } else if (s.type == RC_SHAPE_PLANE) {
+    e.c = dot(v3(O.x - s.p[0], O.y - s.p[1], O.z - s.p[2]), v3(s.n[0], s.n[1], s.n[2]));
+  } else if (s.type == RC_SHAPE_QUADRIC) {
+    double acc;
+    acc = s.A * ((double)O.x * (double)O.x);
+    acc = acc + s.B * ((double)O.y * (double)O.y);
+    acc = acc + s.C * ((double)O.z * (double)O.z);
+    if (!x0) {
+      acc = acc + (double)(s.qd * O.x * O.y);
+      acc = acc + (double)(s.qe * O.x * O.z);
+      acc = acc + (double)(s.qf * O.y * O.z);
+    }
+    acc = acc + (double)(s.qg * O.x);
+    acc = acc + (double)(s.qh * O.y);
+    acc = acc + (double)(s.qi * O.z);
+    acc = acc + (double)s.qj;
+    e.c = (float)acc;
+    e.b[0] = 2.0 * s.A * (double)O.x;
+    e.b[1] = 2.0 * s.B * (double)O.y;
+    e.b[2] = 2.0 * s.C * (double)O.z;
+  }
+  return e;
+}
+
+// nearest(sc, O, D, -1, tbest) with the origin-only terms read from tb (tb[k] = eye_shape of
+// shape k at O): hit_sphere, hit_plane and hit_quadric behind those terms, line for line.
+__device__ __forceinline__ int nearest_eye(const Scene& sc, V3 O, V3 D, const EyeShape* tb,
+                                           float& tbest) {
+  const RayK rk = ray_consts(D);
+  const bool x0 = quad_x0(sc), rej = x0 && x0_reject(O, D);
+  float best = __builtin_inff();
+  int idx = -1;
+  for (int k = 0; k < sc.n; ++k) {
+    const rc_shape& s = sc.shapes[k];
+    const EyeShape& e = tb[k];
+    float t = 0.0f;
+    bool hit = false;
+    if (s.type == RC_SHAPE_SPHERE) {
+      const float b = 2.0f * dot(D, v3(e.tv[0], e.tv[1], e.tv[2]));
+      const float fac = rk.a4 * e.c;
+      const float disc = (float)__builtin_fma((double)b, (double)b, -(double)fac);
+      if (!(disc < 0.0f)) {
+        const double sq = sqrt_ns((double)disc);
+        const float t1 = pin(tquot((double)(-b) - sq, rk.den, rk.yden));
+        const float t2 = pin(tquot((double)(-b) + sq, rk.den, rk.yden));
+        t = t1 < 0.0f ? t2 : t1;
+        hit = true;
+      }
+    } else if (s.type == RC_SHAPE_PLANE) {
+      const float den = dot(D, v3(s.n[0], s.n[1], s.n[2]));
+      if (den != 0.0f) {
+        const float tt = (-e.c) / den;
+        if (!(tt < 0.0f)) {
+          t = tt;
+          hit = true;
+        }
+      }
+    } else if (s.type == RC_SHAPE_QUADRIC) {
+      double acc;
+      acc = s.A * ((double)D.x * (double)D.x);
+      acc = acc + s.B * ((double)D.y * (double)D.y);
+      acc = acc + s.C * ((double)D.z * (double)D.z);
+      if (!x0) {
+        acc = acc + (double)(s.qd * D.x * D.y);
+        acc = acc + (double)(s.qe * D.x * D.z);
+        acc = acc + (double)(s.qf * D.y * D.z);
+      }
+      const float aq = (float)acc;
+      acc = e.b[0] * (double)D.x;
+      acc = acc + e.b[1] * (double)D.y;
+      acc = acc + e.b[2] * (double)D.z;
+      if (!x0) {
+        acc = acc + (double)(s.qd * (O.x * D.y + O.y * D.x));
+        acc = acc + (double)(s.qe * (O.x * D.z + O.z * D.x));
+        acc = acc + (double)(s.qf * (O.y * D.z + O.z * D.y));
+      }
+      acc = acc + (double)(s.qg * D.x);
+      acc = acc + (double)(s.qh * D.y);
+      acc = acc + (double)(s.qi * D.z);
+      const float bq = (float)acc;
+      const float cq = e.c;
+      if (!rej) {
+        if ((double)aq == 0.0) {
+          t = tquot(-1.0 * (double)cq, (double)bq, RC_NRDIV ? recip_nr((double)bq) : 0.0);
+          hit = true;
+        } else {
+          const float disc =
+              (float)__builtin_fma((double)bq, (double)bq, -(4.0 * (double)aq * (double)cq));
+          if (!((double)disc < 0.0)) {
+            const double den = 2.0 * (double)aq;
+            const double sq = sqrt_ns((double)disc);
+            const double y = RC_NRDIV ? recip_nr(den) : 0.0;
+            const float t1 = pin(tquot((double)(-bq) - sq, den, y));
+            const float t2 = pin(tquot((double)(-bq) + sq, den, y));
+            t = t1 <= 0.0f ? t2 : t1;
+            hit = true;
+          }
+        }
+      }
+    }
+    if (hit && best > t && t > 0.0f) {
+      best = t;
+      idx = k;
+    }
+  }
+  tbest = best;
+  return idx;
+}
+
+// shoot<kModeFast> for a primary ray that leaves O0: the primary hit i0 at t0 is the caller's
+// (nearest(sc, O0, d, -1, t0), or nearest_eye with a camera frame's table), hit_frame takes O0,
+// and the bounce loop is shoot's.  A routine of its own beside shoot, not a parameter of it: the
+// kernels that instantiate shoot<> sit at the 128-register edge and must keep their instructions.
+__device__ __forceinline__ V3 shoot_from(const Scene& sc, V3 O0, V3 d, int i0, float t0,
+                                         int maxrec, int& zero_events) {
+  if (i0 < 0) return v3(0.0f, 0.0f, 0.0f);
+  V3 P0, N0;
+  hit_frame(sc, i0, O0, d, t0, P0, N0, zero_events);
+  const V3 prim = shade(sc, i0, P0, N0, d, zero_events);   // added last, as in shoot
+  int obj = i0, S = i0;
+  V3 O = P0, D = d, N = N0;
+  float T = sc.lshapes[i0].refl;
+  V3 out = v3(0.0f, 0.0f, 0.0f);
+  for (int lvl = 1; lvl < maxrec; ++lvl) {
+    if (!reflective(sc, obj)) break;
+    D = normalize(reflect(D, N), zero_events);
+    float t;
+    const int i = nearest(sc, O, D, S, t);
+    if (i < 0) break;
+    V3 P;
+    hit_frame(sc, i, O, D, t, P, N, zero_events);
+    obj = i;
+    const V3 col = shade(sc, i, P, N, D, zero_events);
+    out.x = out.x + col.x * T;
+    out.y = out.y + col.y * T;
+    out.z = out.z + col.z * T;
+    T = T * sc.lshapes[obj].refl;
+    O = P;
+    S = i;
+  }
+  return v3(out.x + prim.x, out.y + prim.y, out.z + prim.z);
+}
+
 // Phase C of a DEP pixel under dep_fast, from its carry-in c: the bounce loop of
 // iterative_shoot (C/raycast.c:348-376) resumed at level 2, then the primary shade phase A
 // computed (the record's p*, C/raycast.c:377-378).  Level 1 missed: its shade is the black phantom's

@@ -311,6 +311,18 @@ hipError_t launch_rays(const LaunchScene& s, long long n, const float* dirs, int
                        uint8_t* rgb8, float* rgb, void* hits, bool frame,
                        unsigned long long* zcount, hipStream_t stream, bool cuda_sem);
 
+// A free camera and rays with origins (rc_render_camera*, rc_trace_rays_from*; fast mode only).
+//   launch_camera     launch_view with every primary ray leaving eye (three floats, used as
+//                     given); an eye of three +0 is launch_view itself;
+//   launch_rays_from  launch_rays with an origin per ray (origins: n x 3 floats, device memory,
+//                     not looked at by the launcher).
+hipError_t launch_camera(const LaunchScene& s, const float eye[3], const View& v, const Window& w,
+                         int W, int H, int ssaa, int maxrec, uint8_t* out,
+                         unsigned long long* zcount, hipStream_t stream);
+hipError_t launch_rays_from(const LaunchScene& s, long long n, const float* origins,
+                            const float* dirs, int maxrec, uint8_t* rgb8, float* rgb, void* hits,
+                            bool frame, unsigned long long* zcount, hipStream_t stream);
+
 // ------------------- defined in rc_kernels.hip: the renderer, the parity pipeline, row shards --
 // cuda_sem: RC_MODE_CUDA (the CUDA port's arithmetic, rc_cudasem.hpp) instead of fast mode
 hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_step, int nrows,

@@ -245,6 +245,7 @@ struct GbufFrame {
 // *_device entries the caller's memory.  Spans: [0] start, [1] end of the one kernel.
 struct ViewFrame {
   DevBuf dirs, rgb8, rgb, hits;   // rc_trace_rays' arrays
+  DevBuf origins;                 // rc_trace_rays_from's second input
 };
 
 struct DevCtx {

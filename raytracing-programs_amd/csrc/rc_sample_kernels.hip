@@ -35,6 +35,11 @@
 //                 rays that are not the pinhole grid's (fast and cuda modes): k_window through a
 //                 view matrix, and a batch of the caller's own directions, one lane each, with
 //                 the colour before quantisation, its bytes and the primary hit's record.
+//   k_camera / k_rays_from
+//                 the same two with an origin (fast mode): every ray of a frame from one eye,
+//                 and a batch with an origin per ray.
+#include <cstring>
+
 #include "rc_cudasem.hpp"
 #include "rc_pixel.hpp"
 
@@ -1673,6 +1678,156 @@ hipError_t launch_rays(const LaunchScene& s, long long n, const float* dirs, int
   if (cuda_sem) go(k_rays<true, false>);
   else if (frame && hits) go(k_rays<false, true>);
   else go(k_rays<false, false>);
+  return hipGetLastError();
+}
+
+// ------------------- a free camera and rays with origins (fast) --
+// rc_render_camera*, rc_trace_rays_from* (include/raycast_hip.h, rc_camera): k_view and k_rays
+// with an origin.  No new arithmetic: shoot_from (rc_device.hpp) is shoot<kModeFast> with the
+// general nearest and hit_frame at the origin given.
+//
+// RC_CAMERA_TABLE 1: k_camera reads the eye's origin-only shape terms from a table in LDS
+// (EyeShape, nearest_eye), built by every workgroup for itself; 0, the default: it calls the
+// general nearest with O = eye.  Equal bytes either way (`make camera-variants` builds both;
+// scripts/camera_ab.py checks each against k_view's and k_rays_from's bytes and measures them).
+// Measured (profiles/camera_ab_quadric.txt): the table is 0.999-1.013 of
+// the general form, inside the spreads of the repeats.  The terms it saves are a few scalar-fed
+// operations a shape beside the f64 work of every test, and reading them back costs LDS loads
+// in their place.  So the general form ships, and the table stays behind the switch.
+#ifndef RC_CAMERA_TABLE
+#define RC_CAMERA_TABLE 0
+#endif
+
+struct Eye {
+  float x, y, z;
+};
+
+// k_camera: k_view (its grid, lane layout, bounds test, reduction and stores) in fast mode with
+// the primary ray leaving the eye.  With RC_CAMERA_TABLE the table is the workgroup's own LDS,
+// filled by one thread per shape in front of stage_scene's barrier: nothing is shared between two
+// frames in flight.  A scene too large to stage (stage_fits) has no table either way and takes the
+// general nearest.
+template <bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_camera(
+    Scene sc, Cam cam, View v, Eye e, int W, int H, int ls, int ox, int oy, int maxrec,
+    uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount) {
+  constexpr bool kTable = kStage && RC_CAMERA_TABLE;
+  if (!RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  const V3 eye = v3(e.x, e.y, e.z);
+  __shared__ StageBuf<kStage> stage;
+  __shared__ EyeShape eyes[kTable ? kStageShapes : 1];
+  if constexpr (kTable)
+    if ((int)threadIdx.x < sc.n) eyes[threadIdx.x] = eye_shape(sc.shapes[threadIdx.x], eye, quad_x0(sc));
+  stage_scene<kStage>(sc, stage);   // its barrier publishes the table too
+  int bx, by;
+  xcd_tile<0>(bx, by);
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const unsigned sub = lane & ((1u << (2 * ls)) - 1u);
+  const unsigned grp = lane >> (2 * ls);
+  const int lgw = 3 - ls;
+  const unsigned xs = (unsigned)bx * kTileW + (wave % (kTileW / 8)) * 8u +
+                      ((grp & ((1u << lgw) - 1u)) << ls) + (sub & ((1u << ls) - 1u));
+  const unsigned rs = (unsigned)by * kTileH + (wave / (kTileW / 8)) * 8u + ((grp >> lgw) << ls) +
+                      (sub >> ls);
+  const bool inside = (xs >> ls) < (unsigned)W && (rs >> ls) < (unsigned)H;
+  unsigned rg = 0u, b = 0u;
+  if (inside) {
+    int zero = 0;
+    const V3 d = view_dir<false>(cam, v, ox + (int)xs, oy + (int)rs, zero);
+    float t0;
+    int i0;
+    if constexpr (kTable) i0 = nearest_eye(sc, eye, d, eyes, t0);
+    else i0 = nearest(sc, eye, d, -1, t0);
+    const V3 c = shoot_from(sc, eye, d, i0, t0, maxrec, zero);
+    rg = (unsigned)quant(c.x) | ((unsigned)quant(c.y) << 16);
+    b = quant(c.z);
+    flush_events(zero, zcount);
+  }
+  sample_reduce(rg, b, 2 * ls);
+  if (inside && sub == 0u) {   // the group's first lane
+    uint8_t* q = out + ((size_t)(rs >> ls) * W + (xs >> ls)) * 3;
+    if (ls == 0) {
+      q[0] = (uint8_t)(rg & 0xffffu);
+      q[1] = (uint8_t)(rg >> 16);
+      q[2] = (uint8_t)b;
+    } else {
+      sample_store(q, rg, b, 2 * ls);
+    }
+  }
+}
+
+// k_rays_from: k_rays in fast mode with a second 12-byte-stride load, the ray's origin.  The
+// record is nearest(O, d, skip = -1) and its frame at O; the colour is shoot_from's.  Origins are
+// device data and are not looked at: a non-finite one fails every shape test, as in the oracle.
+template <bool kFrame>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_rays_from(
+    Scene sc, unsigned n, const float* __restrict__ origins, const float* __restrict__ dirs,
+    int maxrec, RayOut o, unsigned long long* __restrict__ zcount) {
+  if (!RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;
+  const unsigned k = blockIdx.x * (unsigned)kBlock + threadIdx.x;
+  if (k >= n) return;
+  const float* p = dirs + 3 * (size_t)k;
+  const float* q0 = origins + 3 * (size_t)k;
+  const V3 d = v3(p[0], p[1], p[2]);
+  const V3 O = v3(q0[0], q0[1], q0[2]);
+  int zero = 0, zrec = 0;   // zrec: the record's frame alone (shoot_from counts its own)
+  float t;
+  const int id = nearest(sc, O, d, -1, t);
+  if (o.hits) {
+    V3 P = v3(0.0f, 0.0f, 0.0f), N = P;
+    if constexpr (kFrame)
+      if (id >= 0) hit_frame(sc, id, O, d, t, P, N, zrec);
+    o.hits[2 * (size_t)k] = make_float4(__int_as_float(id), id < 0 ? 0.0f : t, P.x, P.y);
+    o.hits[2 * (size_t)k + 1] = make_float4(P.z, N.x, N.y, N.z);
+  }
+  if (!o.rgb && !o.rgb8) zero = zrec;
+  if (o.rgb || o.rgb8) {
+    const V3 c = shoot_from(sc, O, d, id, t, maxrec, zero);
+    if (o.rgb) {
+      float* q = o.rgb + 3 * (size_t)k;
+      q[0] = c.x, q[1] = c.y, q[2] = c.z;
+    }
+    if (o.rgb8) store_rgb(o.rgb8 + 3 * (size_t)k, c);
+  }
+  flush_events(zero, zcount);
+}
+
+hipError_t launch_camera(const LaunchScene& s, const float eye[3], const View& v, const Window& w,
+                         int W, int H, int ssaa, int maxrec, uint8_t* out,
+                         unsigned long long* zcount, hipStream_t stream) {
+  uint32_t bits[3];
+  std::memcpy(bits, eye, sizeof bits);
+  if ((bits[0] | bits[1] | bits[2]) == 0u)   // the eye at +0: a view (k_view's primary forms)
+    return launch_view(s, v, w, W, H, ssaa, maxrec, out, zcount, stream, false);
+  if (!window_supported(w, W, H, ssaa)) return hipErrorInvalidValue;
+  const int ls = ssaa == 1 ? 0 : ssaa_log2(ssaa);
+  dim3 grid((unsigned)(((unsigned long long)W * ssaa + kTileW - 1) / kTileW),
+            (unsigned)(((unsigned long long)H * ssaa + kTileH - 1) / kTileH));
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, w.full_w * ssaa, w.full_h * ssaa);   // of the s*full_w x s*full_h image
+  const Eye e{eye[0], eye[1], eye[2]};
+  dispatch(stage_fits(s), [&](auto st) {
+    hipLaunchKernelGGL((k_camera<st.value>), grid, dim3(kBlock), 0, stream, sc, cam, v, e, W, H, ls,
+                       w.x0 * ssaa, w.y0 * ssaa, maxrec, out, zcount);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_rays_from(const LaunchScene& s, long long n, const float* origins,
+                            const float* dirs, int maxrec, uint8_t* rgb8, float* rgb, void* hits,
+                            bool frame, unsigned long long* zcount, hipStream_t stream) {
+  if (n < 1 || n > (1ll << 24) || !origins || !dirs || (!rgb8 && !rgb && !hits) ||
+      ((uintptr_t)hits & 15u))
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+  const Scene sc = make_scene(s);
+  const RayOut o{rgb8, rgb, (float4*)hits};
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, stream, sc, (unsigned)n, origins, dirs,
+                       maxrec, o, zcount);
+  };
+  if (frame && hits) go(k_rays_from<true>);
+  else go(k_rays_from<false>);
   return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // rc_sampling.hip — the sampling features of libraycast_hip.so's C-ABI (include/raycast_hip.h):
 // rate maps, reconstruction filters, sparse sample patterns, progressive accumulation, windows of a
-// virtual image, the primary-visibility G-buffer and rotated views and ray batches, with adaptive
+// virtual image, the primary-visibility G-buffer, rotated views and ray batches and the free camera
+// and rays with origins, with adaptive
 // supersampling's getters.  Host code only: the kernels are
 // rc_sample_kernels.hip's and rc_filter.hip's (the one-ray image is rc_kernels.hip's k_render), the device context and the frame scaffold (enter,
 // ws_frame, claim_event_set, finish_device, finish_host) are rc_api.hip's, through rc_runtime.h.
@@ -220,6 +221,47 @@ static int rays_refused(const char* who, const rc_options* opt, int64_t n, const
     if (out->frame && out->hits && opt->mode == RC_MODE_CUDA)
       return say("Error: %s: the hit point and the normal (frame = 1) are for fast mode: no "
                  "reference pins the CUDA port's hit frame; ask for id and t\n", who);
+    if (n < 1 || n > ((int64_t)1 << 24))
+      return say("Error: %s: n %lld is not 1 .. 2^24 rays\n", who, (long long)n);
+    return 0;
+  }, no_check);
+}
+
+// The camera family is the view family in fast mode alone: the tables' mode clause refuses parity,
+// and cuda mode is the first thing the family's own check refuses.
+static int camera_mode_refused(const char* who, const rc_options* opt) {
+  if (opt->mode == RC_MODE_FAST) return 0;
+  return say("Error: %s: rays with an origin are for fast mode: the oracle exports no hit frame "
+             "for the CUDA port, so no reference pins a colour there\n", who);
+}
+
+static const Refusal kCameraRefusal = {
+    "Error: %s: ssaa %d carries an adaptive threshold: a camera frame is shot at a plain factor\n",
+    0, nullptr,
+    "Error: %s: cameras are for fast mode: a parity image is defined by the scan-order carry of "
+    "the reference's own camera\n",
+    "Error: %s: num_gpus %d: the row shards take no camera\n",
+    nullptr};   // rc_window_check tests the sizes
+
+static int camera_refused(const char* who, const rc_options* opt, int W, int H,
+                          const rc_camera* cam, const rc_window* vw) {
+  return refused(kCameraRefusal, who, opt, W, H, 0, 0, false, [&](int ss) {
+    return camera_mode_refused(who, opt) || rc_camera_check(cam) ||
+           rc_window_check(vw, W, H, ss);
+  }, no_check);
+}
+
+static const Refusal kRaysFromRefusal = {
+    "Error: %s: ssaa %d carries an adaptive threshold: a ray is one sample, leave ssaa at 0 or 1\n",
+    1, "Error: %s: ssaa %d in the options: a ray is one sample, leave ssaa at 0 or 1\n",
+    "Error: %s: rays with an origin are for fast mode: a parity colour is defined by the "
+    "scan-order carry of the reference's own camera\n",
+    "Error: %s: num_gpus %d: the row shards trace no ray batch\n",
+    nullptr};
+
+static int rays_from_refused(const char* who, const rc_options* opt, int64_t n) {
+  return refused(kRaysFromRefusal, who, opt, 0, 0, 0, 0, false, [&](int) {
+    if (camera_mode_refused(who, opt)) return -1;
     if (n < 1 || n > ((int64_t)1 << 24))
       return say("Error: %s: n %lld is not 1 .. 2^24 rays\n", who, (long long)n);
     return 0;
@@ -620,6 +662,15 @@ int rc_view_check(const rc_view* v) {
   return 0;
 }
 
+int rc_camera_check(const rc_camera* cam) {
+  const char* who = "rc_camera_check";
+  if (!cam) return say("Error: %s: a null camera\n", who);
+  for (int k = 0; k < 3; ++k)
+    if (!__builtin_isfinite(cam->eye[k]))
+      return say("Error: %s: eye[%d] is not finite\n", who, k);
+  return rc_view_check(&cam->view);
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ enqueue bodies --
@@ -954,6 +1005,32 @@ static int enqueue_view(DevCtx& c, const rc_scene* s, const rc_view* view, const
       HIP_TRY(rc::launch_view(f.ls, v, rc::Window{vw->full_w, vw->full_h, vw->x0, vw->y0}, W, H,
                               ssaa_factor(opt, "rc_render_view"), opt->max_recursion, d_out, f.zc,
                               stream, cuda));
+    }
+    return f.end();
+  });
+}
+
+// enqueue_view for the camera family (the caller has passed camera_refused or
+// rays_from_refused): one launch of k_camera for the window's pixels (rays null), or of
+// k_rays_from for the n rays whose origins are `origins`.  The view family's span owner: a camera
+// frame is a view frame to rc_view_phase_ms.
+static int enqueue_camera(DevCtx& c, const rc_scene* s, const rc_camera* cam, const rc_window* vw,
+                          int W, int H, const rc_options* opt, uint8_t* d_out,
+                          const RayBatch* rays, const float* origins, hipStream_t stream) {
+  return ws_frame(c, stream, [] { return 0; }, [&]() -> int {
+    SampleFrame f{c, stream, kSpanView};
+    if (f.begin(s, nullptr, 0)) return -1;
+    if (rays) {
+      HIP_TRY(rc::launch_rays_from(f.ls, rays->n, origins, rays->dirs, opt->max_recursion,
+                                   rays->out.rgb8, rays->out.rgb, rays->out.hits,
+                                   rays->out.frame != 0, f.zc, stream));
+    } else {
+      rc::View v;
+      std::memcpy(v.m, cam->view.m, sizeof v.m);
+      HIP_TRY(rc::launch_camera(f.ls, cam->eye, v,
+                                rc::Window{vw->full_w, vw->full_h, vw->x0, vw->y0}, W, H,
+                                ssaa_factor(opt, "rc_render_camera"), opt->max_recursion, d_out,
+                                f.zc, stream));
     }
     return f.end();
   });
@@ -1407,6 +1484,88 @@ int rc_view_phase_ms(double ms[1]) {
   if (!ms || enter(kCurrentDevice, false, e)) return -1;
   hipEvent_t* ev = e.c->span_ev[kSpanView];
   return ev ? read_spans({ev[0], ev[1]}, ms) : -1;
+}
+
+// --------------------------------------------- a free camera and rays with origins --
+int rc_render_camera_device(const rc_scene* s, const rc_camera* cam, const rc_window* win, int W,
+                            int H, const rc_options* opt, uint8_t* d_out, void* stream,
+                            rc_timing* timing) {
+  const char* who = "rc_render_camera_device";
+  if (!s || !cam || !opt || !d_out) return say("Error: %s: a null pointer\n", who);
+  const rc_window vw = win ? *win : rc_window{W, H, 0, 0};
+  if (camera_refused(who, opt, W, H, cam, &vw)) return -1;
+  return device_entry(opt, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_camera(c, s, cam, &vw, W, H, opt, d_out, nullptr, nullptr, st);
+  });
+}
+
+int rc_render_camera(const rc_scene* s, const rc_camera* cam, const rc_window* win, int W, int H,
+                     const rc_options* opt, uint8_t* pixmap, rc_timing* timing) {
+  const char* who = "rc_render_camera";
+  if (!s || !cam || !opt || !pixmap) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  const rc_window vw = win ? *win : rc_window{W, H, 0, 0};
+  if (camera_refused(who, opt, W, H, cam, &vw)) return -1;
+  return host_entry(opt, W, H, pixmap, timing, t0, kImageOom, false, nothing_more, [&](DevCtx& c) {
+    return enqueue_camera(c, s, cam, &vw, W, H, opt, (uint8_t*)c.out.p, nullptr, nullptr,
+                          c.stream);
+  });
+}
+
+int rc_trace_rays_from_device(const rc_scene* s, const rc_options* opt, int64_t n,
+                              const float* d_origins, const float* d_dirs,
+                              const rc_ray_out* d_out, void* stream) {
+  const char* who = "rc_trace_rays_from_device";
+  if (!s || !opt || !d_origins || !d_dirs || !d_out) return say("Error: %s: a null pointer\n", who);
+  if (rays_out_refused(who, d_out)) return -1;
+  if ((uintptr_t)d_out->hits & 15u)
+    return say("Error: %s: the records are not 16-byte aligned\n", who);
+  if (rays_from_refused(who, opt, n)) return -1;
+  const RayBatch rays{n, d_dirs, *d_out};
+  return device_entry(opt, stream, nullptr, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_camera(c, s, nullptr, nullptr, 0, 0, opt, nullptr, &rays, d_origins, st);
+  });
+}
+
+int rc_trace_rays_from(const rc_scene* s, const rc_options* opt, int64_t n, const float* origins,
+                       const float* dirs, const rc_ray_out* out) {
+  const char* who = "rc_trace_rays_from";
+  if (!s || !opt || !origins || !dirs || !out) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  if (rays_out_refused(who, out)) return -1;
+  if (rays_from_refused(who, opt, n)) return -1;
+  const size_t n3 = (size_t)n * 3, nhits = (size_t)n * sizeof(rc_hit);
+  return host_entry(
+      opt, 0, 0, nullptr, nullptr, t0, "Error: out of device memory for the ray batch\n", false,
+      [&](DevCtx& c) {   // device copies of the rays and of the outputs asked for
+        ViewFrame& v = c.view;
+        return v.origins.ensure(n3 * sizeof(float)) || v.dirs.ensure(n3 * sizeof(float)) ||
+               (out->rgb8 && v.rgb8.ensure(n3)) ||
+               (out->rgb && v.rgb.ensure(n3 * sizeof(float))) ||
+               (out->hits && v.hits.ensure(nhits));
+      },
+      [&](DevCtx& c) -> int {
+        const ViewFrame& v = c.view;
+        const RayBatch rays{n, (const float*)v.dirs.p,
+                            rc_ray_out{out->rgb8 ? (uint8_t*)v.rgb8.p : nullptr,
+                                       out->rgb ? (float*)v.rgb.p : nullptr,
+                                       out->hits ? (rc_hit*)v.hits.p : nullptr, out->frame}};
+        HIP_TRY(hipMemcpyAsync(v.origins.p, origins, n3 * sizeof(float), hipMemcpyHostToDevice,
+                               c.stream));
+        HIP_TRY(hipMemcpyAsync(v.dirs.p, dirs, n3 * sizeof(float), hipMemcpyHostToDevice,
+                               c.stream));
+        if (enqueue_camera(c, s, nullptr, nullptr, 0, 0, opt, nullptr, &rays,
+                           (const float*)v.origins.p, c.stream))
+          return -1;
+        // behind the kernel on c.stream, in front of finish_host's wait
+        auto back = [&](void* host, const void* dev, size_t bytes) -> int {
+          if (host) HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c.stream));
+          return 0;
+        };
+        return back(out->rgb8, rays.out.rgb8, n3) ||
+               back(out->rgb, rays.out.rgb, n3 * sizeof(float)) ||
+               back(out->hits, rays.out.hits, nhits);
+      });
 }
 
 // No frame of the workspace: the resolve of an accumulator alone, on the current device.
