@@ -893,7 +893,8 @@ int rc_view_phase_ms(double ms[1]);
  *     pin a colour there); what rc_camera_check refuses; what rc_window_check refuses.
  *     rc_trace_rays_from*: a null scene, options, origins, dirs or out; then what rc_trace_rays
  *     refuses, with cuda mode refused after num_gpus.
- * Out of scope: cuda and parity mode; accumulation and scrolling with a camera; a G-buffer plane
+ * Out of scope: cuda and parity mode; scrolling with a camera (accumulation with one is
+ *     rc_accum_pass_camera_device, below); a G-buffer plane
  *     entry for cameras (rc_trace_rays_from with hits alone is the pick); any-hit queries with a
  *     distance bound; multi-GPU. */
 typedef struct rc_camera { float eye[3]; rc_view view; } rc_camera;
@@ -911,6 +912,62 @@ int rc_trace_rays_from(const rc_scene *scene, const rc_options *opt, int64_t n,
 int rc_trace_rays_from_device(const rc_scene *scene, const rc_options *opt, int64_t n,
                               const float *d_origins, const float *d_dirs,
                               const rc_ray_out *d_out, void *stream);
+
+/* Accumulation through a free camera: progressive anti-aliasing of a camera frame, depth of field
+ * and camera motion blur (rc_accum_pass_camera_device, rc_render_camera_accum; fast mode).  The
+ * accumulation family above shoots the reference camera's rays from the origin; these two entries
+ * take the samples through rc_camera values instead.  A pass takes one camera for all its samples
+ * (a still camera refines) or one camera for each sample (16 lens points or 16 instants cost one
+ * launch and one read-modify-write of the record).  The state is the caller's rc_accum_px array as
+ * before: nothing in a record says which camera a sample came through, so cameras may change
+ * between passes and the passes of the other accumulation entries may be mixed in.
+ * Contract.  rc_accum_pass_window_device's contract holds word for word, with one substitution:
+ *     the active set, the contrast, saturation, res, reset, first and count (1 <= count <= 16),
+ *     the stats and the spans are unchanged.  Let C_g(c) be the image rc_render_camera defines for
+ *     camera c at g*full_w x g*full_h with ssaa = 1 (the view contract's directions, every ray
+ *     leaving c.eye, the fast-mode bounce loop of the camera contract, the byte rounding).  Sample
+ *     first + j of window pixel (x, y), 0 <= j < count, is
+ *         C_g(cams[ncams == 1 ? 0 : j])[g*(y0 + y) + y[first + j]][g*(x0 + x) + x[first + j]].
+ *     ncams is 1 or count; camera j belongs to the j-th sample of the pass, whatever `first` is.
+ *     The cameras are host memory and are copied at the call.  win = NULL is the whole W x H image.
+ *     A camera with eye = +0 and the identity view gives rc_accum_pass_window_device's records and
+ *     bytes exactly, and with win = NULL rc_accum_pass_device's.  Window independence holds per
+ *     camera, as in the window contract.
+ * rc_render_camera_accum: the host-pixmap form, synchronous on opt->device, the accumulator owned
+ *     by the library.  The whole sequence goes to every pixel: a reset pass, in chunks of at most
+ *     16.  ncams is 1 or seq->nsamples, and sample k goes through cams[ncams == 1 ? 0 : k].  With
+ *     hier<g> and one camera the image is rc_render_camera's at ssaa = g.
+ * The stats, the spans and rc_timing are the accumulation family's (rc_accum_stats_get,
+ *     rc_accum_phase_ms), as rc_accum_pass_window_device documents them.
+ * On the device: the accumulation kernels' layout (one lane a pixel, the samples one after the
+ *     other, one 8-byte load and one 8-byte store of the record) with each sample shot as
+ *     rc_render_camera shoots a subsample.  The cameras are a kernel argument read with the uniform
+ *     sample index: nothing derived from a camera lives in device memory, and two passes in flight
+ *     share nothing.  t > 0 is the edge list and the list kernel on one stream with no host wait.
+ * Refused, each with one message and -1, from the arguments alone (before any device work), in
+ *     this order:
+ *       1. a null scene, cams, options, sequence, accumulator or image (win may be null);
+ *       2. (pass) an accumulator that is not 8-byte aligned;
+ *       3. what rc_accum_pass_window_device refuses, in its order, on W and H: a factor above 1 or
+ *          a threshold in opt->ssaa; parity mode; num_gpus > 1; then cuda mode (as in the camera
+ *          family: the oracle exports no hit frame for the CUDA port); a sequence that fails
+ *          rc_sample_seq_check; a threshold outside 0..255; W or H below 1 or above 2^28 / g; with
+ *          t > 0, W * H >= 2^32; more than 65535 rows of tiles; what rc_window_check refuses at g;
+ *          (pass) first or count out of range; reset with t > 0;
+ *       4. ncams outside {1, count} (the host form: {1, nsamples});
+ *       5. the first camera that rc_camera_check would refuse, named by its index.
+ * Out of scope: scrolling with a camera (rc_accum_scroll_device moves records of the reference
+ *     camera's pan; a camera's turn is not a pan); cuda and parity mode; a threshold in the host
+ *     form (follow with rc_accum_pass_camera_device, t > 0); a RAYCAST_* variable; multi-GPU. */
+int rc_accum_pass_camera_device(const rc_scene *scene, const rc_camera *cams, int ncams,
+                                const rc_window *win /* NULL: the whole image */,
+                                int width, int height, const rc_options *opt,
+                                const rc_sample_seq *seq, int first, int count, int threshold,
+                                int reset, rc_accum_px *d_acc, uint8_t *d_out,
+                                void *stream, rc_timing *timing);
+int rc_render_camera_accum(const rc_scene *scene, const rc_camera *cams, int ncams,
+                           const rc_window *win, int width, int height, const rc_options *opt,
+                           const rc_sample_seq *seq, uint8_t *pixmap, rc_timing *timing);
 
 /* Frames in flight(an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out

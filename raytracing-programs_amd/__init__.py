@@ -300,7 +300,8 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_render_view", "rc_render_view_device", "rc_trace_rays",
                "rc_trace_rays_device", "rc_view_phase_ms", "rc_camera_check",
                "rc_render_camera", "rc_render_camera_device", "rc_trace_rays_from",
-               "rc_trace_rays_from_device"]
+               "rc_trace_rays_from_device", "rc_accum_pass_camera_device",
+               "rc_render_camera_accum"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -537,6 +538,19 @@ def _hip_lib_locked():
     lib.rc_trace_rays_from_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcOptions),
                                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.POINTER(RcRayOut), ctypes.c_void_p]
+    lib.rc_accum_pass_camera_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcCamera),
+                                                ctypes.c_int, ctypes.POINTER(RcWindow),
+                                                ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(RcOptions),
+                                                ctypes.POINTER(RcSampleSeq), ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.POINTER(RcTiming)]
+    lib.rc_render_camera_accum.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcCamera),
+                                           ctypes.c_int, ctypes.POINTER(RcWindow), ctypes.c_int,
+                                           ctypes.c_int, ctypes.POINTER(RcOptions),
+                                           ctypes.POINTER(RcSampleSeq), ctypes.c_void_p,
+                                           ctypes.POINTER(RcTiming)]
     _hip = lib
     return lib
 
@@ -1813,6 +1827,117 @@ def render_camera_device(scene, eye, m, width, height, d_out_ptr, window=None, s
     with _timed(timing) as (_, t):
         _call("rc_render_camera_device", scene.packed(), ctypes.byref(cam), win, width, height,
               ctypes.byref(opt), ctypes.c_void_p(d_out_ptr), _stream(stream_ptr), t)
+
+
+def accum_add(acc, out, planes, t=0, reset=False):
+    """One accumulation pass in numpy for per-sample planes: planes[j] is the [H, W, 3] uint8 image
+    sample j of the pass is taken from (for a pass through cameras, the lattice point's slice of
+    camera j's g*H x g*W image), count = len(planes) in 1..16.  The contract is accum_step's: the
+    active set is every pixel (t = 0, or reset, which also zeroes the accumulator first) or
+    edge_mask(out, t); an active pixel whose n would pass 256 is saturated and keeps everything.
+    Returns (acc', out', active, saturated); the arguments are not written.
+    accum_step(acc, out, big, g, points, ...) is accum_add on the planes big[y::g, x::g]."""
+    planes, t = np.asarray(planes), int(t)
+    if planes.dtype != np.uint8 or planes.ndim != 4 or planes.shape[3] != 3:
+        raise ValueError(f"accum_add: planes are [count, H, W, 3] uint8, got {planes.dtype} "
+                         f"{planes.shape}")
+    count, h, w = planes.shape[:3]
+    if not 1 <= count <= ACCUM_MAX_COUNT:
+        raise ValueError(f"accum_add: {count} samples, a pass takes 1..{ACCUM_MAX_COUNT}")
+    if not 0 <= t <= 255 or (reset and t):
+        raise ValueError(f"accum_add: threshold {t} (0..255, and 0 with reset)")
+    acc, out = _accum_state(acc), np.asarray(out)
+    if acc.shape[:2] != (h, w) or out.shape != (h, w, 3) or out.dtype != np.uint8:
+        raise ValueError(f"accum_add: acc {acc.shape} and out {out.dtype} {out.shape} do not fit "
+                         f"a {w} x {h} image")
+    state = np.zeros((h, w, 4), dtype=np.uint32) if reset else acc.astype(np.uint32)
+    mask = edge_mask(out, t) if t > 0 else np.ones((h, w), dtype=bool)
+    saturated = mask & (state[:, :, 3] + count > ACCUM_MAX_N)
+    take = mask & ~saturated
+    state[:, :, :3] += planes.astype(np.uint32).sum(axis=0) * take[:, :, None]
+    state[:, :, 3] += (count * take).astype(np.uint32)
+    new_acc = np.where(take[:, :, None], state, acc).astype(np.uint16)
+    new_out = np.where(take[:, :, None], accum_resolve(new_acc), out)
+    return new_acc, new_out, int(mask.sum()), int(saturated.sum())
+
+
+def thin_lens(eye, m, focus, lens_points):
+    """The cameras of a thin lens around the pinhole camera (eye, m): one (eye, m) pair for each
+    lens point (lx, ly), in camera units on the plane z = 0 of the camera's frame.  With M the
+    view matrix and f = focus > 0 the distance of the focal plane, the eye is eye + M (lx, ly, 0)
+    and the view M [[1, 0, lx/f], [0, 1, ly/f], [0, 0, 1]]: the primary vector's z is -1, so the
+    ray's vector is proportional to f M p - M (lx, ly, 0) and the ray through any lens point passes
+    through the pinhole ray's point on the plane at depth f.  Computed in float64 and rounded once
+    to float32; lens point (0, 0) is the camera as given, bit for bit.  The helper only makes
+    cameras: the device contract is exact for whatever cameras it is given."""
+    e, m = camera(eye, m)
+    f = float(focus)
+    if not (f > 0.0 and np.isfinite(f)):
+        raise ValueError(f"thin_lens: focus {focus} is not a finite distance above 0")
+    pts = np.asarray(lens_points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 2 or not len(pts):
+        raise ValueError(f"thin_lens: lens points are [n, 2], got shape {pts.shape}")
+    e64, m64 = e.astype(np.float64), m.astype(np.float64)
+    cams = []
+    for lx, ly in pts:
+        if lx == 0.0 and ly == 0.0:
+            cams.append((e.copy(), m.copy()))
+            continue
+        shear = np.array([[1.0, 0.0, lx / f], [0.0, 1.0, ly / f], [0.0, 0.0, 1.0]])
+        cams.append(((e64 + m64 @ np.array([lx, ly, 0.0])).astype(np.float32),
+                     (m64 @ shear).astype(np.float32)))
+    return cams
+
+
+def _rc_cameras(cams, per, what):
+    """The RcCamera array of `cams`: one (eye, m) pair, or a sequence of `per` of them."""
+    try:
+        single = len(cams) == 2 and np.ndim(cams[0][0]) == 0
+    except (TypeError, IndexError):
+        raise ValueError(f"{what}: cams is one (eye, m) pair or a list of them") from None
+    pairs = [cams] if single else list(cams)
+    if len(pairs) not in (1, int(per)):
+        raise ValueError(f"{what}: {len(pairs)} cameras, it takes 1 or {int(per)}")
+    arr = (RcCamera * len(pairs))()
+    for k, pair in enumerate(pairs):
+        if len(pair) != 2:
+            raise ValueError(f"{what}: camera {k} is not an (eye, m) pair")
+        arr[k] = _rc_camera(pair[0], pair[1])
+    return arr
+
+
+def accum_pass_camera_device(scene, cams, window, width, height, seq, first, count, d_acc_ptr,
+                             d_out_ptr, threshold=0, reset=False, stream_ptr=None, depth=6,
+                             mode="fast", timing=None):
+    """rc_accum_pass_camera_device: accum_pass_window_device with the samples taken through
+    cameras: `cams` is one (eye, m) pair for the whole pass or a list of `count` of them, sample
+    first + j through camera j (accum_add on the lattice points' slices of the cameras' g*full_w x
+    g*full_h images).  window = None: the whole width x height image.  Fast mode only."""
+    arr = _rc_cameras(cams, count, "accum_pass_camera_device")
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    s = _rc_sample_seq(seq)
+    opt = options(depth, mode)
+    with _timed(timing) as (_, t):
+        _call("rc_accum_pass_camera_device", scene.packed(), arr, len(arr), win, width, height,
+              ctypes.byref(opt), ctypes.byref(s), int(first), int(count), int(threshold),
+              1 if reset else 0, ctypes.c_void_p(d_acc_ptr), ctypes.c_void_p(d_out_ptr),
+              _stream(stream_ptr), t)
+
+
+def render_camera_accum(scene, cams, width, height, seq, window=None, depth=6, device=0,
+                        mode="fast", timing=None, out=None):
+    """rc_render_camera_accum: the whole of `seq` for every pixel through `cams`, one (eye, m) pair
+    or a list of one for each sample of the sequence; the mean image.  With hier<g> and one camera
+    that is render_camera's image at ssaa = g.  Fast mode only."""
+    s = _rc_sample_seq(seq)
+    arr = _rc_cameras(cams, s.nsamples, "render_camera_accum")
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    out = _pixmap(out, width, height)
+    opt = options(depth, mode, 1, device)
+    with _timed(timing) as (t, _):
+        _call("rc_render_camera_accum", scene.packed(), arr, len(arr), win, width, height,
+              ctypes.byref(opt), ctypes.byref(s), _host_ptr(out), ctypes.byref(t))
+    return out
 
 
 def trace_rays_from(scene, origins, dirs, outputs=("rgb8",), frame=False, depth=6, mode="fast",

@@ -323,6 +323,28 @@ hipError_t launch_rays_from(const LaunchScene& s, long long n, const float* orig
                             const float* dirs, int maxrec, uint8_t* rgb8, float* rgb, void* hits,
                             bool frame, unsigned long long* zcount, hipStream_t stream);
 
+// Accumulation through a free camera (rc_accum_pass_camera_device, rc_render_camera_accum; fast
+// mode only): launch_accum_window and launch_accum_list_window with sample j of the pass shot as
+// launch_camera shoots a subsample, through camera j of `cams`.  The cameras travel by value as a
+// kernel argument (768 bytes) and are read with the pass's uniform sample index, so a caller with
+// one camera for the whole pass fills every slot it uses with that camera.  Slots at and past
+// `count` are not read.  An eye of three +0 is not dispatched anywhere else: the general nearest
+// at +0 gives the origin forms' bits.  The guards are the window launchers'.
+struct CamSet {
+  float eye[16][3];
+  View view[16];
+};
+static_assert(sizeof(CamSet) == 768, "16 eyes and 16 views, one kernel argument");
+hipError_t launch_accum_cam(const LaunchScene& s, const CamSet& cams, const Window& w, int W,
+                            int H, int g, int count, const uint8_t* px, const uint8_t* py,
+                            bool reset, int maxrec, void* acc, uint8_t* out,
+                            unsigned long long* zcount, unsigned* sat, hipStream_t stream);
+hipError_t launch_accum_list_cam(const LaunchScene& s, const CamSet& cams, const Window& w, int W,
+                                 int H, int g, int count, const uint8_t* px, const uint8_t* py,
+                                 int maxrec, const uint32_t* list, const unsigned* nlist,
+                                 void* acc, uint8_t* out, unsigned long long* zcount,
+                                 unsigned* sat, int blocks, hipStream_t stream);
+
 // ------------------- defined in rc_kernels.hip: the renderer, the parity pipeline, row shards --
 // cuda_sem: RC_MODE_CUDA (the CUDA port's arithmetic, rc_cudasem.hpp) instead of fast mode
 hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_step, int nrows,

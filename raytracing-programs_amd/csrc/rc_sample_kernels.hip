@@ -38,6 +38,10 @@
 //   k_camera / k_rays_from
 //                 the same two with an origin (fast mode): every ray of a frame from one eye,
 //                 and a batch with an origin per ray.
+//   k_accum_cam / k_accum_list_cam
+//                 the accumulation passes through free cameras (fast mode): k_accum_win's and
+//                 k_accum_list_win's layout with sample j shot k_camera's way through camera j
+//                 of a kernel argument of up to 16 cameras.
 #include <cstring>
 
 #include "rc_cudasem.hpp"
@@ -1828,6 +1832,184 @@ hipError_t launch_rays_from(const LaunchScene& s, long long n, const float* orig
   };
   if (frame && hits) go(k_rays_from<true>);
   else go(k_rays_from<false>);
+  return hipGetLastError();
+}
+
+// ------------------- accumulation through a free camera (fast) --
+// rc_accum_pass_camera_device / rc_render_camera_accum (include/raycast_hip.h): accum_dense's and
+// accum_listed's bodies with sample k shot k_camera's way through camera k of the pass: view_dir
+// on the subsample's virtual coordinates, the general nearest from the eye, shoot_from and quant.
+// Bodies of their own beside the old ones, so that k_accum*, k_accum_*win and k_accum_exposed keep
+// their instructions.  No new arithmetic.
+//
+// The cameras are one kernel argument (CamSet, 768 bytes).  The sample loop is uniform, so k, the
+// lattice entry and the camera are scalar: camera k is read from the argument segment with scalar
+// loads at a scalar offset, never copied to scratch or chosen lane by lane.  A pass with one
+// camera has that camera in every slot (the host fills them), so the loop has no branch for it.
+// Nothing derived from a camera is stored anywhere: two passes in flight share nothing.
+// An eye of +0 takes the general nearest like any other (bit-equal to the origin forms).
+__device__ __forceinline__ void cam_sample_shoot(const Scene& sc, const Cam& cam,
+                                                 const CamSet& cams, int k, int xs, int ys,
+                                                 int maxrec,
+                                                 unsigned long long* __restrict__ zcount,
+                                                 unsigned& rg, unsigned& b) {
+  int zero = 0;
+  const V3 eye = v3(cams.eye[k][0], cams.eye[k][1], cams.eye[k][2]);
+  const V3 d = view_dir<false>(cam, cams.view[k], xs, ys, zero);
+  float t0;
+  const int i0 = nearest(sc, eye, d, -1, t0);
+  const V3 c = shoot_from(sc, eye, d, i0, t0, maxrec, zero);
+  rg = (unsigned)quant(c.x) | ((unsigned)quant(c.y) << 16);
+  b = quant(c.z);
+  flush_events(zero, zcount);
+}
+
+// k_accum_cam: accum_dense line for line (its grid, tiles, the record's n read alone before the
+// samples, one 8-byte load and one 8-byte store behind them, the image through the tile stores);
+// across a sample only the two packed sums and what accum_dense keeps stay live.
+template <bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_cam(
+    Scene sc, Cam cam, CamSet cams, int W, int H, int ox, int oy, int lg, int count, PatWords pat,
+    int reset, int maxrec, uint2* __restrict__ acc, uint8_t* __restrict__ out,
+    unsigned long long* __restrict__ zcount, unsigned* __restrict__ sat) {
+  if (!RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  __shared__ TileBytes tb;
+  tile_init(tb);
+  stage_scene<kStage>(sc, stage);
+  if (!kStage) __syncthreads();
+  int lx, ly;
+  tile_pixel(lx, ly);
+  int bx, by;
+  xcd_tile<0>(bx, by);
+  const int x0 = bx * kTileW, y0 = by * kTileH;
+  const int x = x0 + lx, y = y0 + ly;
+  bool saturated = false;
+  if (x < W && y < H) {
+    const size_t p = (size_t)y * W + x;
+    const unsigned had = reset ? 0u : (unsigned)((const uint16_t*)(acc + p))[3];
+    saturated = had + (unsigned)count > 256u;
+    if (!saturated) {
+      unsigned rg = 0u, b = 0u;
+      for (int k = 0; k < count; ++k) {   // uniform
+        unsigned srg, sb;
+        cam_sample_shoot(sc, cam, cams, k, ((ox + x) << lg) + pat_entry(pat.x, (unsigned)k),
+                         ((oy + y) << lg) + pat_entry(pat.y, (unsigned)k), maxrec, zcount, srg,
+                         sb);
+        rg += srg;
+        b += sb;
+      }
+      uint2 rec = make_uint2(0u, 0u);
+      if (!reset) rec = acc[p];
+      rec.x += rg;
+      rec.y += b + ((unsigned)count << 16);
+      acc[p] = rec;
+      uint8_t r8, g8, b8;
+      accum_resolve_px(rec, r8, g8, b8);
+      tile_put_rgb(tb, lx, ly, r8, g8, b8, out + p * 3);
+    } else if (RC_TILE_STAGE) {   // the staged tile's whole-row stores write this pixel too
+      const uint8_t* q = out + p * 3;
+      tile_put_rgb(tb, lx, ly, q[0], q[1], q[2], out + p * 3);
+    }
+  }
+  accum_count_saturated(saturated, sat);
+  if (!tile_last_wave(tb)) return;
+  const int nx = W - x0 < kTileW ? W - x0 : kTileW;
+  tile_write_rows<kTileW * 3 / 4>(tb.rgb, [&](int q) -> uint8_t* {
+    return y0 + q < H ? out + ((size_t)(y0 + q) * W + x0) * 3 : nullptr;
+  }, nx * 3);
+}
+
+// k_accum_list_cam: accum_listed line for line over k_aa_mark's list; the entry is read again
+// behind the samples, as there.
+template <bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_accum_list_cam(
+    Scene sc, Cam cam, CamSet cams, int W, int ox, int oy, int lg, int count, PatWords pat,
+    int maxrec, const uint32_t* __restrict__ list, const unsigned* __restrict__ nlist,
+    uint2* __restrict__ acc, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
+    unsigned* __restrict__ sat) {
+  if (!RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  __shared__ StageBuf<kStage> stage;
+  const unsigned n = *nlist;
+  if (n == 0u) return;   // uniform over the grid: an empty list costs its launch
+  stage_scene<kStage>(sc, stage);   // its barrier comes before the loop: every thread is here
+  const int lane = threadIdx.x & 63;
+  const unsigned wave =
+      __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
+  const unsigned step = gridDim.x * (kBlock / 64) * 64u;   // <= 4096 * 4 * 64
+  // 64-bit index: n + step may pass 2^32
+  for (unsigned long long first = (unsigned long long)wave * 64u; first < n; first += step) {
+    const unsigned long long e = first + (unsigned)lane;
+    bool saturated = false;
+    if (e < n) {
+      const unsigned p = list[e];
+      saturated = (unsigned)((const uint16_t*)(acc + p))[3] + (unsigned)count > 256u;
+      if (!saturated) {
+        const int xs = (int)((p % (unsigned)W + (unsigned)ox) << lg);
+        const int ys = (int)((p / (unsigned)W + (unsigned)oy) << lg);
+        unsigned rg = 0u, b = 0u;
+        for (int k = 0; k < count; ++k) {   // uniform
+          unsigned srg, sb;
+          cam_sample_shoot(sc, cam, cams, k, xs + pat_entry(pat.x, (unsigned)k),
+                           ys + pat_entry(pat.y, (unsigned)k), maxrec, zcount, srg, sb);
+          rg += srg;
+          b += sb;
+        }
+        unsigned l = (unsigned)lane;   // opaque: the entry is read again, as in accum_listed
+        asm volatile("" : "+v"(l));
+        const size_t q = list[first + l];
+        uint2 rec = acc[q];
+        rec.x += rg;
+        rec.y += b + ((unsigned)count << 16);
+        acc[q] = rec;
+        uint8_t r8, g8, b8;
+        accum_resolve_px(rec, r8, g8, b8);
+        uint8_t* o = out + q * 3;
+        o[0] = r8;
+        o[1] = g8;
+        o[2] = b8;
+      }
+    }
+    accum_count_saturated(saturated, sat);
+  }
+}
+
+hipError_t launch_accum_cam(const LaunchScene& s, const CamSet& cams, const Window& w, int W,
+                            int H, int g, int count, const uint8_t* px, const uint8_t* py,
+                            bool reset, int maxrec, void* acc, uint8_t* out,
+                            unsigned long long* zcount, unsigned* sat, hipStream_t stream) {
+  if (!accum_supported(W, H, g, false) || !window_inside(w, W, H, g) || count < 1 || count > 16)
+    return hipErrorInvalidValue;
+  const int lg = pattern_log2(g, 1, 3);
+  dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, w.full_w * g, w.full_h * g);   // of the g*full_w x g*full_h image
+  const PatWords pat = pattern_words(count, px, py);
+  dispatch(stage_fits(s), [&](auto st) {
+    hipLaunchKernelGGL((k_accum_cam<st.value>), grid, dim3(kBlock), 0, stream, sc, cam, cams, W, H,
+                       w.x0, w.y0, lg, count, pat, reset ? 1 : 0, maxrec, (uint2*)acc, out, zcount,
+                       sat);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_accum_list_cam(const LaunchScene& s, const CamSet& cams, const Window& w, int W,
+                                 int H, int g, int count, const uint8_t* px, const uint8_t* py,
+                                 int maxrec, const uint32_t* list, const unsigned* nlist,
+                                 void* acc, uint8_t* out, unsigned long long* zcount,
+                                 unsigned* sat, int blocks, hipStream_t stream) {
+  if (!accum_supported(W, H, g, true) || !window_inside(w, W, H, g) || count < 1 || count > 16 ||
+      blocks < 1 || blocks > 4096)
+    return hipErrorInvalidValue;
+  const int lg = pattern_log2(g, 1, 3);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, w.full_w * g, w.full_h * g);   // of the g*full_w x g*full_h image
+  const PatWords pat = pattern_words(count, px, py);
+  dispatch(stage_fits(s), [&](auto st) {
+    hipLaunchKernelGGL((k_accum_list_cam<st.value>), dim3((unsigned)blocks), dim3(kBlock), 0,
+                       stream, sc, cam, cams, W, w.x0, w.y0, lg, count, pat, maxrec, list, nlist,
+                       (uint2*)acc, out, zcount, sat);
+  });
   return hipGetLastError();
 }
 

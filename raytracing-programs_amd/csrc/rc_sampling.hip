@@ -1,7 +1,7 @@
 // rc_sampling.hip — the sampling features of libraycast_hip.so's C-ABI (include/raycast_hip.h):
 // rate maps, reconstruction filters, sparse sample patterns, progressive accumulation, windows of a
-// virtual image, the primary-visibility G-buffer, rotated views and ray batches and the free camera
-// and rays with origins, with adaptive
+// virtual image, the primary-visibility G-buffer, rotated views and ray batches, the free camera
+// and rays with origins and accumulation through free cameras, with adaptive
 // supersampling's getters.  Host code only: the kernels are
 // rc_sample_kernels.hip's and rc_filter.hip's (the one-ray image is rc_kernels.hip's k_render), the device context and the frame scaffold (enter,
 // ws_frame, claim_event_set, finish_device, finish_host) are rc_api.hip's, through rc_runtime.h.
@@ -249,6 +249,50 @@ static int camera_refused(const char* who, const rc_options* opt, int W, int H,
     return camera_mode_refused(who, opt) || rc_camera_check(cam) ||
            rc_window_check(vw, W, H, ss);
   }, no_check);
+}
+
+// Accumulation through a camera: the accumulation family's clauses in the camera family's mode
+// (parity by the table, cuda first in the check, then the sequence).
+static const Refusal kCameraAccumRefusal = {
+    nullptr,
+    1, "Error: %s: ssaa %d in the options: the sample sequence carries the grid, leave ssaa at 0 "
+    "or 1\n",
+    "Error: %s: accumulated samples through a camera are for fast mode: every pixel of a parity "
+    "image depends on the scan-order carry of the reference's own camera\n",
+    "Error: %s: num_gpus %d: the row shards take no accumulator\n",
+    kLatticeSide};
+
+static int camera_accum_refused(const char* who, const rc_options* opt, int W, int H,
+                                const rc_sample_seq* seq, int threshold, bool dense, bool masked) {
+  return refused(kCameraAccumRefusal, who, opt, W, H, seq->grid, threshold, masked,
+                 [&](int) { return camera_mode_refused(who, opt) || rc_sample_seq_check(seq); },
+                 [&](int) {
+                   if ((!dense || rc::accum_supported(W, H, seq->grid, false)) &&
+                       (!masked || rc::accum_supported(W, H, seq->grid, true)))
+                     return 0;
+                   return say("Error: %s: %d x %d is too large for the kernels' grids (at most "
+                              "65535 rows of tiles)\n", who, W, H);
+                 });
+}
+
+// The last two clauses of the pair: the number of cameras (`per`: the pass's count, the host
+// form's nsamples), then the first camera rc_camera_check would refuse, named by its index.
+static int cameras_refused(const char* who, const rc_camera* cams, int ncams, int per,
+                           const char* per_name) {
+  if (ncams != 1 && ncams != per)
+    return say("Error: %s: ncams %d is not 1 or %s (%d): one camera for all the samples, or one "
+               "for each\n", who, ncams, per_name, per);
+  for (int j = 0; j < ncams; ++j) {
+    for (int k = 0; k < 3; ++k)
+      if (!__builtin_isfinite(cams[j].eye[k]))
+        return say("Error: %s: cams[%d] fails rc_camera_check: eye[%d] is not finite\n", who, j,
+                   k);
+    for (int k = 0; k < 9; ++k)
+      if (!__builtin_isfinite(cams[j].view.m[k]))
+        return say("Error: %s: cams[%d] fails rc_camera_check: view.m[%d] (row %d, column %d) is "
+                   "not finite\n", who, j, k, k / 3, k % 3);
+  }
+  return 0;
 }
 
 static const Refusal kRaysFromRefusal = {
@@ -1036,6 +1080,73 @@ static int enqueue_camera(DevCtx& c, const rc_scene* s, const rc_camera* cam, co
   });
 }
 
+// enqueue_accum for passes through cameras (the caller holds c.mu and has passed
+// camera_accum_refused, the range checks and cameras_refused; fast mode): the accumulation
+// family's frame, with its counter slots, its span owner and its edge list, and the camera
+// kernels in the window kernels' place.  Sample j of pass k goes through cams[cam0[k] + j], or
+// through cams[0] when ncams is 1.  The cameras are copied into the launch's argument here, so the
+// caller's array is free when the call returns and nothing of a camera stays on the device.
+static int enqueue_accum_camera(DevCtx& c, const rc_scene* s, const rc_camera* cams, int ncams,
+                                const rc_window* vw, int W, int H, const rc_options* opt,
+                                const rc_sample_seq* seq, const AccumPass* passes,
+                                const int* cam0, int npasses, rc_accum_px* d_acc, uint8_t* d_out,
+                                hipStream_t stream) {
+  AccumFrame& a = c.acc;
+  bool masked = false;
+  for (int k = 0; k < npasses; ++k) masked = masked || passes[k].at > 0;
+  auto prepare = [&]() -> int {
+    if (a.count.ensure(AccumFrame::kSlots * 8) ||
+        (masked && c.aa_list.ensure((size_t)W * H * sizeof(uint32_t)))) {
+      std::fprintf(stderr, "Error: out of device memory for the edge list (%d x %d)\n", W, H);
+      return -1;
+    }
+    return ensure_done(a.done);
+  };
+  return ws_frame(c, stream, prepare, [&]() -> int {
+    a.valid = false;   // the block is this call's from here on
+    SampleFrame f{c, stream, kSpanAccum};
+    if (f.begin(s, &a.count, (size_t)npasses * 8)) return -1;
+    unsigned* cnt = (unsigned*)a.count.p;
+    uint32_t* list = (uint32_t*)c.aa_list.p;
+    const int maxrec = opt->max_recursion, g = seq->grid;
+    const rc::Window win{vw->full_w, vw->full_h, vw->x0, vw->y0};
+    for (int k = 0; k < npasses; ++k) {
+      const AccumPass& p = passes[k];
+      const bool last = k + 1 == npasses;
+      if (last && k > 0) HIP_TRY(hipEventRecord(f.ev[2], stream));
+      rc::CamSet set;
+      for (int j = 0; j < 16; ++j) {   // the slots past the pass's count are not read: camera 0's
+        const rc_camera& cam = cams[ncams == 1 || j >= p.count ? 0 : cam0[k] + j];
+        std::memcpy(set.eye[j], cam.eye, sizeof set.eye[j]);
+        std::memcpy(set.view[j].m, cam.view.m, sizeof set.view[j].m);
+      }
+      const uint8_t* px = seq->x + p.first;
+      const uint8_t* py = seq->y + p.first;
+      unsigned* slot = cnt + 2 * k;
+      if (p.at == 0) {
+        HIP_TRY(rc::launch_accum_cam(f.ls, set, win, W, H, g, p.count, px, py, p.reset, maxrec,
+                                     d_acc, d_out, f.zc, slot + 1, stream));
+      } else {
+        HIP_TRY(rc::launch_aa_mark(d_out, W, H, p.at, list, slot, stream));
+        if (last) HIP_TRY(hipEventRecord(f.ev[3], stream));
+        HIP_TRY(rc::launch_accum_list_cam(
+            f.ls, set, win, W, H, g, p.count, px, py, maxrec, list, slot, d_acc, d_out, f.zc,
+            slot + 1, rc::accum_list_blocks(W, H, c.cus, tune().adaptive_blocks), stream));
+      }
+      a.samples[k] = (uint8_t)p.count;
+      a.listed[k] = p.at > 0;
+    }
+    if (f.end()) return -1;
+    HIP_TRY(hipEventRecord(a.done, stream));
+    a.valid = true;
+    a.passes = npasses;
+    a.pixels = (long long)W * H;
+    a.ev_first = npasses > 1 ? 2 : 0;
+    a.ev_listed = passes[npasses - 1].at > 0;
+    return 0;
+  });
+}
+
 // -------------------------------------------------------------- the two entry shapes --
 // A *_device entry behind its null checks and its refusal: on the current device, on the
 // caller's stream or the context's, enqueue(c, st), then finish_device.  plain: the frame goes
@@ -1611,6 +1722,65 @@ int rc_render_accum(const rc_scene* s, int W, int H, const rc_options* opt,
       [&](DevCtx& c) {
         return enqueue_accum(c, s, W, H, opt, seq, passes, np, (rc_accum_px*)c.accum_px.p,
                              (uint8_t*)c.out.p, c.stream);
+      });
+}
+
+// ------------------------------------------------ accumulation through a free camera --
+int rc_accum_pass_camera_device(const rc_scene* s, const rc_camera* cams, int ncams,
+                                const rc_window* win, int W, int H, const rc_options* opt,
+                                const rc_sample_seq* seq, int first, int count, int threshold,
+                                int reset, rc_accum_px* d_acc, uint8_t* d_out, void* stream,
+                                rc_timing* timing) {
+  const char* who = "rc_accum_pass_camera_device";
+  if (!s || !cams || !opt || !seq || !d_acc || !d_out)
+    return say("Error: %s: a null pointer\n", who);
+  if ((uintptr_t)d_acc & 7u)
+    return say("Error: %s: the accumulator is not 8-byte aligned\n", who);
+  if (camera_accum_refused(who, opt, W, H, seq, threshold, threshold == 0, threshold > 0))
+    return -1;
+  const rc_window vw = win ? *win : rc_window{W, H, 0, 0};
+  if (rc_window_check(&vw, W, H, seq->grid)) return -1;
+  if (count < 1 || count > 16 || first < 0 || first > seq->nsamples - count)
+    return say("Error: %s: samples [%d, %d + %d) of a sequence of %d: a pass takes 1..16 samples "
+               "inside the sequence\n", who, first, first, count, seq->nsamples);
+  if (reset && threshold > 0)
+    return say("Error: %s: reset with threshold %d: a reset pass takes every pixel (there is no "
+               "image yet to find edges in), leave the threshold at 0\n", who, threshold);
+  if (cameras_refused(who, cams, ncams, count, "count")) return -1;
+  const AccumPass pass{first, count, threshold, reset != 0};
+  const int cam0 = 0;   // camera j of the pass is cams[j], whatever `first` is
+  return device_entry(opt, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_accum_camera(c, s, cams, ncams, &vw, W, H, opt, seq, &pass, &cam0, 1, d_acc,
+                                d_out, st);
+  });
+}
+
+int rc_render_camera_accum(const rc_scene* s, const rc_camera* cams, int ncams,
+                           const rc_window* win, int W, int H, const rc_options* opt,
+                           const rc_sample_seq* seq, uint8_t* pixmap, rc_timing* timing) {
+  const char* who = "rc_render_camera_accum";
+  if (!s || !cams || !opt || !seq || !pixmap) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  if (camera_accum_refused(who, opt, W, H, seq, 0, true, false)) return -1;
+  const rc_window vw = win ? *win : rc_window{W, H, 0, 0};
+  if (rc_window_check(&vw, W, H, seq->grid)) return -1;
+  if (cameras_refused(who, cams, ncams, seq->nsamples, "the sequence's length")) return -1;
+  // the whole sequence for every pixel in chunks of at most 16, the first one resetting; sample k
+  // goes through cams[k]
+  AccumPass passes[(RC_ACCUM_MAX_SAMPLES + 15) / 16];
+  int cam0[(RC_ACCUM_MAX_SAMPLES + 15) / 16];
+  int np = 0;
+  for (int k = 0; k < seq->nsamples; k += 16) {
+    cam0[np] = k;
+    passes[np++] = {k, seq->nsamples - k < 16 ? seq->nsamples - k : 16, 0, k == 0};
+  }
+  return host_entry(
+      opt, W, H, pixmap, timing, t0,
+      "Error: out of device memory for the image and its accumulator (%d x %d)\n", false,
+      [&](DevCtx& c) { return c.accum_px.ensure((size_t)W * H * sizeof(rc_accum_px)); },
+      [&](DevCtx& c) {
+        return enqueue_accum_camera(c, s, cams, ncams, &vw, W, H, opt, seq, passes, cam0, np,
+                                    (rc_accum_px*)c.accum_px.p, (uint8_t*)c.out.p, c.stream);
       });
 }
 
