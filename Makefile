@@ -3,7 +3,9 @@
 #   make            libraycast_hip.so (HIP kernels + C-ABI), libraycast_front.so (host
 #                   scene parser / P3 writer), bin/raytrace (drop-in CLI), oracle, primcheck
 #                   (tests/build/libprimcheck.so, the ray-level suite's device harness), pincheck
-#                   (tests/build/libpincheck.so, phase C's carry-point table wave by wave)
+#                   (tests/build/libpincheck.so, phase C's carry-point table wave by wave), resolvecheck
+#                   (tests/build/libresolvecheck.so and its four wrong variants, the carry resolver
+#                   entry by entry)
 #   make ref        oracle/_ref: the reference C/ sources compiled in place (test oracle)
 #
 # Numerics flags (parity with the x86-64 gcc -O3 reference):
@@ -28,11 +30,11 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
 CFLAGS   := -O3 -ffp-contract=off -fPIC -Wall -Wno-unused-result -Iinclude -I$(SRC)
 
 HIP_SRCS  := $(SRC)/rc_kernels.hip $(SRC)/rc_sample_kernels.hip $(SRC)/rc_api.hip $(SRC)/rc_sampling.hip $(SRC)/rc_shard.hip $(SRC)/rc_filter.hip
-HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_pixel.hpp $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
+HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_pixel.hpp $(SRC)/rc_resolve.hpp $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
 FRONT_SRC := $(SRC)/front/parse.c $(SRC)/front/objects.c $(SRC)/front/ppm.c
 
-.PHONY: all oracle ref clean stamps stamps2 sanitize primcheck pincheck
-all: $(LIB)/libraycast_hip.so $(LIB)/libraycast_front.so $(BIN)/raytrace oracle primcheck pincheck
+.PHONY: all oracle ref clean stamps stamps2 sanitize primcheck pincheck resolvecheck
+all: $(LIB)/libraycast_hip.so $(LIB)/libraycast_front.so $(BIN)/raytrace oracle primcheck pincheck resolvecheck
 
 $(OBJ)/%.o: $(SRC)/%.hip $(HIP_HDRS)
 	@mkdir -p $(OBJ)
@@ -147,6 +149,19 @@ pincheck: $(PRIM_OUT)/libpincheck.so
 $(PRIM_OUT)/libpincheck.so: tests/tools/pin_check.hip $(HIP_HDRS) $(OBJ)/rc_scene.o | oracle
 	@mkdir -p $(PRIM_OUT)
 	$(HIPCC) $(HIPFLAGS) -shared $(OBJ)/rc_scene.o tests/tools/pin_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
+
+# Test-only device harness of the carry resolver (tests/test_gpu_resolve.py): the evaluator forms
+# case by case and the product's wave_window / block_window (rc_resolve.hpp) chain by chain, built
+# like primcheck.  libresolvecheck_w1..w4.so are the same harness with one deliberate mistake each
+# (RV_WRONG), which the suite must catch.
+RESOLVE_LIBS := $(PRIM_OUT)/libresolvecheck.so $(foreach k,1 2 3 4,$(PRIM_OUT)/libresolvecheck_w$(k).so)
+resolvecheck: $(RESOLVE_LIBS)
+$(PRIM_OUT)/libresolvecheck.so: tests/tools/resolve_check.hip $(HIP_HDRS) $(OBJ)/rc_scene.o | oracle
+	@mkdir -p $(PRIM_OUT)
+	$(HIPCC) $(HIPFLAGS) -shared $(OBJ)/rc_scene.o tests/tools/resolve_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
+$(PRIM_OUT)/libresolvecheck_w%.so: tests/tools/resolve_check.hip $(HIP_HDRS) $(OBJ)/rc_scene.o | oracle
+	@mkdir -p $(PRIM_OUT)
+	$(HIPCC) $(HIPFLAGS) -DRV_WRONG=$* -shared $(OBJ)/rc_scene.o tests/tools/resolve_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
 
 # occupancy variants of the pixel kernels (RC_HIP_LIB=libraycast_hip_<v>.so): w3 = phase A /
 # k_render compiled for 3 waves per SIMD (no VGPR spills), f3 = phase C (k_dep_chunks, k_finish)

@@ -1011,6 +1011,17 @@ int rc_debug_inject_error(int nth_frame);
  * and skip < 0 then ends the frame with a failure (-2).  Returns the number of wrong pixmap bytes (0) or the
  * sweep's failure status (< 0); -1 for ndep outside 1 .. 2^24. */
 int rc_debug_scatter_selftest(int64_t ndep, int64_t seed, int skip);
+/* Test aid: what the carry resolver published in the current device's last one-frame-at-a-time
+ * parity frame (rc_render on one GPU, rc_render_device), copied out of that frame's workspace
+ * once the device is idle.  *ndep: its DEP pixels.  With cap >= *ndep also pix (the DEP pixels'
+ * indices y * W + x in scan order), carry (3 floats per entry: the carry-in the entry was
+ * resolved to, decoded from its three tagged granules) and hit (1 where some bounce level hit at
+ * that carry-in: the tags' bit 31); with a smaller cap only *ndep is written.  *first_bad
+ * (optional): the first entry whose three tags are not all the frame's epoch, -1 when every one
+ * is.  Returns 0; -1 when the workspace holds no parity frame; -2 when the frame's hand-off
+ * failed.  No kernel runs and no render path changes. */
+int rc_debug_carry_ins(int64_t cap, int64_t *ndep, int64_t *pix, float *carry, uint8_t *hit,
+                       int64_t *first_bad);
 /* Wait for every submitted frame, then release the current device's frame pipeline (its
  * CU-partitioned streams and events; the frame workspaces stay allocated).  The next
  * rc_frame_submit builds it again, re-reading RC_PIPE_* from the environment.  Returns what

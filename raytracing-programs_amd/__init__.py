@@ -284,7 +284,8 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_group_transport", "rc_render_sharded", "rc_group_last_stats",
                "rc_default_tuning", "rc_set_tuning", "rc_get_tuning", "rc_lone_frames_check",
                "rc_debug_inject_error", "rc_group_debug_bound", "rc_resolver_stats_get",
-               "rc_group_rank_stats", "rc_debug_scatter_selftest", "rc_adaptive_stats_get",
+               "rc_group_rank_stats", "rc_debug_scatter_selftest", "rc_debug_carry_ins",
+               "rc_adaptive_stats_get",
                "rc_adaptive_phase_ms", "rc_render_rates", "rc_render_rates_device",
                "rc_rate_stats_get", "rc_rate_phase_ms", "rc_filter_box", "rc_filter_tent",
                "rc_filter_check", "rc_filter_env", "rc_render_filtered",
@@ -2026,6 +2027,31 @@ def scatter_selftest(ndep, seed=0, skip=0):
     lib = hip_lib()
     lib.rc_debug_scatter_selftest.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
     return lib.rc_debug_scatter_selftest(int(ndep), int(seed), int(skip))
+
+
+def debug_carry_ins():
+    """Test aid (rc_debug_carry_ins): what the resolver published in the device's last
+    one-frame-at-a-time parity frame (render on one GPU, render_device), read back from the
+    frame's workspace: (pix int64[n] the DEP pixels y * W + x in scan order, carry float32[n, 3]
+    each entry's carry-in, hit uint8[n] its hit bit, first_bad: the first entry whose tags are not
+    the frame's epoch, or -1).  Raises if there is no such frame or its hand-off failed."""
+    lib = hip_lib()
+    lib.rc_debug_carry_ins.argtypes = [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)] + \
+        [ctypes.c_void_p] * 3 + [ctypes.POINTER(ctypes.c_int64)]
+    n, bad = ctypes.c_int64(0), ctypes.c_int64(-1)
+    rc = lib.rc_debug_carry_ins(0, ctypes.byref(n), None, None, None, None)
+    if rc != 0:
+        raise RuntimeError(f"rc_debug_carry_ins: {rc} (no completed parity frame in the workspace, or "
+                           f"its hand-off failed)")
+    pix = np.zeros(n.value, np.int64)
+    carry = np.zeros((n.value, 3), np.float32)
+    hit = np.zeros(n.value, np.uint8)
+    if n.value:
+        rc = lib.rc_debug_carry_ins(n.value, ctypes.byref(n), pix.ctypes.data, carry.ctypes.data,
+                                    hit.ctypes.data, ctypes.byref(bad))
+        if rc != 0 or n.value != len(pix):
+            raise RuntimeError(f"rc_debug_carry_ins: {rc}")
+    return pix, carry, hit, int(bad.value)
 
 
 def write_p3(img, path):

@@ -2085,6 +2085,51 @@ int rc_debug_scatter_selftest(int64_t ndep, int64_t seed, int skip) {
   return (int)std::min<long long>(bad, 1 << 30);
 }
 
+// Test aid: the carry-ins the resolver published in the current device's last lone parity frame
+// (rc_render, rc_render_device), read back from the frame's workspace after it has completed.
+// No kernel and no render path is involved: three copies out of FrameBufs.
+int rc_debug_carry_ins(int64_t cap, int64_t* ndep, int64_t* pix, float* carry, uint8_t* hit,
+                       int64_t* first_bad) {
+  if (!ndep || cap < 0) return -1;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  DevCtx* c;
+  if (ctx_get(dev, &c)) return -1;
+  std::lock_guard<std::mutex> lk(c->mu);
+  if (flush_phase_c(*c, false)) return -1;
+  HIP_TRY(hipDeviceSynchronize());   // the frame ran on the caller's stream
+  const FrameBufs& b = c->fb;
+  if (!b.epoch || !b.cin.p || !b.counters.p || !b.dep_pix.p || !b.team.p) return -1;
+  int err = 0, cnt[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpy(&err, b.team.p, sizeof err, hipMemcpyDeviceToHost));
+  if (err) return -2;   // the frame's hand-off failed: its carry-ins are not all there
+  HIP_TRY(hipMemcpy(cnt, b.counters.p, sizeof cnt, hipMemcpyDeviceToHost));
+  const int64_t n = cnt[2];
+  if (n < 0 || (size_t)n * rc::kCinBytes > b.cin.bytes || (size_t)n * sizeof(long long) > b.dep_pix.bytes)
+    return -1;
+  *ndep = n;
+  if (first_bad) *first_bad = -1;
+  if (cap < n || n == 0) return 0;   // the count alone (the caller sizes its arrays by it)
+  if (!pix || !carry || !hit) return -1;
+  static_assert(sizeof(long long) == sizeof(int64_t), "dep_pix entries");
+  HIP_TRY(hipMemcpy(pix, b.dep_pix.p, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost));
+  std::vector<unsigned long long> g((size_t)n * 3);
+  HIP_TRY(hipMemcpy(g.data(), b.cin.p, g.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  for (int64_t j = 0; j < n; ++j) {
+    const unsigned t0 = (unsigned)(g[3 * j] >> 32);
+    for (int k = 0; k < 3; ++k) {
+      const unsigned long long v = g[3 * j + k];
+      const unsigned bits = (unsigned)v;
+      std::memcpy(&carry[3 * j + k], &bits, 4);
+      // three tags, all this frame's epoch, the hit flag (bit 31) the same in each
+      if (((unsigned)(v >> 32) != t0 || (t0 & 0x7fffffffu) != b.epoch) && first_bad && *first_bad < 0)
+        *first_bad = j;
+    }
+    hit[j] = (uint8_t)(t0 >> 31);
+  }
+  return 0;
+}
+
 int rc_profile_begin(void) {
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));

@@ -1548,12 +1548,18 @@ __device__ __forceinline__ unsigned group_min_u(unsigned v, int Grt) {
     v = __builtin_elementwise_min(v, (unsigned)__shfl_xor((int)v, off, 64));
   return v;
 }
+// (RC_ARGMIN_KEY / RC_ARGMIN_UNKEY and RC_SKIP_AFTER_MISS below: only the wrong variants of the
+// test harness tests/tools/resolve_check.hip define them otherwise; the product never does)
+#ifndef RC_ARGMIN_KEY
+#define RC_ARGMIN_KEY(k) (unsigned)(k)
+#define RC_ARGMIN_UNKEY(kb) (int)(kb)
+#endif
 template <int GT>
 __device__ __forceinline__ int group_argmin_pos(float& t, int k, int G) {
   const unsigned tb = group_min_u<GT>(__float_as_uint(t), G);
-  const unsigned kb = group_min_u<GT>(__float_as_uint(t) == tb ? (unsigned)k : 0xffffffffu, G);
+  const unsigned kb = group_min_u<GT>(__float_as_uint(t) == tb ? RC_ARGMIN_KEY(k) : 0xffffffffu, G);
   t = __uint_as_float(tb);
-  return (int)kb;
+  return RC_ARGMIN_UNKEY(kb);
 }
 
 __device__ __forceinline__ V3 carry_path_coop(const Scene& sc, const LaneShape& ls, int kself,
@@ -1778,6 +1784,9 @@ __device__ __forceinline__ void hit_frame_sel(const rc_shape& s, V3 O, V3 D, flo
 #ifndef RC_LAST_SKIP
 #define RC_LAST_SKIP 0   // measured: lone resolver 4.21 -> 4.37 ms (the branch splits the step)
 #endif
+#ifndef RC_SKIP_AFTER_MISS
+#define RC_SKIP_AFTER_MISS (-1)   // the shape a level skips after a missed level: none
+#endif
 template <int GT, int kQ>
 __device__ __forceinline__ V3 carry_path_spec(const Scene& sc, const LaneShape& ls, int kself,
                                               int Grt, int half, const DepRec& r, int maxrec,
@@ -1861,7 +1870,7 @@ __device__ __forceinline__ V3 carry_path_spec(const Scene& sc, const LaneShape& 
     C = sel(hit, P, C);
     N = sel(hit, Nw, N);
     obj = hit ? w : obj;
-    S = hit ? w : -1;
+    S = hit ? w : RC_SKIP_AFTER_MISS;
     lvl += two ? 2 : 1;
     if (lvl >= maxrec || !reflective(sc, obj)) break;
     RC_STAMP(3);
