@@ -895,8 +895,8 @@ int rc_view_phase_ms(double ms[1]);
  *     refuses, with cuda mode refused after num_gpus.
  * Out of scope: cuda and parity mode; scrolling with a camera (accumulation with one is
  *     rc_accum_pass_camera_device, below); a G-buffer plane
- *     entry for cameras (rc_trace_rays_from with hits alone is the pick); any-hit queries with a
- *     distance bound; multi-GPU. */
+ *     entry for cameras (rc_trace_rays_from with hits alone is the pick); multi-GPU.  Any-hit
+ *     queries with a distance bound are rc_occluded_rays, below. */
 typedef struct rc_camera { float eye[3]; rc_view view; } rc_camera;
 _Static_assert(sizeof(rc_camera) == 48, "rc_camera layout (ctypes binding)");
 int rc_camera_check(const rc_camera *cam);
@@ -968,6 +968,109 @@ int rc_accum_pass_camera_device(const rc_scene *scene, const rc_camera *cams, in
 int rc_render_camera_accum(const rc_scene *scene, const rc_camera *cams, int ncams,
                            const rc_window *win, int width, int height, const rc_options *opt,
                            const rc_sample_seq *seq, uint8_t *pixmap, rc_timing *timing);
+
+/* Any-hit visibility queries and ambient occlusion (rc_occluded_rays, rc_occluded_rays_device,
+ * rc_ao_pass_device, rc_ao_resolve_device, rc_render_ao; fast mode).  The question a shadow ray
+ * asks, for the caller's own rays: is anything in the way, within this distance?  And the pass
+ * that asks it for a set of directions around every primary hit of a camera frame and counts the
+ * answers, in one kernel: an ambient-occlusion plane, accumulated across calls.
+ * The occlusion rule for one ray (O, D, skip, tmax).  With (hit_k, t_k) = rco_prim_shape(shape k,
+ *     O, D, skip) of the oracle,
+ *         blocked = any over k != skip of (hit_k and t_k > 0 and t_k < tmax).
+ *     D is used as given, not normalised: t and tmax are in units of |D|.  skip = -1 skips nothing
+ *     and switches the quadrics' z rule off; any other value switches it on (a bounce ray's
+ *     quadric hit below the origin's z is ignored), which is exactly the reference's use of skip.
+ *     With tmax = +inf the rule is the reference's shadow test: blocked equals
+ *     rco_prim_nearest(O, D, skip, shadow = 1).idx >= 0.  A tmax that is NaN, <= 0 or -inf blocks
+ *     nothing (t < tmax fails).  On the device tmax = +inf takes the shade path's own shadow scan
+ *     and a finite tmax the nearest scan's tests with the bound in the place of the best t; both
+ *     stop at the first accepted shape.
+ * rc_occluded_rays*: n rays (1 .. 2^24); origins and dirs as in rc_trace_rays_from; skip: int32[n]
+ *     or NULL for -1 everywhere; tmax: float[n] or NULL for +inf everywhere; out: one byte a ray,
+ *     1 blocked, 0 open.  Per-ray data is data (device data for the _device entry) and is not
+ *     inspected: a non-finite origin or direction blocks nothing, as in the oracle; a skip outside
+ *     [-1, n_shapes) skips nothing but switches the z rule on.  One lane a ray.  The two entries
+ *     take the same arguments: the _device entry is enqueued on the stream and timing (may be
+ *     NULL) is rc_render_view_device's; the host form is synchronous on opt->device, ignores
+ *     `stream` and fills timing as rc_render_view does.
+ * Ambient occlusion through a camera.  The state is the caller's array of rc_ao_px, one a pixel,
+ *     row-major, 4-byte aligned device memory: `rays` occlusion rays have been counted for the
+ *     pixel, `open` of them were not blocked.  A direction set (rc_ao_dirs) travels by value: n
+ *     directions u[0..n), used as given, and one tmax in units of |u|.
+ *     rc_ao_dirs_check: 0, or one message and -1 for a null set, n outside 1..64, a tmax that is
+ *     not in (0, +inf] (NaN included), and the first direction that has a non-finite component or
+ *     is (+-0, +-0, +-0), named by its index.
+ *     rc_ao_pass_device does this for window pixel (x, y) (win = NULL: the whole image):
+ *       1. the primary ray is rc_render_camera's for cam at ssaa = 1: the view contract's
+ *          direction d, the origin cam->eye, (id, t, P, N) = rco_prim_nearest(eye, d, skip = -1).
+ *          The general scan is used at every eye, +0 included (bit-equal to the origin forms);
+ *       2. a miss: open_add = n;
+ *       3. a hit: direction j is D_j = dot(N, u_j) < 0 ? u_j * -1.0f : u_j (the oracle's float dot,
+ *          (N0 u0 + N1 u1) + N2 u2; a NaN dot does not flip), the ray is (P, D_j, skip = id,
+ *          dirs.tmax), and open_add = the number of j whose ray is not blocked.  skip = id carries
+ *          the reference's z rule for rays that leave a surface, as its own shadow rays do: a
+ *          quadric hit below P's z does not block;
+ *       4. (open, rays) = reset ? (0, 0) : d_ao[pixel].  If rays + n > 65535 the record stays as
+ *          it is: the pixel is saturated and none of its rays are shot, the primary ray included.
+ *          Otherwise open += open_add, rays += n;
+ *       5. d_out (W*H bytes, may be NULL) gets rc_ao_byte(open, rays) of the record as it now is.
+ *     rc_ao_byte(open, rays) = rays ? (510 * open + rays) / (2 * rays) : 255 in integer
+ *     arithmetic: 255 * open / rays rounded half up.
+ *     rc_ao_resolve_device: step 5 alone, for every record; no scene, no workspace.
+ *     rc_render_ao: the host form, synchronous on opt->device, the state owned by the library: a
+ *     reset pass with sets[0], one further pass for each of sets[1..nsets), then the W*H bytes.
+ *     rc_ao_stats_get: the last pass of the current device: hit_pixels (unsaturated pixels whose
+ *     primary ray hit), rays (occlusion rays shot: n * hit_pixels), blocked (those that were
+ *     blocked) and saturated (pixels left as they were).  rc_ao_phase_ms: the span of the last
+ *     call's kernels (every pass of rc_render_ao; a ray batch too).
+ * On the device: one kernel a pass, rc_render_camera's grid, one lane a pixel.  The direction loop
+ *     is uniform, so u_j and tmax are read from the kernel's arguments with scalar loads and only
+ *     the hit point, the skip index and the flip are per lane: neighbouring lanes test the same
+ *     direction from neighbouring points, so the early exit diverges little.  The record is one
+ *     4-byte load and one 4-byte store a lane.  Nothing is kept on the device between passes but
+ *     the caller's state, and two passes in flight on two states share nothing.
+ * Refused, each with one message and -1, from the arguments alone (before any device work), in
+ *     this order:
+ *       1. a null scene, camera, options, direction set or state (win and d_out may be null;
+ *          rc_render_ao: the pixmap may not; rc_occluded_rays*: a null scene, options, origins,
+ *          dirs or out);
+ *       2. a d_ao that is not 4-byte aligned;
+ *       3. the camera family's clauses in their order: parity mode, num_gpus > 1, cuda mode, then
+ *          what rc_window_check refuses for W, H and the window at factor 1 (rc_occluded_rays*: the
+ *          three mode clauses);
+ *       4. an opt->ssaa other than 0 or 1;
+ *       5. what rc_camera_check refuses (rc_occluded_rays*: n outside 1 .. 2^24);
+ *       6. what rc_ao_dirs_check refuses (rc_render_ao: nsets outside 1..1024, then the first set
+ *          that fails, named by its index).
+ *     rc_ao_resolve_device: a null pointer, a misaligned d_ao, W or H below 1 or an image past
+ *     one grid.
+ * Out of scope: cosine or per-direction weights; supersampled primary rays; multiplying the plane
+ *     into a colour image; cuda and parity mode; multi-GPU. */
+#define RC_AO_MAX_DIRS 64
+typedef struct rc_ao_px { uint16_t open, rays; } rc_ao_px;
+typedef struct rc_ao_dirs { int32_t n; float tmax; float u[RC_AO_MAX_DIRS][3]; } rc_ao_dirs;
+typedef struct rc_ao_stats { int64_t hit_pixels, rays, blocked, saturated; } rc_ao_stats;
+_Static_assert(sizeof(rc_ao_px) == 4, "rc_ao_px layout (the kernels' 4-byte record)");
+_Static_assert(sizeof(rc_ao_dirs) == 776, "rc_ao_dirs layout (a kernel argument, ctypes binding)");
+int rc_ao_dirs_check(const rc_ao_dirs *dirs);
+int rc_occluded_rays(const rc_scene *scene, const rc_options *opt, int64_t n,
+                     const float *origins /* n x 3 */, const float *dirs /* n x 3 */,
+                     const int32_t *skip /* n, or NULL */, const float *tmax /* n, or NULL */,
+                     uint8_t *out /* n */, void *stream /* ignored */, rc_timing *timing);
+int rc_occluded_rays_device(const rc_scene *scene, const rc_options *opt, int64_t n,
+                            const float *d_origins, const float *d_dirs, const int32_t *d_skip,
+                            const float *d_tmax, uint8_t *d_out, void *stream, rc_timing *timing);
+int rc_ao_pass_device(const rc_scene *scene, const rc_camera *cam,
+                      const rc_window *win /* NULL: the whole image */, int width, int height,
+                      const rc_options *opt, const rc_ao_dirs *dirs, int reset, rc_ao_px *d_ao,
+                      uint8_t *d_out /* W*H bytes, or NULL */, void *stream, rc_timing *timing);
+int rc_ao_resolve_device(const rc_ao_px *d_ao, int width, int height, uint8_t *d_out,
+                         void *stream);
+int rc_render_ao(const rc_scene *scene, const rc_camera *cam, const rc_window *win, int width,
+                 int height, const rc_options *opt, const rc_ao_dirs *sets, int nsets,
+                 uint8_t *pixmap /* W*H bytes */, rc_timing *timing);
+int rc_ao_stats_get(rc_ao_stats *out);
+int rc_ao_phase_ms(double ms[1]);
 
 /* Frames in flight(an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out

@@ -195,6 +195,26 @@ RAYS_MAX = 1 << 24
 # the outputs of a ray batch in rc_ray_out's order: name -> (dtype, trailing shape)
 RAY_OUTPUTS = {"rgb8": (np.uint8, (3,)), "rgb": (np.float32, (3,)), "hits": (HIT_DTYPE, ())}
 
+AO_MAX_DIRS = 64          # directions of one set at most
+AO_MAX_RAYS = 65535       # occlusion rays a pixel's record can hold
+AO_MAX_SETS = 1024        # sets of one render_ao call at most
+
+
+class RcAoDirs(ctypes.Structure):
+    """rc_ao_dirs (776 bytes): n directions, used as given, and one tmax in units of their length."""
+    _fields_ = [("n", ctypes.c_int32), ("tmax", ctypes.c_float),
+                ("u", (ctypes.c_float * 3) * AO_MAX_DIRS)]
+
+
+class RcAoStats(ctypes.Structure):
+    _fields_ = [("hit_pixels", ctypes.c_int64), ("rays", ctypes.c_int64),
+                ("blocked", ctypes.c_int64), ("saturated", ctypes.c_int64)]
+
+
+# rc_ao_px as a numpy record: `rays` occlusion rays counted for the pixel, `open` of them not blocked
+AO_DTYPE = np.dtype([("open", np.uint16), ("rays", np.uint16)])
+assert ctypes.sizeof(RcAoDirs) == 776 and AO_DTYPE.itemsize == 4
+
 
 def _hier_points(g):
     """hier<g> (include/raycast_hip.h, rc_sample_seq): point k is the bit-reversal r of k over
@@ -302,7 +322,9 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_trace_rays_device", "rc_view_phase_ms", "rc_camera_check",
                "rc_render_camera", "rc_render_camera_device", "rc_trace_rays_from",
                "rc_trace_rays_from_device", "rc_accum_pass_camera_device",
-               "rc_render_camera_accum"]
+               "rc_render_camera_accum", "rc_ao_dirs_check", "rc_occluded_rays",
+               "rc_occluded_rays_device", "rc_ao_pass_device", "rc_ao_resolve_device",
+               "rc_render_ao", "rc_ao_stats_get", "rc_ao_phase_ms"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -552,6 +574,25 @@ def _hip_lib_locked():
                                            ctypes.c_int, ctypes.POINTER(RcOptions),
                                            ctypes.POINTER(RcSampleSeq), ctypes.c_void_p,
                                            ctypes.POINTER(RcTiming)]
+    lib.rc_ao_dirs_check.argtypes = [ctypes.POINTER(RcAoDirs)]
+    for name in ("rc_occluded_rays", "rc_occluded_rays_device"):
+        getattr(lib, name).argtypes = [ctypes.c_void_p, ctypes.POINTER(RcOptions), ctypes.c_int64,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.POINTER(RcTiming)]
+    lib.rc_ao_pass_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcCamera),
+                                      ctypes.POINTER(RcWindow), ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(RcOptions), ctypes.POINTER(RcAoDirs),
+                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.POINTER(RcTiming)]
+    lib.rc_ao_resolve_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_void_p]
+    lib.rc_render_ao.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcCamera),
+                                 ctypes.POINTER(RcWindow), ctypes.c_int, ctypes.c_int,
+                                 ctypes.POINTER(RcOptions), ctypes.POINTER(RcAoDirs), ctypes.c_int,
+                                 ctypes.c_void_p, ctypes.POINTER(RcTiming)]
+    lib.rc_ao_stats_get.argtypes = [ctypes.POINTER(RcAoStats)]
+    lib.rc_ao_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
     _hip = lib
     return lib
 
@@ -1974,6 +2015,197 @@ def trace_rays_from_device(scene, n, d_origins_ptr, d_dirs_ptr, d_rgb8_ptr=None,
     _call("rc_trace_rays_from_device", scene.packed(), ctypes.byref(opt), int(n),
           ctypes.c_void_p(d_origins_ptr), ctypes.c_void_p(d_dirs_ptr), ctypes.byref(ro),
           _stream(stream_ptr))
+
+
+def ao_dirs(n, tmax=np.inf, rot=None):
+    """A direction set (u [n, 3] float32, tmax) for the occlusion pass: the spiral points of the
+    unit sphere, z_i = 1 - 2 (i + 1/2) / n, r_i = sqrt(1 - z_i^2), phi_i = (i + 1/2) pi (3 -
+    sqrt 5), u_i = (r_i cos phi_i, r_i sin phi_i, z_i), computed in float64, multiplied by the
+    3 x 3 `rot` when one is given (so that successive passes use different sets) and rounded once
+    to float32.  The pass flips each direction into the hit normal's hemisphere.  The function only
+    makes inputs: the device contract is exact for whatever set it is given."""
+    n = int(n)
+    if not 1 <= n <= AO_MAX_DIRS:
+        raise ValueError(f"ao_dirs: n {n} is not 1..{AO_MAX_DIRS}")
+    i = np.arange(n, dtype=np.float64) + 0.5
+    z = 1.0 - 2.0 * i / n
+    r = np.sqrt(1.0 - z * z)
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    u = np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+    if rot is not None:
+        m = np.asarray(rot, dtype=np.float64)
+        if m.shape != (3, 3):
+            raise ValueError(f"ao_dirs: rot is a 3 x 3 matrix, got shape {m.shape}")
+        u = u @ m.T
+    return u.astype(np.float32), float(tmax)
+
+
+def _rc_ao_dirs(dirs, what):
+    """The RcAoDirs of a set (u, tmax): u is [n, 3], used as given (the library checks it)."""
+    try:
+        u, tmax = dirs
+        u = np.ascontiguousarray(u, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: a direction set is a (u [n, 3], tmax) pair") from None
+    if u.ndim != 2 or u.shape[1] != 3 or not 1 <= len(u) <= AO_MAX_DIRS:
+        raise ValueError(f"{what}: u is [n, 3] with n in 1..{AO_MAX_DIRS}, got shape {u.shape}")
+    d = RcAoDirs(n=len(u), tmax=float(tmax))
+    ctypes.memmove(d.u, u.ctypes.data, u.nbytes)
+    return d
+
+
+def ao_dirs_check(dirs):
+    """rc_ao_dirs_check: True when the library takes the set (u, tmax): tmax in (0, +inf], every
+    direction finite and not zero (its message goes to stderr otherwise)."""
+    return hip_lib().rc_ao_dirs_check(ctypes.byref(_rc_ao_dirs(dirs, "ao_dirs_check"))) == 0
+
+
+def ao_flip(N, u):
+    """The pass's directions at a hit: [..., n, 3] float32, u_j * -1.0f where the float dot
+    (N0 u0 + N1 u1) + N2 u2 is below zero and u_j as given elsewhere (a zero or NaN dot does not
+    flip).  N is [..., 3], u is [n, 3]."""
+    N = np.asarray(N, dtype=np.float32)[..., None, :]
+    u = np.asarray(u, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        d = N[..., 0] * u[:, 0]
+        d = d + N[..., 1] * u[:, 1]
+        d = d + N[..., 2] * u[:, 2]
+        return np.where((d < 0)[..., None], u * np.float32(-1.0), u).astype(np.float32)
+
+
+def _ao_state(acc):
+    acc = np.asarray(acc)
+    if acc.dtype != AO_DTYPE or acc.ndim != 2:
+        raise ValueError(f"an occlusion state is [H, W] of AO_DTYPE, got {acc.dtype} {acc.shape}")
+    return acc
+
+
+def ao_step(acc, open_add, n, reset=False):
+    """One occlusion pass in numpy: (acc', saturated).  acc is [H, W] of AO_DTYPE, open_add [H, W]
+    the pass's open rays per pixel (n at a primary miss), n its directions.  A pixel whose rays + n
+    would pass 65535 is saturated and keeps its record; `reset` takes every record as zero."""
+    acc, n = _ao_state(acc), int(n)
+    add = np.asarray(open_add)
+    if not 1 <= n <= AO_MAX_DIRS or add.shape != acc.shape or (add < 0).any() or (add > n).any():
+        raise ValueError(f"ao_step: n {n} (1..{AO_MAX_DIRS}) and open_add {add.shape} in 0..n for "
+                         f"a state of {acc.shape}")
+    rays = np.zeros(acc.shape, np.uint32) if reset else acc["rays"].astype(np.uint32)
+    opn = np.zeros(acc.shape, np.uint32) if reset else acc["open"].astype(np.uint32)
+    sat = rays + n > AO_MAX_RAYS
+    new = np.zeros(acc.shape, AO_DTYPE)
+    new["open"] = np.where(sat, opn, opn + add.astype(np.uint32))
+    new["rays"] = np.where(sat, rays, rays + n)
+    return new, int(sat.sum())
+
+
+def ao_byte(acc):
+    """rc_ao_byte of every record: (510 open + rays) // (2 rays), 255 where rays is 0."""
+    acc = _ao_state(acc)
+    opn, rays = acc["open"].astype(np.int64), acc["rays"].astype(np.int64)
+    return np.where(rays > 0, (510 * opn + rays) // np.maximum(2 * rays, 1), 255).astype(np.uint8)
+
+
+def _ray_words(a, n, dtype, what, name):
+    """A per-ray word array of an occlusion batch ([n] of dtype), or None."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.shape != (n,):
+        raise ValueError(f"{what}: {name} is [n] like the rays ({n}), got shape {a.shape}")
+    return a
+
+
+def occluded_rays(scene, origins, dirs, skip=None, tmax=None, depth=6, mode="fast", device=0,
+                  timing=None):
+    """rc_occluded_rays: is ray k, leaving origins[k] along dirs[k] (both [n, 3] float32, used as
+    given), blocked by a shape other than skip[k] (int32, None: -1 everywhere) at 0 < t < tmax[k]
+    (float32 in units of |dirs[k]|, None: +inf everywhere)?  [n] uint8, 1 blocked.  With tmax inf
+    that is the reference's shadow test.  Fast mode only."""
+    d = _ray_dirs(dirs)
+    o = np.asarray(origins)
+    if o.shape != d.shape:
+        raise ValueError(f"occluded_rays: origins is an [n, 3] array like dirs {d.shape}, got "
+                         f"{o.shape}")
+    o = np.ascontiguousarray(o, dtype=np.float32)
+    s = _ray_words(skip, len(d), np.int32, "occluded_rays", "skip")
+    tm = _ray_words(tmax, len(d), np.float32, "occluded_rays", "tmax")
+    out = np.zeros(len(d), dtype=np.uint8)
+    opt = options(depth, mode, 1, device)
+    with _timed(timing) as (t, _):
+        _call("rc_occluded_rays", scene.packed(), ctypes.byref(opt), len(d), _host_ptr(o),
+              _host_ptr(d), None if s is None else _host_ptr(s),
+              None if tm is None else _host_ptr(tm), _host_ptr(out), None, ctypes.byref(t))
+    return out
+
+
+def occluded_rays_device(scene, n, d_origins_ptr, d_dirs_ptr, d_out_ptr, d_skip_ptr=None,
+                         d_tmax_ptr=None, stream_ptr=None, depth=6, mode="fast", timing=None):
+    """rc_occluded_rays_device: the n rays, the optional per-ray words and the n bytes in device
+    memory, enqueued on the stream and asynchronous unless `timing` is given."""
+    opt = options(depth, mode)
+    with _timed(timing) as (_, t):
+        _call("rc_occluded_rays_device", scene.packed(), ctypes.byref(opt), int(n),
+              ctypes.c_void_p(d_origins_ptr), ctypes.c_void_p(d_dirs_ptr),
+              ctypes.c_void_p(d_skip_ptr or 0), ctypes.c_void_p(d_tmax_ptr or 0),
+              ctypes.c_void_p(d_out_ptr), _stream(stream_ptr), t)
+
+
+def ao_pass_device(scene, eye, m, width, height, dirs, d_ao_ptr, d_out_ptr=None, window=None,
+                   reset=False, stream_ptr=None, depth=6, mode="fast", timing=None):
+    """rc_ao_pass_device: one ambient-occlusion pass of the camera (eye, m) with the set dirs =
+    (u, tmax) into the state at d_ao_ptr (width * height AO_DTYPE records, device memory): from
+    every primary hit the flipped directions (ao_flip) with the hit shape skipped, counted by
+    ao_step; d_out_ptr (or None): the width * height bytes of ao_byte.  Fast mode only."""
+    cam = _rc_camera(eye, m)
+    d = _rc_ao_dirs(dirs, "ao_pass_device")
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    opt = options(depth, mode)
+    with _timed(timing) as (_, t):
+        _call("rc_ao_pass_device", scene.packed(), ctypes.byref(cam), win, width, height,
+              ctypes.byref(opt), ctypes.byref(d), 1 if reset else 0, ctypes.c_void_p(d_ao_ptr),
+              ctypes.c_void_p(d_out_ptr or 0), _stream(stream_ptr), t)
+
+
+def ao_resolve_device(d_ao_ptr, width, height, d_out_ptr, stream_ptr=None):
+    """rc_ao_resolve_device: the bytes of a state (ao_byte), nothing shot."""
+    _call("rc_ao_resolve_device", ctypes.c_void_p(d_ao_ptr), width, height,
+          ctypes.c_void_p(d_out_ptr), _stream(stream_ptr))
+
+
+def render_ao(scene, eye, m, width, height, sets, window=None, depth=6, device=0, mode="fast",
+              timing=None, out=None):
+    """rc_render_ao: the [H, W] uint8 occlusion plane of the camera (eye, m) after a reset pass
+    with sets[0] and one pass for each further set; `sets` is one (u, tmax) pair or a list of
+    them.  255 is open sky, 0 fully enclosed.  Fast mode only."""
+    single = isinstance(sets, tuple) and len(sets) == 2 and np.ndim(sets[1]) == 0
+    pairs = [sets] if single else list(sets)
+    if not 1 <= len(pairs) <= AO_MAX_SETS:
+        raise ValueError(f"render_ao: {len(pairs)} sets, it takes 1..{AO_MAX_SETS}")
+    arr = (RcAoDirs * len(pairs))(*[_rc_ao_dirs(p, "render_ao") for p in pairs])
+    cam = _rc_camera(eye, m)
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    if out is None:
+        out = np.empty((height, width), dtype=np.uint8)
+    assert out.shape == (height, width) and out.dtype == np.uint8 and out.flags.c_contiguous
+    opt = options(depth, mode, 1, device)
+    with _timed(timing) as (t, _):
+        _call("rc_render_ao", scene.packed(), ctypes.byref(cam), win, width, height,
+              ctypes.byref(opt), arr, len(arr), _host_ptr(out), ctypes.byref(t))
+    return out
+
+
+def ao_stats():
+    """The last occlusion pass on the current device: hit_pixels (unsaturated pixels whose primary
+    ray hit), rays (occlusion rays shot), blocked (of those) and saturated (pixels left as they
+    were)."""
+    return _stats("rc_ao_stats_get", RcAoStats,
+                  "no ambient-occlusion pass has run on the current device")
+
+
+def ao_phase_ms():
+    """The span of the last occlusion call's kernels in ms: {"ao": ...}."""
+    return _phase_ms("rc_ao_phase_ms", ("ao",),
+                     "no ambient-occlusion call has been recorded on the current device")
 
 
 def window_from_env(width, height, mode="fast", ssaa=1, adaptive=0, gpus=1):

@@ -656,6 +656,21 @@ __device__ __forceinline__ bool shadowed(const Scene& sc, V3 O, V3 D, int skip) 
   }
   return false;
 }
+// shadowed with a distance bound (rc_occluded_rays*, rc_ao_pass_device): is any shape but `skip`
+// hit with 0 < t < tmax?  nearest's loop over test_shape with tmax in the place of the best t,
+// stopping at the first accepted shape; no arithmetic of its own.  A tmax that is NaN, <= 0 or
+// -inf accepts nothing.  With tmax = +inf this is shadowed (whose callers take that instead: its
+// quotient classifier decides without the divisions).
+__device__ __forceinline__ bool occluded(const Scene& sc, V3 O, V3 D, int skip, float tmax) {
+  const RayK rk = ray_consts(D);
+  const bool x0 = quad_x0(sc), rej = x0 && x0_reject(O, D);
+  for (int k = 0; k < sc.n; ++k) {
+    float t = 0.0f;
+    const bool hit = test_shape(sc.shapes[k], O, D, rk, skip, t, x0, rej);
+    if (hit && k != skip && tmax > t && t > 0.0f) return true;
+  }
+  return false;
+}
 // Hit point and normal of the accepted shape (C/raycast.c:461-523).
 __device__ __forceinline__ void hit_frame(const Scene& sc, int idx, V3 O, V3 D, float t, V3& P,
                                           V3& N, int& zero_events) {

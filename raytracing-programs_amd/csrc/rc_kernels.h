@@ -345,6 +345,44 @@ hipError_t launch_accum_list_cam(const LaunchScene& s, const CamSet& cams, const
                                  void* acc, uint8_t* out, unsigned long long* zcount,
                                  unsigned* sat, int blocks, hipStream_t stream);
 
+// Any-hit visibility queries and ambient occlusion (rc_occluded_rays*, rc_ao_pass_device,
+// rc_ao_resolve_device, rc_render_ao; fast mode only).
+//   launch_occluded_rays  one lane per ray, n in 1 .. 2^24; origins, dirs: n x 3 floats used as
+//                         given; skip (n ints) and tmax (n floats) may be null: -1 and +inf
+//                         everywhere; out: one byte a ray, 1 blocked.  tmax = +inf takes shadowed,
+//                         anything else occluded (rc_device.hpp), lane by lane;
+//   launch_ao             launch_camera's primary ray at ssaa = 1 (the general nearest at every
+//                         eye), then from a hit the set's n directions, flipped into the normal's
+//                         hemisphere, with skip = the hit shape and the set's tmax; ao: one 4-byte
+//                         record a pixel (open | rays << 16), 4-byte aligned; reset: not read, counts
+//                         as zero; out: W*H bytes or null; stats: kAoStatBytes of counters, zeroed by
+//                         the caller: kAoStatSlots lines of kAoStatStride 64-bit words, the first
+//                         three of a line {hit pixels, blocked rays, saturated pixels}; a wave adds
+//                         to one line with one atomic a counter, and the sums over the lines are
+//                         the pass's counts (one line for all would serialise the pass's waves).
+//                         The set travels by value as a kernel argument (776 bytes) and is read
+//                         with the uniform direction index.  The guards are window_supported's
+//                         at factor 1 and n in 1..64;
+//   launch_ao_resolve     out = the bytes of `ao`, nothing shot (255 where rays = 0).
+// The launchers return hipErrorInvalidValue for what breaks these rules.
+struct AoDirs {
+  int n;
+  float tmax;
+  float u[64][3];
+};
+static_assert(sizeof(AoDirs) == 776, "rc_ao_dirs' layout, one kernel argument");
+constexpr int kAoStatSlots = 256;    // a power of two
+constexpr int kAoStatStride = 16;    // 64-bit words: a 128-byte line a slot
+constexpr size_t kAoStatBytes = (size_t)kAoStatSlots * kAoStatStride * sizeof(unsigned long long);
+hipError_t launch_occluded_rays(const LaunchScene& s, long long n, const float* origins,
+                                const float* dirs, const int* skip, const float* tmax,
+                                uint8_t* out, hipStream_t stream);
+hipError_t launch_ao(const LaunchScene& s, const float eye[3], const View& v, const Window& w,
+                     int W, int H, const AoDirs& dirs, bool reset, void* ao, uint8_t* out,
+                     unsigned long long* zcount, unsigned long long* stats,
+                     hipStream_t stream);
+hipError_t launch_ao_resolve(const void* ao, int W, int H, uint8_t* out, hipStream_t stream);
+
 // ------------------- defined in rc_kernels.hip: the renderer, the parity pipeline, row shards --
 // cuda_sem: RC_MODE_CUDA (the CUDA port's arithmetic, rc_cudasem.hpp) instead of fast mode
 hipError_t launch_render(const LaunchScene& s, int W, int H, int row0, int row_step, int nrows,

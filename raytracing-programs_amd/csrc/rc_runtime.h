@@ -166,7 +166,7 @@ struct Pipe {
 // The sampling features whose frames leave phase spans behind (DevCtx::span_ev).
 enum SpanOwner {
   kSpanAdaptive, kSpanRates, kSpanFilter, kSpanPattern, kSpanAccum, kSpanWindow, kSpanGbuffer,
-  kSpanView, kSpanOwners
+  kSpanView, kSpanAo, kSpanOwners
 };
 
 // The sampling features' frame records.  Each documents the events its rc_*_phase_ms reads out
@@ -248,6 +248,21 @@ struct ViewFrame {
   DevBuf origins;                 // rc_trace_rays_from's second input
 };
 
+// Any-hit visibility and ambient occlusion (rc_ao_pass_device, rc_render_ao, rc_occluded_rays*):
+// `count` is the last pass's counter block (launch_ao's lines, rc::kAoStatBytes), zeroed on the
+// call's stream in front of every pass, so that it holds the last pass's counts; `n`: that pass's
+// directions.
+// The host forms' device copies: rc_render_ao's state and plane, rc_occluded_rays' arrays.
+// Spans: [0] start, [1] end of the call's kernels.
+struct AoFrame {
+  DevBuf count;
+  hipEvent_t done = nullptr;   // behind the call's last pass
+  bool valid = false;          // a pass has been enqueued on this device
+  int n = 0;
+  DevBuf state, plane;
+  DevBuf origins, dirs, skip, tmax, flags;
+};
+
 struct DevCtx {
   bool init = false;
   int device = 0;
@@ -280,6 +295,7 @@ struct DevCtx {
   AccumFrame acc;
   GbufFrame gbuf;      // the G-buffer's host entries
   ViewFrame view;      // rc_trace_rays' arrays
+  AoFrame ao;          // ambient occlusion's last pass and the host forms' arrays
   // The event set whose spans each sampling feature's rc_*_phase_ms may still read, null once
   // another frame has recorded that set anew (claim_event_set).  Which events of the set a
   // feature reads is documented at its record above; window (rc_render_window*): [0] start,

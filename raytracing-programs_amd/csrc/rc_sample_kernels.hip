@@ -42,6 +42,10 @@
 //                 the accumulation passes through free cameras (fast mode): k_accum_win's and
 //                 k_accum_list_win's layout with sample j shot k_camera's way through camera j
 //                 of a kernel argument of up to 16 cameras.
+//   k_ao / k_occluded_rays / k_ao_resolve
+//                 any-hit visibility (fast mode): a camera frame's primary hit and the blocked /
+//                 open count of up to 64 directions around it, added to the caller's per-pixel
+//                 records; a batch of the caller's own rays, one byte each; the records' bytes.
 #include <cstring>
 
 #include "rc_cudasem.hpp"
@@ -2010,6 +2014,194 @@ hipError_t launch_accum_list_cam(const LaunchScene& s, const CamSet& cams, const
                        stream, sc, cam, cams, W, w.x0, w.y0, lg, count, pat, maxrec, list, nlist,
                        (uint2*)acc, out, zcount, sat);
   });
+  return hipGetLastError();
+}
+
+// ------------------- any-hit visibility queries and ambient occlusion (fast) --
+// rc_occluded_rays*, rc_ao_pass_device, rc_ao_resolve_device (include/raycast_hip.h, rc_ao_dirs):
+// the shadow rays' question for rays that are not shade's own.  No new arithmetic: the primary hit
+// is k_camera's (view_dir, the general nearest, hit_frame), the flip is the project's dot and a
+// product with -1.0f, and a ray's answer is shadowed (tmax = +inf) or occluded (rc_device.hpp).
+// No shade, shoot or bounce loop is instantiated.
+//
+// The record is one dword: open | rays << 16 (rc_ao_px's two uint16).
+__device__ __forceinline__ unsigned ao_byte(unsigned rec) {
+  const unsigned open = rec & 0xffffu, rays = rec >> 16;
+  return rays ? (510u * open + rays) / (2u * rays) : 255u;   // 510 * 65535 < 2^25
+}
+
+// the sum of v over the wave, in every lane; called by every lane
+__device__ __forceinline__ unsigned ao_wave_sum(unsigned v) {
+  for (int m = 1; m < 64; m <<= 1) v += (unsigned)__shfl_xor((int)v, m, 64);
+  return v;
+}
+
+// k_ao: k_camera's grid at ssaa = 1 with accum_dense's tiles, one lane a pixel.  The direction
+// loop is the outer loop and its trip count and index are uniform: u_j and tmax are scalar loads
+// from the argument segment (as k_accum_cam reads its cameras), the branch on tmax is uniform, and
+// the lanes of a wave test one direction from neighbouring hit points, so shadowed's and occluded's
+// early exits diverge little.  Per lane: the hit point, the normal, the skip index, the count.
+// ray_consts stays inside shadowed and occluded: it depends on D only through its squares, which
+// the flip does not change, but gfx950 has no scalar floating-point unit to hoist it into, and it
+// is one evaluation a direction beside sc.n shape tests.
+// stats: kAoStatSlots lines of {hit pixels, blocked rays, saturated pixels}; one atomic a wave and
+// counter into the wave's line, none for a wave that has nothing to add (flush_events' manner);
+// the host sums the lines.
+template <bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_ao(
+    Scene sc, Cam cam, View v, Eye e, AoDirs dirs, int W, int H, int ox, int oy, int reset,
+    uint32_t* __restrict__ ao, uint8_t* __restrict__ out, unsigned long long* __restrict__ zcount,
+    unsigned long long* __restrict__ stats) {
+  if (!RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  const V3 eye = v3(e.x, e.y, e.z);
+  __shared__ StageBuf<kStage> stage;
+  __shared__ TileBytes tb;
+  tile_init(tb);
+  stage_scene<kStage>(sc, stage);
+  if (!kStage) __syncthreads();
+  int lx, ly;
+  tile_pixel(lx, ly);
+  int bx, by;
+  xcd_tile<0>(bx, by);
+  const int x0 = bx * kTileW, y0 = by * kTileH;
+  const int x = x0 + lx, y = y0 + ly;
+  const unsigned n = (unsigned)dirs.n;
+  bool saturated = false, hit = false;
+  unsigned blocked = 0u;
+  if (x < W && y < H) {
+    const size_t p = (size_t)y * W + x;
+    unsigned rec = reset ? 0u : ao[p];
+    saturated = (rec >> 16) + n > 65535u;
+    if (!saturated) {
+      int zero = 0;
+      const V3 d = view_dir<false>(cam, v, ox + x, oy + y, zero);
+      float t;
+      const int id = nearest(sc, eye, d, -1, t);
+      hit = id >= 0;
+      V3 P = v3(0.0f, 0.0f, 0.0f), N = P;
+      if (hit) hit_frame(sc, id, eye, d, t, P, N, zero);
+      const bool bounded = dirs.tmax != __builtin_inff();   // uniform
+      for (unsigned j = 0; j < n; ++j) {   // uniform
+        const V3 u = v3(dirs.u[j][0], dirs.u[j][1], dirs.u[j][2]);
+        if (hit) {
+          const V3 D = dot(N, u) < 0.0f ? v3(u.x * -1.0f, u.y * -1.0f, u.z * -1.0f) : u;
+          const bool b = bounded ? occluded(sc, P, D, id, dirs.tmax) : shadowed(sc, P, D, id);
+          blocked += b ? 1u : 0u;
+        }
+      }
+      rec += (n - blocked) + (n << 16);
+      ao[p] = rec;
+      flush_events(zero, zcount);
+    }
+    if (out) {   // uniform
+      const uint8_t byte = (uint8_t)ao_byte(rec);
+      if (RC_TILE_STAGE) ((uint8_t*)tb.cls[ly])[lx] = byte;
+      else out[p] = byte;
+    }
+  }
+  const unsigned hits = (unsigned)__popcll(__ballot(hit));
+  const unsigned sats = (unsigned)__popcll(__ballot(saturated));
+  const unsigned blk = ao_wave_sum(blocked);
+  if ((threadIdx.x & 63) == 0) {
+    // nearly every wave has hits to add, unlike flush_events' and accum_count_saturated's rare
+    // ones: on one address the atomics of a 1024 x 1024 pass cost three times its rays (measured,
+    // DESIGN.md section 27), so the waves are dealt over kAoStatSlots lines
+    const unsigned w = (blockIdx.y * gridDim.x + blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+    unsigned long long* s = stats + (size_t)(w & (kAoStatSlots - 1)) * kAoStatStride;
+    if (hits) atomicAdd(s, (unsigned long long)hits);
+    if (blk) atomicAdd(s + 1, (unsigned long long)blk);
+    if (sats) atomicAdd(s + 2, (unsigned long long)sats);
+  }
+  if (!out || !tile_last_wave(tb)) return;
+  const int nx = W - x0 < kTileW ? W - x0 : kTileW;
+  tile_write_rows<kTileW / 4>(tb.cls, [&](int q) -> uint8_t* {
+    return y0 + q < H ? out + (size_t)(y0 + q) * W + x0 : nullptr;
+  }, nx);
+}
+
+// k_occluded_rays: k_rays_from's loads (two 12-byte strides) and the two optional per-ray words,
+// one byte out a lane.  Nothing per ray is looked at: a NaN, zero or negative tmax takes occluded,
+// which accepts nothing; a skip that names no shape skips nothing and switches the z rule on.  The
+// branch on tmax is per lane.  No normalisation happens here, so there is no zero event to count.
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_occluded_rays(
+    Scene sc, unsigned n, const float* __restrict__ origins, const float* __restrict__ dirs,
+    const int* __restrict__ skip, const float* __restrict__ tmax, uint8_t* __restrict__ out) {
+  if (!RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;
+  const unsigned k = blockIdx.x * (unsigned)kBlock + threadIdx.x;
+  if (k >= n) return;
+  const float* p = dirs + 3 * (size_t)k;
+  const float* q0 = origins + 3 * (size_t)k;
+  const V3 D = v3(p[0], p[1], p[2]);
+  const V3 O = v3(q0[0], q0[1], q0[2]);
+  const int s = skip ? skip[k] : -1;
+  const float tm = tmax ? tmax[k] : __builtin_inff();
+  const bool b = tm == __builtin_inff() ? shadowed(sc, O, D, s) : occluded(sc, O, D, s, tm);
+  out[k] = b ? 1 : 0;
+}
+
+// k_ao_resolve: out = ao_byte of every record, nothing shot: 4 bytes in and 1 out a pixel,
+// memory-bound.  Lane i takes the four records from `head` + 4 i on, 16 bytes in and one aligned
+// dword out (`head`: the pixels in front of out's first 4-byte boundary); with `wide` the 16 bytes
+// are one load (the records there are 16-byte aligned).  The thread behind the last group takes
+// the at most 3 + 3 pixels of the head and the tail one by one.
+__global__ void __launch_bounds__(256) k_ao_resolve(const uint32_t* __restrict__ ao,
+                                                    unsigned long long pixels, unsigned head,
+                                                    unsigned long long groups, int wide,
+                                                    uint8_t* __restrict__ out) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+  if (i < groups) {
+    const uint32_t* a = ao + head + 4 * i;
+    uint4 r;
+    if (wide) r = *(const uint4*)a;   // uniform
+    else r = make_uint4(a[0], a[1], a[2], a[3]);
+    *(uint32_t*)(out + head + 4 * i) =
+        ao_byte(r.x) | (ao_byte(r.y) << 8) | (ao_byte(r.z) << 16) | (ao_byte(r.w) << 24);
+  } else if (i == groups) {
+    for (unsigned long long p = 0; p < head; ++p) out[p] = (uint8_t)ao_byte(ao[p]);
+    for (unsigned long long p = head + 4 * groups; p < pixels; ++p) out[p] = (uint8_t)ao_byte(ao[p]);
+  }
+}
+
+hipError_t launch_occluded_rays(const LaunchScene& s, long long n, const float* origins,
+                                const float* dirs, const int* skip, const float* tmax,
+                                uint8_t* out, hipStream_t stream) {
+  if (n < 1 || n > (1ll << 24) || !origins || !dirs || !out) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+  const Scene sc = make_scene(s);
+  hipLaunchKernelGGL(k_occluded_rays, grid, dim3(kBlock), 0, stream, sc, (unsigned)n, origins,
+                     dirs, skip, tmax, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_ao(const LaunchScene& s, const float eye[3], const View& v, const Window& w,
+                     int W, int H, const AoDirs& dirs, bool reset, void* ao, uint8_t* out,
+                     unsigned long long* zcount, unsigned long long* stats,
+                     hipStream_t stream) {
+  if (!window_supported(w, W, H, 1) || dirs.n < 1 || dirs.n > 64 || !ao || ((uintptr_t)ao & 3u) ||
+      !stats)
+    return hipErrorInvalidValue;
+  dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, w.full_w, w.full_h);
+  const Eye e{eye[0], eye[1], eye[2]};
+  dispatch(stage_fits(s), [&](auto st) {
+    hipLaunchKernelGGL((k_ao<st.value>), grid, dim3(kBlock), 0, stream, sc, cam, v, e, dirs, W, H,
+                       w.x0, w.y0, reset ? 1 : 0, (uint32_t*)ao, out, zcount, stats);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_ao_resolve(const void* ao, int W, int H, uint8_t* out, hipStream_t stream) {
+  if (W <= 0 || H <= 0 || !ao || !out || ((uintptr_t)ao & 3u)) return hipErrorInvalidValue;
+  const unsigned long long pixels = (unsigned long long)W * (unsigned long long)H;
+  unsigned long long head = (4u - ((uintptr_t)out & 3u)) & 3u;
+  if (head > pixels) head = pixels;
+  const unsigned long long groups = (pixels - head) / 4;
+  const unsigned long long blocks = (groups + 1 + 255) / 256;   // one thread more: head and tail
+  if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  const int wide = (((uintptr_t)ao + 4 * head) & 15u) == 0u;
+  hipLaunchKernelGGL(k_ao_resolve, dim3((unsigned)blocks), dim3(256), 0, stream,
+                     (const uint32_t*)ao, pixels, (unsigned)head, groups, wide, out);
   return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // rc_sampling.hip — the sampling features of libraycast_hip.so's C-ABI (include/raycast_hip.h):
 // rate maps, reconstruction filters, sparse sample patterns, progressive accumulation, windows of a
 // virtual image, the primary-visibility G-buffer, rotated views and ray batches, the free camera
-// and rays with origins and accumulation through free cameras, with adaptive
+// and rays with origins, accumulation through free cameras and any-hit visibility queries with the
+// ambient-occlusion pass, with adaptive
 // supersampling's getters.  Host code only: the kernels are
 // rc_sample_kernels.hip's and rc_filter.hip's (the one-ray image is rc_kernels.hip's k_render), the device context and the frame scaffold (enter,
 // ws_frame, claim_event_set, finish_device, finish_host) are rc_api.hip's, through rc_runtime.h.
@@ -318,6 +319,55 @@ static int rates_refused(const char* who, const rc_options* opt, int W, int H) {
     return say("Error: %s: %d x %d is too large for a rate map (32-bit pixel indices at 8 "
                "subsamples a side, at most 65535 rows of tiles)\n", who, W, H);
   }, no_check);
+}
+
+// Any-hit visibility and ambient occlusion: the camera family's mode clauses in their order
+// (parity, num_gpus, cuda), what the entry tests of its sizes in between (image(): rc_window_check
+// for a pass, nothing for a ray batch), then the options' ssaa, which is not decoded: anything but
+// 0 and 1 is refused in one clause, behind the sizes.  The table's other fields stay unused.
+static const Refusal kAoRefusal = {
+    nullptr,
+    1, "Error: %s: ssaa %d in the options: an occlusion query has one primary ray a pixel and one "
+    "sample a ray, leave ssaa at 0 or 1\n",
+    "Error: %s: occlusion queries are for fast mode: a parity image is defined by the scan-order "
+    "carry of the reference's own camera\n",
+    "Error: %s: num_gpus %d: the row shards answer no occlusion query\n",
+    nullptr};   // rc_window_check tests the sizes
+
+template <class Image>
+static int ao_refused(const char* who, const rc_options* opt, Image image) {
+  const Refusal& d = kAoRefusal;
+  if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) return say(d.mode, who);
+  if (opt->num_gpus > 1) return say(d.shards, who, opt->num_gpus);
+  if (camera_mode_refused(who, opt) || image()) return -1;
+  if (opt->ssaa != 0 && opt->ssaa != 1) return say(d.factor, who, opt->ssaa);
+  return 0;
+}
+
+// What rc_ao_dirs_check refuses of a non-null set, as words for the caller's message; null: the
+// set passes.
+static const char* ao_dirs_problem(const rc_ao_dirs* d, char* buf, size_t room) {
+  if (d->n < 1 || d->n > RC_AO_MAX_DIRS) {
+    std::snprintf(buf, room, "n %d is not 1..%d", d->n, RC_AO_MAX_DIRS);
+    return buf;
+  }
+  if (!(d->tmax > 0.0f)) {   // NaN included
+    std::snprintf(buf, room, "tmax %g is not in (0, +inf]", (double)d->tmax);
+    return buf;
+  }
+  for (int j = 0; j < d->n; ++j) {
+    const float* u = d->u[j];
+    for (int k = 0; k < 3; ++k)
+      if (!__builtin_isfinite(u[k])) {
+        std::snprintf(buf, room, "u[%d][%d] is not finite", j, k);
+        return buf;
+      }
+    if (u[0] == 0.0f && u[1] == 0.0f && u[2] == 0.0f) {
+      std::snprintf(buf, room, "u[%d] is the zero vector", j);
+      return buf;
+    }
+  }
+  return nullptr;
 }
 
 // ------------------------------------------- sample lattices: patterns and sequences --
@@ -1147,6 +1197,61 @@ static int enqueue_accum_camera(DevCtx& c, const rc_scene* s, const rc_camera* c
   });
 }
 
+// The passes of one ambient-occlusion call on `stream` through the device's one-frame workspace
+// (the caller holds c.mu and has passed the pass's refusals): one launch of k_ao a set, pass k with
+// sets[k]; the first one resets when `reset`, the last one alone stores the bytes (d_out, or null).
+// The counter block is zeroed in front of every pass, so it holds the last pass's counts and
+// nothing waits for the host.  The set is copied into the launch's argument here.  rays (or null):
+// the call is a ray batch instead, one launch of k_occluded_rays, which counts nothing.
+struct OccludedBatch {
+  long long n;
+  const float *origins, *dirs;
+  const int32_t* skip;
+  const float* tmax;
+  uint8_t* out;
+};
+static int enqueue_ao(DevCtx& c, const rc_scene* s, const rc_camera* cam, const rc_window* vw,
+                      int W, int H, const rc_ao_dirs* sets, int nsets, bool reset, rc_ao_px* d_ao,
+                      uint8_t* d_out, const OccludedBatch* rays, hipStream_t stream) {
+  AoFrame& a = c.ao;
+  auto prepare = [&]() -> int {
+    if (rays) return 0;
+    if (a.count.ensure(rc::kAoStatBytes)) {
+      std::fprintf(stderr, "Error: out of device memory for the occlusion counters\n");
+      return -1;
+    }
+    return ensure_done(a.done);
+  };
+  return ws_frame(c, stream, prepare, [&]() -> int {
+    SampleFrame f{c, stream, kSpanAo};
+    if (rays) {
+      if (f.begin(s, nullptr, 0)) return -1;
+      HIP_TRY(rc::launch_occluded_rays(f.ls, rays->n, rays->origins, rays->dirs, rays->skip,
+                                       rays->tmax, rays->out, stream));
+      return f.end();
+    }
+    a.valid = false;   // the block is this call's from here on
+    if (f.begin(s, &a.count, rc::kAoStatBytes)) return -1;
+    rc::View v;
+    std::memcpy(v.m, cam->view.m, sizeof v.m);
+    const rc::Window win{vw->full_w, vw->full_h, vw->x0, vw->y0};
+    for (int k = 0; k < nsets; ++k) {
+      if (k > 0) HIP_TRY(hipMemsetAsync(a.count.p, 0, rc::kAoStatBytes, stream));
+      rc::AoDirs d;
+      static_assert(sizeof d == sizeof sets[k], "rc_ao_dirs is the kernel's argument");
+      std::memcpy(&d, &sets[k], sizeof d);
+      HIP_TRY(rc::launch_ao(f.ls, cam->eye, v, win, W, H, d, reset && k == 0, d_ao,
+                            k + 1 == nsets ? d_out : nullptr, f.zc,
+                            (unsigned long long*)a.count.p, stream));
+    }
+    if (f.end()) return -1;
+    HIP_TRY(hipEventRecord(a.done, stream));
+    a.valid = true;
+    a.n = sets[nsets - 1].n;
+    return 0;
+  });
+}
+
 // -------------------------------------------------------------- the two entry shapes --
 // A *_device entry behind its null checks and its refusal: on the current device, on the
 // caller's stream or the context's, enqueue(c, st), then finish_device.  plain: the frame goes
@@ -1781,6 +1886,165 @@ int rc_render_camera_accum(const rc_scene* s, const rc_camera* cams, int ncams,
       [&](DevCtx& c) {
         return enqueue_accum_camera(c, s, cams, ncams, &vw, W, H, opt, seq, passes, cam0, np,
                                     (rc_accum_px*)c.accum_px.p, (uint8_t*)c.out.p, c.stream);
+      });
+}
+
+// ------------------------------------- any-hit visibility queries and ambient occlusion --
+int rc_ao_dirs_check(const rc_ao_dirs* dirs) {
+  const char* who = "rc_ao_dirs_check";
+  if (!dirs) return say("Error: %s: a null direction set\n", who);
+  char buf[96];
+  const char* why = ao_dirs_problem(dirs, buf, sizeof buf);
+  return why ? say("Error: %s: %s\n", who, why) : 0;
+}
+
+int rc_ao_stats_get(rc_ao_stats* out) {
+  Entered e;
+  if (!out || enter(kCurrentDevice, false, e) || !e.c->ao.valid) return -1;
+  const AoFrame& a = e.c->ao;
+  HIP_TRY(hipEventSynchronize(a.done));   // the call's stream, up to its last pass
+  unsigned long long lines[rc::kAoStatSlots][rc::kAoStatStride];   // 32 KiB
+  HIP_TRY(hipMemcpy(lines, a.count.p, sizeof lines, hipMemcpyDeviceToHost));
+  unsigned long long n[3] = {0, 0, 0};    // launch_ao's counters, summed over its lines
+  for (const auto& line : lines)
+    for (int k = 0; k < 3; ++k) n[k] += line[k];
+  out->hit_pixels = (int64_t)n[0];
+  out->rays = (int64_t)n[0] * a.n;
+  out->blocked = (int64_t)n[1];
+  out->saturated = (int64_t)n[2];
+  return 0;
+}
+
+int rc_ao_phase_ms(double ms[1]) {
+  Entered e;
+  if (!ms || enter(kCurrentDevice, false, e)) return -1;
+  hipEvent_t* ev = e.c->span_ev[kSpanAo];
+  return ev ? read_spans({ev[0], ev[1]}, ms) : -1;
+}
+
+static int occluded_rays_refused(const char* who, const rc_options* opt, int64_t n) {
+  if (ao_refused(who, opt, [] { return 0; })) return -1;
+  if (n < 1 || n > ((int64_t)1 << 24))
+    return say("Error: %s: n %lld is not 1 .. 2^24 rays\n", who, (long long)n);
+  return 0;
+}
+
+int rc_occluded_rays_device(const rc_scene* s, const rc_options* opt, int64_t n,
+                            const float* d_origins, const float* d_dirs, const int32_t* d_skip,
+                            const float* d_tmax, uint8_t* d_out, void* stream,
+                            rc_timing* timing) {
+  const char* who = "rc_occluded_rays_device";
+  if (!s || !opt || !d_origins || !d_dirs || !d_out) return say("Error: %s: a null pointer\n", who);
+  if (occluded_rays_refused(who, opt, n)) return -1;
+  const OccludedBatch rays{n, d_origins, d_dirs, d_skip, d_tmax, d_out};
+  return device_entry(opt, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_ao(c, s, nullptr, nullptr, 0, 0, nullptr, 0, false, nullptr, nullptr, &rays,
+                      st);
+  });
+}
+
+int rc_occluded_rays(const rc_scene* s, const rc_options* opt, int64_t n, const float* origins,
+                     const float* dirs, const int32_t* skip, const float* tmax, uint8_t* out,
+                     void* /*stream*/, rc_timing* timing) {
+  const char* who = "rc_occluded_rays";
+  if (!s || !opt || !origins || !dirs || !out) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  if (occluded_rays_refused(who, opt, n)) return -1;
+  const size_t n3 = (size_t)n * 3 * sizeof(float), n1 = (size_t)n * 4;
+  return host_entry(
+      opt, 0, 0, nullptr, timing, t0, "Error: out of device memory for the ray batch\n", false,
+      [&](DevCtx& c) {   // device copies of the rays and of the bytes
+        AoFrame& a = c.ao;
+        return a.origins.ensure(n3) || a.dirs.ensure(n3) || (skip && a.skip.ensure(n1)) ||
+               (tmax && a.tmax.ensure(n1)) || a.flags.ensure((size_t)n);
+      },
+      [&](DevCtx& c) -> int {
+        const AoFrame& a = c.ao;
+        auto in = [&](void* dev, const void* host, size_t bytes) -> int {
+          if (host) HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c.stream));
+          return 0;
+        };
+        if (in(a.origins.p, origins, n3) || in(a.dirs.p, dirs, n3) || in(a.skip.p, skip, n1) ||
+            in(a.tmax.p, tmax, n1))
+          return -1;
+        const OccludedBatch rays{n, (const float*)a.origins.p, (const float*)a.dirs.p,
+                                 skip ? (const int32_t*)a.skip.p : nullptr,
+                                 tmax ? (const float*)a.tmax.p : nullptr, (uint8_t*)a.flags.p};
+        if (enqueue_ao(c, s, nullptr, nullptr, 0, 0, nullptr, 0, false, nullptr, nullptr, &rays,
+                       c.stream))
+          return -1;
+        // behind the kernel on c.stream, in front of finish_host's wait
+        HIP_TRY(hipMemcpyAsync(out, a.flags.p, (size_t)n, hipMemcpyDeviceToHost, c.stream));
+        return 0;
+      });
+}
+
+// rc_ao_pass_device and rc_render_ao behind their null checks and the alignment: clauses 3 to 5
+// of the documented order, and the window the pass is shot through (win null: the whole image)
+static int ao_pass_refused(const char* who, const rc_options* opt, const rc_camera* cam,
+                           const rc_window* win, int W, int H, rc_window* vw) {
+  *vw = win ? *win : rc_window{W, H, 0, 0};
+  if (ao_refused(who, opt, [&] { return rc_window_check(vw, W, H, 1); })) return -1;
+  return rc_camera_check(cam);
+}
+
+int rc_ao_pass_device(const rc_scene* s, const rc_camera* cam, const rc_window* win, int W, int H,
+                      const rc_options* opt, const rc_ao_dirs* dirs, int reset, rc_ao_px* d_ao,
+                      uint8_t* d_out, void* stream, rc_timing* timing) {
+  const char* who = "rc_ao_pass_device";
+  if (!s || !cam || !opt || !dirs || !d_ao) return say("Error: %s: a null pointer\n", who);
+  if ((uintptr_t)d_ao & 3u) return say("Error: %s: the state is not 4-byte aligned\n", who);
+  rc_window vw;
+  if (ao_pass_refused(who, opt, cam, win, W, H, &vw) || rc_ao_dirs_check(dirs)) return -1;
+  return device_entry(opt, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_ao(c, s, cam, &vw, W, H, dirs, 1, reset != 0, d_ao, d_out, nullptr, st);
+  });
+}
+
+// No frame of the workspace: the bytes of a state alone, on the current device.
+int rc_ao_resolve_device(const rc_ao_px* d_ao, int W, int H, uint8_t* d_out, void* stream) {
+  const char* who = "rc_ao_resolve_device";
+  if (!d_ao || !d_out) return say("Error: %s: a null pointer\n", who);
+  if ((uintptr_t)d_ao & 3u) return say("Error: %s: the state is not 4-byte aligned\n", who);
+  if (W <= 0 || H <= 0 ||
+      ((unsigned long long)W * (unsigned long long)H / 4 + 256) / 256 > 0x7fffffffull)
+    return say("Error: %s: %d x %d: both sides must be at least 1 and the image within one grid of "
+               "four pixels a lane (about 2^41 pixels)\n", who, W, H);
+  Entered e;
+  if (enter(kCurrentDevice, false, e)) return -1;
+  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
+  HIP_TRY(rc::launch_ao_resolve(d_ao, W, H, d_out, st));
+  return 0;
+}
+
+int rc_render_ao(const rc_scene* s, const rc_camera* cam, const rc_window* win, int W, int H,
+                 const rc_options* opt, const rc_ao_dirs* sets, int nsets, uint8_t* pixmap,
+                 rc_timing* timing) {
+  const char* who = "rc_render_ao";
+  if (!s || !cam || !opt || !sets || !pixmap) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  rc_window vw;
+  if (ao_pass_refused(who, opt, cam, win, W, H, &vw)) return -1;
+  if (nsets < 1 || nsets > 1024)
+    return say("Error: %s: nsets %d is not 1..1024: a reset pass and up to 1023 further ones (a "
+               "record holds 65535 rays)\n", who, nsets);
+  for (int k = 0; k < nsets; ++k) {
+    char buf[96];
+    if (const char* why = ao_dirs_problem(&sets[k], buf, sizeof buf))
+      return say("Error: %s: sets[%d] fails rc_ao_dirs_check: %s\n", who, k, why);
+  }
+  const size_t px = (size_t)W * H;
+  return host_entry(
+      opt, W, H, nullptr, timing, t0,
+      "Error: out of device memory for the occlusion plane and its state (%d x %d)\n", false,
+      [&](DevCtx& c) { return c.ao.state.ensure(px * sizeof(rc_ao_px)) || c.ao.plane.ensure(px); },
+      [&](DevCtx& c) -> int {
+        if (enqueue_ao(c, s, cam, &vw, W, H, sets, nsets, true, (rc_ao_px*)c.ao.state.p,
+                       (uint8_t*)c.ao.plane.p, nullptr, c.stream))
+          return -1;
+        // behind the last pass on c.stream, in front of finish_host's wait
+        HIP_TRY(hipMemcpyAsync(pixmap, c.ao.plane.p, px, hipMemcpyDeviceToHost, c.stream));
+        return 0;
       });
 }
 
