@@ -29,7 +29,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -Wno-c11-extensions -Wno-unused-result
 CFLAGS   := -O3 -ffp-contract=off -fPIC -Wall -Wno-unused-result -Iinclude -I$(SRC)
 
-HIP_SRCS  := $(SRC)/rc_kernels.hip $(SRC)/rc_sample_kernels.hip $(SRC)/rc_api.hip $(SRC)/rc_sampling.hip $(SRC)/rc_shard.hip $(SRC)/rc_filter.hip
+HIP_SRCS  := $(SRC)/rc_kernels.hip $(SRC)/rc_sample_kernels.hip $(SRC)/rc_api.hip $(SRC)/rc_sampling.hip $(SRC)/rc_shard.hip $(SRC)/rc_filter.hip $(SRC)/rc_guided.hip
 HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_pixel.hpp $(SRC)/rc_resolve.hpp $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
 FRONT_SRC := $(SRC)/front/parse.c $(SRC)/front/objects.c $(SRC)/front/ppm.c
 
@@ -50,7 +50,7 @@ HIPLIBS := -L$(ROCM)/lib -lrccl -Wl,-rpath,$(ROCM)/lib -lpthread
 # variants' -D options (RC_STAMPS and RC_DIAG reach rc_kernels.hip and rc_api.hip only, the kernels'
 # -D options rc_kernels.hip only: the render, parity and phase C kernels), so the sampling kernels
 # of every variant are the product's
-PLAIN_OBJS := $(OBJ)/rc_sample_kernels.o $(OBJ)/rc_sampling.o $(OBJ)/rc_shard.o $(OBJ)/rc_filter.o $(OBJ)/rc_scene.o
+PLAIN_OBJS := $(OBJ)/rc_sample_kernels.o $(OBJ)/rc_sampling.o $(OBJ)/rc_shard.o $(OBJ)/rc_filter.o $(OBJ)/rc_guided.o $(OBJ)/rc_scene.o
 
 $(LIB)/libraycast_hip.so: $(OBJ)/rc_kernels.o $(OBJ)/rc_api.o $(PLAIN_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ $(HIPLIBS)
@@ -118,6 +118,15 @@ $(OBJ)/camtable_sample_kernels.o: $(SRC)/rc_sample_kernels.hip $(HIP_HDRS)
 $(OBJ)/camgen_sample_kernels.o: $(SRC)/rc_sample_kernels.hip $(HIP_HDRS)
 	$(HIPCC) $(HIPFLAGS) -DRC_CAMERA_TABLE=0 -c $< -o $@
 $(LIB)/libraycast_hip_cam%.so: $(OBJ)/rc_kernels.o $(OBJ)/rc_api.o $(OBJ)/cam%_sample_kernels.o $(filter-out $(OBJ)/rc_sample_kernels.o,$(PLAIN_OBJS))
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ $(HIPLIBS)
+
+# measurement variant of k_ao_filter (scripts/ao_filter_ab.py): the neighbours read from global
+# memory through the caches (aofdirect) against the product's LDS-staged tile; every other kernel
+# is the product's
+filter-variants: $(LIB)/libraycast_hip_aofdirect.so
+$(OBJ)/aofdirect_guided.o: $(SRC)/rc_guided.hip $(HIP_HDRS)
+	$(HIPCC) $(HIPFLAGS) -DRC_AO_FILTER_DIRECT=1 -c $< -o $@
+$(LIB)/libraycast_hip_aofdirect.so: $(OBJ)/rc_kernels.o $(OBJ)/rc_api.o $(OBJ)/aofdirect_guided.o $(filter-out $(OBJ)/rc_guided.o,$(PLAIN_OBJS))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $^ -o $@ $(HIPLIBS)
 
 # ASan + UBSan builds of the host C (tests/test_sanitize.py; SURVEY.md §5: the CPU restatement

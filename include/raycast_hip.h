@@ -1044,8 +1044,9 @@ int rc_render_camera_accum(const rc_scene *scene, const rc_camera *cams, int nca
  *          that fails, named by its index).
  *     rc_ao_resolve_device: a null pointer, a misaligned d_ao, W or H below 1 or an image past
  *     one grid.
- * Out of scope: cosine or per-direction weights; supersampled primary rays; multiplying the plane
- *     into a colour image; cuda and parity mode; multi-GPU. */
+ * Out of scope: cosine or per-direction weights; supersampled primary rays; cuda and parity mode;
+ *     multi-GPU.  Filtering the plane and adding it to a colour image are rc_ao_filter_device and
+ *     rc_ao_compose_device, below. */
 #define RC_AO_MAX_DIRS 64
 typedef struct rc_ao_px { uint16_t open, rays; } rc_ao_px;
 typedef struct rc_ao_dirs { int32_t n; float tmax; float u[RC_AO_MAX_DIRS][3]; } rc_ao_dirs;
@@ -1071,6 +1072,103 @@ int rc_render_ao(const rc_scene *scene, const rc_camera *cam, const rc_window *w
                  uint8_t *pixmap /* W*H bytes */, rc_timing *timing);
 int rc_ao_stats_get(rc_ao_stats *out);
 int rc_ao_phase_ms(double ms[1]);
+
+/* The G-buffer through a camera, the guided filter of the occlusion records and the ambient
+ * compose (rc_render_camera_gbuffer, rc_render_camera_gbuffer_device, rc_ao_filter_device,
+ * rc_ao_compose_device, rc_render_ambient; fast mode).  What turns the occlusion plane above into
+ * part of a picture: the guide for a moved eye, an edge-aware blur of the records that pools
+ * neighbouring pixels of the same surface, and an ambient term modulated by the result.
+ * rc_render_camera_gbuffer*: step 1 of rc_ao_pass_device, stored.  For window pixel (x, y) the
+ *     direction d is rc_render_camera's at ssaa = 1 (the view contract's), and
+ *     (id, t, P, N) = rco_prim_nearest(cam->eye, d, skip = -1, shadow = 0) and its frame; the
+ *     general scan is used at every eye, +0 included.  The planes are rc_gbuffer's, any may be
+ *     null; a miss is id = -1 and +0.0f everywhere else; every stored float is bit-identical to
+ *     the oracle's.  zero_normalize counts as in rc_render_gbuffer (the normal's events only when
+ *     P or N is asked for).  The two entries take the same arguments as rc_render_gbuffer*'s with
+ *     the camera in front of the window.
+ *     Refused, in this order: 1. a null scene, camera, options or planes struct; 2. all four
+ *     planes null; 3. the camera family's mode clauses (parity mode, num_gpus > 1, cuda mode), then
+ *     what rc_window_check refuses at factor 1; 4. an opt->ssaa other than 0 or 1; 5. what
+ *     rc_camera_check refuses.
+ * rc_ao_filter: the pooling window and its thresholds, by value (32 bytes).  radius 0..8 (0 pools
+ *     nothing), taps[|d|] for d = 0..radius, pad = 0.  rc_ao_filter_box (taps 1) and
+ *     rc_ao_filter_tent (taps[d] = radius + 1 - d) fill one with nmin = 0.9f, dplane = 0.05f.
+ *     rc_ao_filter_check: 0, or one message and -1 for, in this order: 1. a null struct; 2. a
+ *     radius outside 0..8; 3. pad != 0; 4. taps[0] == 0; 5. (taps[0] + 2 * sum taps[1..radius])^2
+ *     > 32768; 6. an nmin that is NaN; 7. a dplane that is NaN or negative.  With clause 5 the
+ *     sums below stay under 2^31 (32768 * 65535 < 2^31).  nmin = -inf with dplane = +inf pools
+ *     every neighbour of the same id; nmin = 2 pools nothing.
+ * rc_ao_filter_device: the rule, for p = (x, y) and every q = (x + dx, y + dy) with |dx|, |dy| <=
+ *     radius inside the W x H plane; every float operation is one float32 operation in this
+ *     order, nothing contracted:
+ *         e         = P_q - P_p                                   (componentwise)
+ *         pd        = (N_p[0]*e[0] + N_p[1]*e[1]) + N_p[2]*e[2]   (the oracle's dot)
+ *         nd        = (N_p[0]*N_q[0] + N_p[1]*N_q[1]) + N_p[2]*N_q[2]
+ *         accept(q) = q == p or (id_q == id_p and nd >= nmin and fabsf(pd) <= dplane)
+ *         w(q)      = taps[|dx|] * taps[|dy|]
+ *         O = sum over accepted q of w(q) * open_q     R = sum over accepted q of w(q) * rays_q
+ *         out[p]    = id_p < 0 ? rc_ao_byte(open_p, rays_p) : (R ? (510*O + R) / (2*R) : 255)
+ *     A comparison with a NaN is false, so such a q is rejected; the centre is always accepted, so
+ *     a pixel that stands alone keeps its own byte; a miss (id_p < 0) keeps its own byte and is
+ *     pooled into nothing.  Guide and records are data (device memory: d_ao W*H records, 4-byte
+ *     aligned; the guide's id, P and N planes, t is not read) and are not inspected; records with
+ *     open > rays are outside the contract (no fault, the byte is unspecified).  The plane has no
+ *     window: a window's filtered plane is not the crop of the whole image's, because the pixels
+ *     next to the window's edge pool neighbours outside it; a tiling caller supplies its own halo
+ *     (filter a window grown by `radius` and keep the middle).  No scene and no workspace, like
+ *     rc_ao_resolve_device; d_out: W*H bytes of any alignment.
+ *     Refused, in this order: 1. a null d_ao, guide, filter or d_out; 2. a guide without id, P or
+ *     N; 3. a d_ao that is not 4-byte aligned; 4. W or H below 1; 5. an image past one grid (a
+ *     side above 16 * 65535); 6. what rc_ao_filter_check refuses.
+ * rc_ao_compose_device: with a[k][c] = quant(ambient[c] * diffuse_color_k[c]) for shape k and
+ *     channel c (one float32 product, then rco_prim_quant), a pixel with 0 <= id < n_shapes gets
+ *         out[c] = min(255, in[c] + (a[id][c] * ao + 127) / 255)     in integers,
+ *     and any other id leaves out = in.  d_id: W*H int32; d_ao: W*H bytes (a filtered or a plain
+ *     plane); d_rgb_in, d_rgb_out: W*H*3 bytes of any alignment, equal or disjoint.
+ *     Refused, in this order: 1. a null pointer; 2. parity mode, num_gpus > 1, cuda mode; 3. an
+ *     ambient component that is not finite or is negative; 4. W or H below 1; 5. an image past
+ *     one grid.
+ * rc_render_ambient: the host form, synchronous on opt->device, everything on the library's
+ *     stream with state and planes owned by the library: rc_render_camera at ssaa = 1,
+ *     rc_render_ao's passes (a reset pass, then one pass a further set), the camera's G-buffer,
+ *     the filter, the compose, one copy out.  Its image is by definition the composition of the
+ *     device entries above.  timing covers all its kernels, zero_normalize their sum;
+ *     rc_ao_stats_get reads its last pass.  Refused, in this order: a null pointer (win may be
+ *     null); what rc_render_ao refuses; an image past one grid; what rc_ao_filter_check refuses;
+ *     the compose's ambient clause.
+ * Out of scope: iterated (a-trous) passes and a record output of the filter; cosine or
+ *     per-direction weights; filtering colours; cuda and parity mode; multi-GPU; a RAYCAST_*
+ *     variable or CLI format for any of it. */
+#define RC_AO_FILTER_MAX_RADIUS 8
+typedef struct rc_ao_filter {
+  int32_t  radius;                              /* 0 .. 8; 0 pools nothing                    */
+  float    nmin;                                /* accept q when dot(N_p, N_q) >= nmin        */
+  float    dplane;                              /* ... and |dot(N_p, P_q - P_p)| <= dplane    */
+  uint16_t taps[RC_AO_FILTER_MAX_RADIUS + 1];   /* taps[|d|], d = 0 .. radius                 */
+  uint16_t pad;                                 /* 0                                          */
+} rc_ao_filter;                                 /* 32 bytes, by value, a kernel argument      */
+_Static_assert(sizeof(rc_ao_filter) == 32, "rc_ao_filter layout (a kernel argument, ctypes binding)");
+int rc_render_camera_gbuffer(const rc_scene *scene, const rc_camera *cam, const rc_window *win,
+                             int width, int height, const rc_options *opt,
+                             const rc_gbuffer *planes, rc_timing *timing);
+int rc_render_camera_gbuffer_device(const rc_scene *scene, const rc_camera *cam,
+                                    const rc_window *win, int width, int height,
+                                    const rc_options *opt, const rc_gbuffer *d_planes,
+                                    void *stream, rc_timing *timing);
+int rc_ao_filter_box(int radius, rc_ao_filter *out);    /* taps 1                    */
+int rc_ao_filter_tent(int radius, rc_ao_filter *out);   /* taps[d] = radius + 1 - d  */
+int rc_ao_filter_check(const rc_ao_filter *f);
+int rc_ao_filter_device(const rc_ao_px *d_ao, const rc_gbuffer *d_guide /* id, P, N non-null */,
+                        int width, int height, const rc_ao_filter *f, uint8_t *d_out /* W*H */,
+                        void *stream);
+int rc_ao_compose_device(const rc_scene *scene, const rc_options *opt, const int32_t *d_id,
+                         const uint8_t *d_ao /* W*H */, const float ambient[3],
+                         const uint8_t *d_rgb_in, uint8_t *d_rgb_out /* may equal d_rgb_in */,
+                         int width, int height, void *stream);
+int rc_render_ambient(const rc_scene *scene, const rc_camera *cam, const rc_window *win, int width,
+                      int height, const rc_options *opt, const rc_ao_dirs *sets, int nsets,
+                      const rc_ao_filter *filter, const float ambient[3],
+                      uint8_t *pixmap /* W*H*3 */, rc_timing *timing);
 
 /* Frames in flight(an extension for rendering frame sequences; no reference
  * counterpart).  rc_frame_submit enqueues one whole W x H image of `scene` into d_out

@@ -215,6 +215,18 @@ class RcAoStats(ctypes.Structure):
 AO_DTYPE = np.dtype([("open", np.uint16), ("rays", np.uint16)])
 assert ctypes.sizeof(RcAoDirs) == 776 and AO_DTYPE.itemsize == 4
 
+AO_FILTER_MAX_RADIUS = 8      # the guided filter pools up to 17 x 17 neighbours
+AO_FILTER_MAX_WEIGHT = 32768  # the weights of one window sum to this at most
+
+
+class RcAoFilter(ctypes.Structure):
+    """rc_ao_filter (32 bytes): the pooling window's radius, the two thresholds and taps[|d|]."""
+    _fields_ = [("radius", ctypes.c_int32), ("nmin", ctypes.c_float), ("dplane", ctypes.c_float),
+                ("taps", ctypes.c_uint16 * (AO_FILTER_MAX_RADIUS + 1)), ("pad", ctypes.c_uint16)]
+
+
+assert ctypes.sizeof(RcAoFilter) == 32
+
 
 def _hier_points(g):
     """hier<g> (include/raycast_hip.h, rc_sample_seq): point k is the bit-reversal r of k over
@@ -324,7 +336,10 @@ HIP_EXPORTS = ["raycast", "rc_default_options", "rc_scene_create", "rc_scene_des
                "rc_trace_rays_from_device", "rc_accum_pass_camera_device",
                "rc_render_camera_accum", "rc_ao_dirs_check", "rc_occluded_rays",
                "rc_occluded_rays_device", "rc_ao_pass_device", "rc_ao_resolve_device",
-               "rc_render_ao", "rc_ao_stats_get", "rc_ao_phase_ms"]
+               "rc_render_ao", "rc_ao_stats_get", "rc_ao_phase_ms", "rc_render_camera_gbuffer",
+               "rc_render_camera_gbuffer_device", "rc_ao_filter_box", "rc_ao_filter_tent",
+               "rc_ao_filter_check", "rc_ao_filter_device", "rc_ao_compose_device",
+               "rc_render_ambient"]
 FRONT_EXPORTS = ["add_new_sphere", "add_new_plane", "add_new_quadric", "free_shape_list",
                  "free_light_list", "add_new_spot_light", "add_new_point_light", "parse_json",
                  "set_to_black", "ppm_WriteOutP3", "ppm_clamp"]
@@ -593,6 +608,32 @@ def _hip_lib_locked():
                                  ctypes.c_void_p, ctypes.POINTER(RcTiming)]
     lib.rc_ao_stats_get.argtypes = [ctypes.POINTER(RcAoStats)]
     lib.rc_ao_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    lib.rc_render_camera_gbuffer.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcCamera),
+                                             ctypes.POINTER(RcWindow), ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(RcOptions), ctypes.POINTER(RcGbuffer),
+                                             ctypes.POINTER(RcTiming)]
+    lib.rc_render_camera_gbuffer_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcCamera),
+                                                    ctypes.POINTER(RcWindow), ctypes.c_int,
+                                                    ctypes.c_int, ctypes.POINTER(RcOptions),
+                                                    ctypes.POINTER(RcGbuffer), ctypes.c_void_p,
+                                                    ctypes.POINTER(RcTiming)]
+    for name in ("rc_ao_filter_box", "rc_ao_filter_tent"):
+        getattr(lib, name).argtypes = [ctypes.c_int, ctypes.POINTER(RcAoFilter)]
+    lib.rc_ao_filter_check.argtypes = [ctypes.POINTER(RcAoFilter)]
+    lib.rc_ao_filter_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcGbuffer), ctypes.c_int,
+                                        ctypes.c_int, ctypes.POINTER(RcAoFilter), ctypes.c_void_p,
+                                        ctypes.c_void_p]
+    lib.rc_ao_compose_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcOptions),
+                                         ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.POINTER(ctypes.c_float), ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_void_p]
+    lib.rc_render_ambient.argtypes = [ctypes.c_void_p, ctypes.POINTER(RcCamera),
+                                      ctypes.POINTER(RcWindow), ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(RcOptions), ctypes.POINTER(RcAoDirs),
+                                      ctypes.c_int, ctypes.POINTER(RcAoFilter),
+                                      ctypes.POINTER(ctypes.c_float), ctypes.c_void_p,
+                                      ctypes.POINTER(RcTiming)]
     _hip = lib
     return lib
 
@@ -1617,6 +1658,39 @@ def render_gbuffer_device(scene, width, height, window=None, d_id_ptr=None, d_t_
               ctypes.byref(g), _stream(stream_ptr), t)
 
 
+def render_camera_gbuffer(scene, eye, m, width, height, planes=("id", "t"), window=None,
+                          mode="fast", device=0, timing=None):
+    """rc_render_camera_gbuffer: render_gbuffer through the camera (eye, m): the primary hit of
+    render_camera's rays at ssaa = 1, the general scan from the eye, as a dict of numpy arrays, one
+    per requested plane.  Fast mode only."""
+    names = _plane_names(planes)
+    out = {p: np.empty((height, width) + ((3,) if GBUFFER_PLANES[p][1] == 3 else ()),
+                       dtype=GBUFFER_PLANES[p][0]) for p in names}
+    g = RcGbuffer(**{p: a.ctypes.data for p, a in out.items()})
+    cam = _rc_camera(eye, m)
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    opt = options(0, mode, 1, device)
+    with _timed(timing) as (t, _):
+        _call("rc_render_camera_gbuffer", scene.packed(), ctypes.byref(cam), win, width, height,
+              ctypes.byref(opt), ctypes.byref(g), ctypes.byref(t))
+    return out
+
+
+def render_camera_gbuffer_device(scene, eye, m, width, height, window=None, d_id_ptr=None,
+                                 d_t_ptr=None, d_p_ptr=None, d_n_ptr=None, stream_ptr=None,
+                                 mode="fast", timing=None):
+    """rc_render_camera_gbuffer_device: the planes are device memory (W*H int32, W*H float32,
+    W*H*3 float32 twice), None for a plane that is not wanted; enqueued on the stream and
+    asynchronous unless `timing` is given."""
+    g = RcGbuffer(d_id_ptr or None, d_t_ptr or None, d_p_ptr or None, d_n_ptr or None)
+    cam = _rc_camera(eye, m)
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    opt = options(0, mode)
+    with _timed(timing) as (_, t):
+        _call("rc_render_camera_gbuffer_device", scene.packed(), ctypes.byref(cam), win, width,
+              height, ctypes.byref(opt), ctypes.byref(g), _stream(stream_ptr), t)
+
+
 def _pick_points(xy):
     xy = np.asarray(xy)
     if xy.ndim != 2 or xy.shape[1] != 2 or xy.dtype.kind not in "iu":
@@ -2206,6 +2280,154 @@ def ao_phase_ms():
     """The span of the last occlusion call's kernels in ms: {"ao": ...}."""
     return _phase_ms("rc_ao_phase_ms", ("ao",),
                      "no ambient-occlusion call has been recorded on the current device")
+
+
+def ao_filter_params(radius, taps="tent", nmin=0.9, dplane=0.05):
+    """An RcAoFilter: `taps` is "tent" (taps[d] = radius + 1 - d, rc_ao_filter_tent), "box" (taps 1,
+    rc_ao_filter_box) or a sequence of radius + 1 integers taps[|d|]; nmin and dplane are the two
+    thresholds of ao_filter's rule.  The library checks the values (ao_filter_check)."""
+    radius = int(radius)
+    if not 0 <= radius <= AO_FILTER_MAX_RADIUS:
+        raise ValueError(f"ao_filter_params: radius {radius} is not 0..{AO_FILTER_MAX_RADIUS}")
+    f = RcAoFilter()
+    if isinstance(taps, str):
+        if taps not in ("tent", "box"):
+            raise ValueError(f"ao_filter_params: taps {taps!r} is not 'tent', 'box' or a sequence")
+        make = "rc_ao_filter_tent" if taps == "tent" else "rc_ao_filter_box"
+        _call(make, radius, ctypes.byref(f))
+    else:
+        k = [int(v) for v in taps]
+        if len(k) != radius + 1 or any(not 0 <= v <= 65535 for v in k):
+            raise ValueError(f"ao_filter_params: taps is radius + 1 = {radius + 1} values in "
+                             f"0..65535, got {k}")
+        f.radius = radius
+        for d, v in enumerate(k):
+            f.taps[d] = v
+    f.nmin, f.dplane = float(nmin), float(dplane)
+    return f
+
+
+def ao_filter_check(params):
+    """rc_ao_filter_check: True when the library takes the filter (its message goes to stderr
+    otherwise)."""
+    return hip_lib().rc_ao_filter_check(ctypes.byref(params)) == 0
+
+
+def ao_filter(acc, ids, P, N, params):
+    """rc_ao_filter_device's rule in numpy: the [H, W] uint8 plane of the state acc ([H, W] of
+    AO_DTYPE) pooled over the (2 radius + 1)^2 window under the guide ids [H, W] int32, P and N
+    [H, W, 3] float32.  Pixel q is pooled into p when q == p, or id_q == id_p and, in float32 in
+    this order, nd = (Np0 Nq0 + Np1 Nq1) + Np2 Nq2 >= nmin and |pd| <= dplane with e = P_q - P_p,
+    pd = (Np0 e0 + Np1 e1) + Np2 e2; its weight is taps[|dx|] taps[|dy|]; the byte is
+    (510 O + R) // (2 R) of the weighted sums of open and rays (255 where R is 0), and ao_byte of
+    the pixel's own record where id_p < 0.  Vectorised over the offsets, int64 sums."""
+    acc = _ao_state(acc)
+    h, w = acc.shape
+    ids = np.asarray(ids)
+    P, N = np.asarray(P), np.asarray(N)
+    if ids.shape != (h, w) or ids.dtype != np.int32 or P.shape != (h, w, 3) or \
+            N.shape != (h, w, 3) or P.dtype != np.float32 or N.dtype != np.float32:
+        raise ValueError(f"ao_filter: ids int32 {(h, w)}, P and N float32 {(h, w, 3)} like the "
+                         f"state, got {ids.dtype} {ids.shape}, {P.dtype} {P.shape}, {N.dtype} "
+                         f"{N.shape}")
+    r = int(params.radius)
+    taps = [int(params.taps[d]) for d in range(r + 1)]
+    nmin, dplane = np.float32(params.nmin), np.float32(params.dplane)
+    opn, rays = acc["open"].astype(np.int64), acc["rays"].astype(np.int64)
+    O, R = np.zeros((h, w), np.int64), np.zeros((h, w), np.int64)
+    with np.errstate(all="ignore"):
+        for dy in range(-r, r + 1):
+            ya, yb = max(0, -dy), min(h, h - dy)          # rows of p whose q is inside
+            if ya >= yb:
+                continue
+            for dx in range(-r, r + 1):
+                xa, xb = max(0, -dx), min(w, w - dx)
+                if xa >= xb:
+                    continue
+                ps = (slice(ya, yb), slice(xa, xb))
+                qs = (slice(ya + dy, yb + dy), slice(xa + dx, xb + dx))
+                if dx == 0 and dy == 0:
+                    ok = np.ones((yb - ya, xb - xa), bool)
+                else:
+                    Np, Nq, e = N[ps], N[qs], P[qs] - P[ps]
+                    nd = (Np[..., 0] * Nq[..., 0] + Np[..., 1] * Nq[..., 1]) + Np[..., 2] * Nq[..., 2]
+                    pd = (Np[..., 0] * e[..., 0] + Np[..., 1] * e[..., 1]) + Np[..., 2] * e[..., 2]
+                    ok = (ids[qs] == ids[ps]) & (nd >= nmin) & (np.abs(pd) <= dplane)
+                wgt = taps[abs(dx)] * taps[abs(dy)]
+                O[ps] += np.where(ok, wgt * opn[qs], 0)
+                R[ps] += np.where(ok, wgt * rays[qs], 0)
+    pooled = np.where(R > 0, (510 * O + R) // np.maximum(2 * R, 1), 255)
+    return np.where(ids < 0, ao_byte(acc), pooled).astype(np.uint8)
+
+
+def ao_filter_device(d_ao_ptr, d_id_ptr, d_P_ptr, d_N_ptr, width, height, params, d_out_ptr,
+                     stream_ptr=None):
+    """rc_ao_filter_device: ao_filter of the state at d_ao_ptr under the guide planes at d_id_ptr,
+    d_P_ptr and d_N_ptr (all width x height, device memory) into the width * height bytes at
+    d_out_ptr; no scene, enqueued on the stream."""
+    g = RcGbuffer(d_id_ptr or None, None, d_P_ptr or None, d_N_ptr or None)
+    _call("rc_ao_filter_device", ctypes.c_void_p(d_ao_ptr), ctypes.byref(g), width, height,
+          ctypes.byref(params), ctypes.c_void_p(d_out_ptr), _stream(stream_ptr))
+
+
+def ao_compose(rgb, ids, ao, table):
+    """rc_ao_compose_device's integer step in numpy: out[c] = min(255, rgb[c] + (table[id][c] * ao +
+    127) // 255) where 0 <= id < len(table), rgb elsewhere.  rgb [H, W, 3] uint8, ids [H, W] int32,
+    ao [H, W] uint8, table [n_shapes, 3] uint8 (quant(ambient[c] * diffuse_color_k[c]))."""
+    rgb, ids, ao = np.asarray(rgb), np.asarray(ids), np.asarray(ao)
+    table = np.asarray(table)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or ids.shape != rgb.shape[:2] or \
+            ao.shape != ids.shape or ao.dtype != np.uint8 or table.dtype != np.uint8 or \
+            table.ndim != 2 or table.shape[1] != 3:
+        raise ValueError(f"ao_compose: rgb [H, W, 3] uint8, ids [H, W], ao [H, W] uint8 and table "
+                         f"[n, 3] uint8, got {rgb.shape}, {ids.shape}, {ao.shape}, {table.shape}")
+    ids = ids.astype(np.int64)
+    known = (ids >= 0) & (ids < len(table))
+    if len(table) == 0:
+        return rgb.copy()
+    a = table[np.where(known, ids, 0)].astype(np.int64)
+    add = (a * ao.astype(np.int64)[..., None] + 127) // 255
+    out = np.minimum(255, rgb.astype(np.int64) + add)
+    return np.where(known[..., None], out, rgb).astype(np.uint8)
+
+
+def _ambient(ambient, what):
+    a = np.asarray(ambient, dtype=np.float32)
+    if a.shape != (3,):
+        raise ValueError(f"{what}: ambient is three floats, got shape {a.shape}")
+    return (ctypes.c_float * 3)(*a.tolist())
+
+
+def ao_compose_device(scene, d_id_ptr, d_ao_ptr, ambient, d_rgb_in_ptr, d_rgb_out_ptr, width,
+                      height, stream_ptr=None, mode="fast"):
+    """rc_ao_compose_device: ao_compose with the table of `scene` and `ambient` (three floats,
+    finite, not negative) on device planes; d_rgb_out_ptr may equal d_rgb_in_ptr."""
+    opt = options(0, mode)
+    _call("rc_ao_compose_device", scene.packed(), ctypes.byref(opt), ctypes.c_void_p(d_id_ptr),
+          ctypes.c_void_p(d_ao_ptr), _ambient(ambient, "ao_compose_device"),
+          ctypes.c_void_p(d_rgb_in_ptr), ctypes.c_void_p(d_rgb_out_ptr), width, height,
+          _stream(stream_ptr))
+
+
+def render_ambient(scene, eye, m, width, height, sets, params, ambient, window=None, depth=6,
+                   device=0, mode="fast", timing=None, out=None):
+    """rc_render_ambient: render_camera's [H, W, 3] image at ssaa = 1 plus the ambient term:
+    render_ao's passes with `sets`, the camera's G-buffer, ao_filter with `params` and ao_compose
+    with `ambient`, all on the device.  Fast mode only."""
+    single = isinstance(sets, tuple) and len(sets) == 2 and np.ndim(sets[1]) == 0
+    pairs = [sets] if single else list(sets)
+    if not 1 <= len(pairs) <= AO_MAX_SETS:
+        raise ValueError(f"render_ambient: {len(pairs)} sets, it takes 1..{AO_MAX_SETS}")
+    arr = (RcAoDirs * len(pairs))(*[_rc_ao_dirs(p, "render_ambient") for p in pairs])
+    cam = _rc_camera(eye, m)
+    win = None if window is None else ctypes.byref(_rc_window(window))
+    out = _pixmap(out, width, height)
+    opt = options(depth, mode, 1, device)
+    with _timed(timing) as (t, _):
+        _call("rc_render_ambient", scene.packed(), ctypes.byref(cam), win, width, height,
+              ctypes.byref(opt), arr, len(arr), ctypes.byref(params),
+              _ambient(ambient, "render_ambient"), _host_ptr(out), ctypes.byref(t))
+    return out
 
 
 def window_from_env(width, height, mode="fast", ssaa=1, adaptive=0, gpus=1):

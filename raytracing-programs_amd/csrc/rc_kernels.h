@@ -1,6 +1,7 @@
 // rc_kernels.h — launch interface between the host runtime (rc_api.hip, rc_sampling.hip,
 // rc_shard.hip) and the kernels: the sampling family's launchers (rc_sample_kernels.hip, and
-// rc_filter.hip's one) first, then the renderer's and the parity pipeline's (rc_kernels.hip).
+// rc_filter.hip's one and rc_guided.hip's two) first, then the renderer's and the parity
+// pipeline's (rc_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -382,6 +383,40 @@ hipError_t launch_ao(const LaunchScene& s, const float eye[3], const View& v, co
                      unsigned long long* zcount, unsigned long long* stats,
                      hipStream_t stream);
 hipError_t launch_ao_resolve(const void* ao, int W, int H, uint8_t* out, hipStream_t stream);
+
+// The G-buffer through a camera, the guided filter of the occlusion records and the ambient
+// compose (rc_render_camera_gbuffer*, rc_ao_filter_device, rc_ao_compose_device; fast mode only).
+//   launch_camera_gbuffer  launch_ao's primary ray, stored: id, t, P, N of the general nearest from
+//                          `eye` and its hit_frame, a null plane is not stored, a miss is id -1 and
+//                          +0 everywhere else (rc_sample_kernels.hip);
+//   launch_ao_filter       out = the cross-bilateral pooling of the records `ao` (launch_ao's
+//                          dwords, 4-byte aligned) guided by id, P (3 W floats a row) and N, all
+//                          W x H and non-null; no scene (rc_guided.hip).  The filter travels by
+//                          value (32 bytes).  The guards: radius 0..kAoFilterMaxRadius, both sides
+//                          1 .. kGuidedMaxSide (one workgroup a 16 x 16 tile, grid.y <= 65535);
+//   launch_ao_compose      out = in + the ambient term of the pixel's shape scaled by ao / 255,
+//                          saturated; diffuse: n x 3 floats of the uploaded scene; out may be in.
+// hipErrorInvalidValue for what breaks these rules.
+constexpr int kAoFilterMaxRadius = 8;
+constexpr int kGuidedMaxSide = 16 * 65535;
+struct AoFilter {
+  int radius;
+  float nmin, dplane;
+  uint16_t taps[kAoFilterMaxRadius + 1];
+  uint16_t pad;
+};
+static_assert(sizeof(AoFilter) == 32, "rc_ao_filter's layout, one kernel argument");
+struct Ambient {
+  float c[3];
+};
+hipError_t launch_camera_gbuffer(const LaunchScene& s, const float eye[3], const View& v,
+                                 const Window& w, int W, int H, int32_t* id, float* t, float* P,
+                                 float* N, unsigned long long* zcount, hipStream_t stream);
+hipError_t launch_ao_filter(const void* ao, const int32_t* id, const float* P, const float* N,
+                            int W, int H, const AoFilter& f, uint8_t* out, hipStream_t stream);
+hipError_t launch_ao_compose(const float* diffuse, int n_shapes, const Ambient& ambient,
+                             const int32_t* id, const uint8_t* ao, const uint8_t* in, uint8_t* out,
+                             int W, int H, hipStream_t stream);
 
 // ------------------- defined in rc_kernels.hip: the renderer, the parity pipeline, row shards --
 // cuda_sem: RC_MODE_CUDA (the CUDA port's arithmetic, rc_cudasem.hpp) instead of fast mode

@@ -263,6 +263,13 @@ struct AoFrame {
   DevBuf origins, dirs, skip, tmax, flags;
 };
 
+// rc_render_ambient's device copies (the host form of the guided family): the occlusion state, the
+// guide's id, P and N planes and the filtered plane; the image is c.out.  The camera G-buffer and
+// the compose keep nothing on the device, the filter not even a workspace frame.
+struct GuidedFrame {
+  DevBuf state, id, P, N, plane;
+};
+
 struct DevCtx {
   bool init = false;
   int device = 0;
@@ -296,6 +303,7 @@ struct DevCtx {
   GbufFrame gbuf;      // the G-buffer's host entries
   ViewFrame view;      // rc_trace_rays' arrays
   AoFrame ao;          // ambient occlusion's last pass and the host forms' arrays
+  GuidedFrame guided;  // rc_render_ambient's planes
   // The event set whose spans each sampling feature's rc_*_phase_ms may still read, null once
   // another frame has recorded that set anew (claim_event_set).  Which events of the set a
   // feature reads is documented at its record above; window (rc_render_window*): [0] start,

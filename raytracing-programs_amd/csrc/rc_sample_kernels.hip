@@ -46,6 +46,8 @@
 //                 any-hit visibility (fast mode): a camera frame's primary hit and the blocked /
 //                 open count of up to 64 directions around it, added to the caller's per-pixel
 //                 records; a batch of the caller's own rays, one byte each; the records' bytes.
+//   k_camera_gbuffer
+//                 the G-buffer through a free camera (fast mode): k_ao's primary hit, stored.
 #include <cstring>
 
 #include "rc_cudasem.hpp"
@@ -2202,6 +2204,63 @@ hipError_t launch_ao_resolve(const void* ao, int W, int H, uint8_t* out, hipStre
   const int wide = (((uintptr_t)ao + 4 * head) & 15u) == 0u;
   hipLaunchKernelGGL(k_ao_resolve, dim3((unsigned)blocks), dim3(256), 0, stream,
                      (const uint32_t*)ao, pixels, (unsigned)head, groups, wide, out);
+  return hipGetLastError();
+}
+
+// ------------------------------------------- the G-buffer through a camera (fast) --
+// rc_render_camera_gbuffer* (include/raycast_hip.h): step 1 of k_ao, stored.  k_ao's grid, scene
+// staging and primary ray (view_dir at ssaa = 1, the general nearest from the eye at every eye,
+// hit_frame), k_gbuffer's stores; no shade and no occluded.  frame (P or N is wanted) is a kernel
+// argument's test and uniform: without it a pixel costs the scan alone and counts the direction's
+// normalisation only, as k_gbuffer does.  A miss is id -1 and +0 everywhere else.
+template <bool kStage>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_camera_gbuffer(
+    Scene sc, Cam cam, View v, Eye e, int W, int H, int ox, int oy, GbufPlanes g,
+    unsigned long long* __restrict__ zcount) {
+  if (!RC_X0_PIXEL) sc.has_quadric = sc.has_quadric != 0;   // as k_render (RC_X0_*)
+  const V3 eye = v3(e.x, e.y, e.z);
+  __shared__ StageBuf<kStage> stage;
+  stage_scene<kStage>(sc, stage);
+  int lx, ly;
+  tile_pixel(lx, ly);
+  int bx, by;
+  xcd_tile<0>(bx, by);
+  const int x = bx * kTileW + lx, y = by * kTileH + ly;
+  if (x >= W || y >= H) return;
+  int zero = 0;
+  const V3 d = view_dir<false>(cam, v, ox + x, oy + y, zero);
+  float t;
+  const int id = nearest(sc, eye, d, -1, t);
+  V3 P = v3(0.0f, 0.0f, 0.0f), N = P;
+  if (id < 0) t = 0.0f;
+  else if (g.P || g.N) hit_frame(sc, id, eye, d, t, P, N, zero);   // uniform test
+  const size_t i = (size_t)y * (size_t)W + (size_t)x;
+  if (g.id) g.id[i] = id;
+  if (g.t) g.t[i] = t;
+  if (g.P) {
+    float* q = g.P + 3 * i;
+    q[0] = P.x, q[1] = P.y, q[2] = P.z;
+  }
+  if (g.N) {
+    float* q = g.N + 3 * i;
+    q[0] = N.x, q[1] = N.y, q[2] = N.z;
+  }
+  flush_events(zero, zcount);
+}
+
+hipError_t launch_camera_gbuffer(const LaunchScene& s, const float eye[3], const View& v,
+                                 const Window& w, int W, int H, int32_t* id, float* t, float* P,
+                                 float* N, unsigned long long* zcount, hipStream_t stream) {
+  if (!window_supported(w, W, H, 1) || (!id && !t && !P && !N)) return hipErrorInvalidValue;
+  dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
+  const Scene sc = make_scene(s);
+  const Cam cam = make_cam(s, w.full_w, w.full_h);
+  const Eye e{eye[0], eye[1], eye[2]};
+  const GbufPlanes g{id, t, P, N};
+  dispatch(stage_fits(s), [&](auto st) {
+    hipLaunchKernelGGL((k_camera_gbuffer<st.value>), grid, dim3(kBlock), 0, stream, sc, cam, v, e,
+                       W, H, w.x0, w.y0, g, zcount);
+  });
   return hipGetLastError();
 }
 

@@ -1,10 +1,10 @@
 // rc_sampling.hip — the sampling features of libraycast_hip.so's C-ABI (include/raycast_hip.h):
 // rate maps, reconstruction filters, sparse sample patterns, progressive accumulation, windows of a
 // virtual image, the primary-visibility G-buffer, rotated views and ray batches, the free camera
-// and rays with origins, accumulation through free cameras and any-hit visibility queries with the
-// ambient-occlusion pass, with adaptive
+// and rays with origins, accumulation through free cameras, any-hit visibility queries with the
+// ambient-occlusion pass and the camera's G-buffer, guided filter and ambient compose, with adaptive
 // supersampling's getters.  Host code only: the kernels are
-// rc_sample_kernels.hip's and rc_filter.hip's (the one-ray image is rc_kernels.hip's k_render), the device context and the frame scaffold (enter,
+// rc_sample_kernels.hip's, rc_filter.hip's and rc_guided.hip's (the one-ray image is rc_kernels.hip's k_render), the device context and the frame scaffold (enter,
 // ws_frame, claim_event_set, finish_device, finish_host) are rc_api.hip's, through rc_runtime.h.
 //
 // A feature is one Refusal description, one enqueue body between SampleFrame::begin and ::end,
@@ -335,13 +335,17 @@ static const Refusal kAoRefusal = {
     nullptr};   // rc_window_check tests the sizes
 
 template <class Image>
-static int ao_refused(const char* who, const rc_options* opt, Image image) {
-  const Refusal& d = kAoRefusal;
+static int one_ray_refused(const Refusal& d, const char* who, const rc_options* opt, Image image) {
   if (opt->mode != RC_MODE_FAST && opt->mode != RC_MODE_CUDA) return say(d.mode, who);
   if (opt->num_gpus > 1) return say(d.shards, who, opt->num_gpus);
   if (camera_mode_refused(who, opt) || image()) return -1;
-  if (opt->ssaa != 0 && opt->ssaa != 1) return say(d.factor, who, opt->ssaa);
+  if (d.factor && opt->ssaa != 0 && opt->ssaa != 1) return say(d.factor, who, opt->ssaa);
   return 0;
+}
+
+template <class Image>
+static int ao_refused(const char* who, const rc_options* opt, Image image) {
+  return one_ray_refused(kAoRefusal, who, opt, image);
 }
 
 // What rc_ao_dirs_check refuses of a non-null set, as words for the caller's message; null: the
@@ -368,6 +372,65 @@ static const char* ao_dirs_problem(const rc_ao_dirs* d, char* buf, size_t room) 
     }
   }
   return nullptr;
+}
+
+// The guided family.  The G-buffer through a camera: the occlusion pass's
+// clauses without its state and directions, in one_ray_refused's order.  The compose: the mode
+// clauses alone (it shoots nothing, so the options' ssaa is not looked at).
+static const Refusal kCameraGbufferRefusal = {
+    nullptr,
+    1, "Error: %s: ssaa %d in the options: a G-buffer holds one primary hit a pixel, leave ssaa at "
+    "0 or 1\n",
+    "Error: %s: a G-buffer through a camera is for fast mode: the reference has one camera, and "
+    "rc_render_gbuffer gives its planes in parity mode\n",
+    "Error: %s: num_gpus %d: the row shards render no G-buffer\n",
+    nullptr};   // rc_window_check tests the sizes
+
+static const Refusal kComposeRefusal = {
+    nullptr,
+    1, nullptr,
+    "Error: %s: the ambient term is for fast mode: the reference's shading has none, so no parity "
+    "image carries one\n",
+    "Error: %s: num_gpus %d: the row shards compose nothing\n",
+    nullptr};
+
+// What rc_ao_filter_check refuses of a non-null filter, as words for the caller's message; null:
+// the filter passes.
+static const char* ao_filter_problem(const rc_ao_filter* f, char* buf, size_t room) {
+  if (f->radius < 0 || f->radius > RC_AO_FILTER_MAX_RADIUS) {
+    std::snprintf(buf, room, "radius %d is not 0..%d", f->radius, RC_AO_FILTER_MAX_RADIUS);
+    return buf;
+  }
+  if (f->pad != 0) {
+    std::snprintf(buf, room, "pad %u is not 0", (unsigned)f->pad);
+    return buf;
+  }
+  if (f->taps[0] == 0) return "taps[0] is 0: the centre is always pooled";
+  unsigned long long sum = f->taps[0];
+  for (int d = 1; d <= f->radius; ++d) sum += 2ull * f->taps[d];
+  if (sum * sum > 32768ull) {
+    std::snprintf(buf, room, "the taps sum to %llu along a side and %llu over the window, more "
+                  "than 32768: the sums are 32-bit", sum, sum * sum);
+    return buf;
+  }
+  if (f->nmin != f->nmin) return "nmin is NaN";
+  if (!(f->dplane >= 0.0f)) {   // NaN included
+    std::snprintf(buf, room, "dplane %g is NaN or negative", (double)f->dplane);
+    return buf;
+  }
+  return nullptr;
+}
+
+// both sides at least 1 and the image within one grid of 16 x 16 tiles (and, one lane a pixel,
+// within 2^31 - 1 workgroups of 256)
+static int guided_image_refused(const char* who, int W, int H) {
+  if (W >= 1 && H >= 1 && W <= rc::kGuidedMaxSide && H <= rc::kGuidedMaxSide &&
+      ((unsigned long long)W * (unsigned long long)H + 255) / 256 <= 0x7fffffffull)
+    return 0;
+  if (W < 1 || H < 1)
+    return say("Error: %s: %d x %d: both sides must be at least 1\n", who, W, H);
+  return say("Error: %s: %d x %d is past one grid: sides up to %d (16 x 16 tiles) and 2^39 pixels "
+             "at most\n", who, W, H, rc::kGuidedMaxSide);
 }
 
 // ------------------------------------------- sample lattices: patterns and sequences --
@@ -1252,6 +1315,101 @@ static int enqueue_ao(DevCtx& c, const rc_scene* s, const rc_camera* cam, const 
   });
 }
 
+// One G-buffer frame through a camera on `stream` through the device's one-frame workspace (the
+// caller holds c.mu and has passed camera_gbuffer_refused): one launch of k_camera_gbuffer.  The
+// G-buffer family's span owner: a camera's planes are a G-buffer frame to rc_gbuffer_phase_ms.
+static int enqueue_camera_gbuffer(DevCtx& c, const rc_scene* s, const rc_camera* cam,
+                                  const rc_window* vw, int W, int H, const rc_gbuffer* planes,
+                                  hipStream_t stream) {
+  return ws_frame(c, stream, [] { return 0; }, [&]() -> int {
+    SampleFrame f{c, stream, kSpanGbuffer};
+    if (f.begin(s, nullptr, 0)) return -1;
+    rc::View v;
+    std::memcpy(v.m, cam->view.m, sizeof v.m);
+    HIP_TRY(rc::launch_camera_gbuffer(f.ls, cam->eye, v,
+                                      rc::Window{vw->full_w, vw->full_h, vw->x0, vw->y0}, W, H,
+                                      planes->id, planes->t, planes->P, planes->N, f.zc, stream));
+    return f.end();
+  });
+}
+
+// the uploaded scene's diffuse colours (rc_scene.h: 3 floats a shape behind the pairs)
+static const float* scene_diffuse(const DevCtx& c, const rc_scene* s) {
+  return (const float*)((const char*)c.fb.scene.p + s->img->off_diffuse);
+}
+
+static rc::AoFilter ao_filter_arg(const rc_ao_filter* f) {
+  rc::AoFilter a;
+  static_assert(sizeof a == sizeof *f, "rc_ao_filter is the kernel's argument");
+  std::memcpy(&a, f, sizeof a);
+  return a;
+}
+
+// The compose on `stream` through the workspace (its scene alone: no counter, no event).
+static int enqueue_compose(DevCtx& c, const rc_scene* s, const int32_t* d_id, const uint8_t* d_ao,
+                           const float ambient[3], const uint8_t* d_in, uint8_t* d_out, int W,
+                           int H, hipStream_t stream) {
+  return ws_frame(c, stream, [] { return 0; }, [&]() -> int {
+    rc::LaunchScene ls;
+    if (upload_scene(c.fb, stream, s, ls)) return -1;
+    const rc::Ambient amb{{ambient[0], ambient[1], ambient[2]}};
+    HIP_TRY(rc::launch_ao_compose(scene_diffuse(c, s), ls.n, amb, d_id, d_ao, d_in, d_out, W, H,
+                                  stream));
+    return 0;
+  });
+}
+
+// rc_render_ambient's frame on c.stream (the caller holds c.mu and has passed every entry's
+// refusal): k_camera at one ray a pixel into c.out, the occlusion passes into the library's
+// state (enqueue_ao's: a reset pass, the counter block zeroed in front of every pass), the
+// camera's id, P and N, the filter into the library's plane and the compose in place, as one
+// workspace frame with one span and one zero-normalize count over all its kernels.
+static int enqueue_ambient(DevCtx& c, const rc_scene* s, const rc_camera* cam, const rc_window* vw,
+                           int W, int H, const rc_options* opt, const rc_ao_dirs* sets, int nsets,
+                           const rc_ao_filter* filter, const float ambient[3]) {
+  AoFrame& a = c.ao;
+  GuidedFrame& g = c.guided;
+  hipStream_t stream = c.stream;
+  auto prepare = [&]() -> int {
+    if (a.count.ensure(rc::kAoStatBytes)) {
+      std::fprintf(stderr, "Error: out of device memory for the occlusion counters\n");
+      return -1;
+    }
+    return ensure_done(a.done);
+  };
+  return ws_frame(c, stream, prepare, [&]() -> int {
+    SampleFrame f{c, stream, kSpanAo};
+    a.valid = false;
+    if (f.begin(s, &a.count, rc::kAoStatBytes)) return -1;
+    rc::View v;
+    std::memcpy(v.m, cam->view.m, sizeof v.m);
+    const rc::Window win{vw->full_w, vw->full_h, vw->x0, vw->y0};
+    uint8_t* img = (uint8_t*)c.out.p;
+    HIP_TRY(rc::launch_camera(f.ls, cam->eye, v, win, W, H, 1, opt->max_recursion, img, f.zc,
+                              stream));
+    for (int k = 0; k < nsets; ++k) {
+      if (k > 0) HIP_TRY(hipMemsetAsync(a.count.p, 0, rc::kAoStatBytes, stream));
+      rc::AoDirs d;
+      std::memcpy(&d, &sets[k], sizeof d);
+      HIP_TRY(rc::launch_ao(f.ls, cam->eye, v, win, W, H, d, k == 0, g.state.p, nullptr, f.zc,
+                            (unsigned long long*)a.count.p, stream));
+    }
+    HIP_TRY(rc::launch_camera_gbuffer(f.ls, cam->eye, v, win, W, H, (int32_t*)g.id.p, nullptr,
+                                      (float*)g.P.p, (float*)g.N.p, f.zc, stream));
+    HIP_TRY(rc::launch_ao_filter(g.state.p, (const int32_t*)g.id.p, (const float*)g.P.p,
+                                 (const float*)g.N.p, W, H, ao_filter_arg(filter),
+                                 (uint8_t*)g.plane.p, stream));
+    const rc::Ambient amb{{ambient[0], ambient[1], ambient[2]}};
+    HIP_TRY(rc::launch_ao_compose(scene_diffuse(c, s), f.ls.n, amb, (const int32_t*)g.id.p,
+                                  (const uint8_t*)g.plane.p, img, img, W, H, stream));
+    if (f.end()) return -1;
+    HIP_TRY(hipEventRecord(a.done, stream));
+    a.valid = true;
+    a.n = sets[nsets - 1].n;
+    return 0;
+  });
+}
+
 // -------------------------------------------------------------- the two entry shapes --
 // A *_device entry behind its null checks and its refusal: on the current device, on the
 // caller's stream or the context's, enqueue(c, st), then finish_device.  plain: the frame goes
@@ -2045,6 +2203,173 @@ int rc_render_ao(const rc_scene* s, const rc_camera* cam, const rc_window* win, 
         // behind the last pass on c.stream, in front of finish_host's wait
         HIP_TRY(hipMemcpyAsync(pixmap, c.ao.plane.p, px, hipMemcpyDeviceToHost, c.stream));
         return 0;
+      });
+}
+
+// ---------------- the G-buffer through a camera, the guided filter, the ambient compose --
+// rc_render_camera_gbuffer* behind their null checks: clauses 2 to 5 of the documented order, and
+// the window the frame is shot through (win null: the whole image)
+static int camera_gbuffer_refused(const char* who, const rc_options* opt, const rc_camera* cam,
+                                  const rc_window* win, int W, int H, const rc_gbuffer* planes,
+                                  rc_window* vw) {
+  if (!planes->id && !planes->t && !planes->P && !planes->N)
+    return say("Error: %s: all four planes are null: ask for at least one of id, t, P and N\n",
+               who);
+  *vw = win ? *win : rc_window{W, H, 0, 0};
+  if (one_ray_refused(kCameraGbufferRefusal, who, opt,
+                      [&] { return rc_window_check(vw, W, H, 1); }))
+    return -1;
+  return rc_camera_check(cam);
+}
+
+int rc_render_camera_gbuffer_device(const rc_scene* s, const rc_camera* cam, const rc_window* win,
+                                    int W, int H, const rc_options* opt,
+                                    const rc_gbuffer* d_planes, void* stream, rc_timing* timing) {
+  const char* who = "rc_render_camera_gbuffer_device";
+  if (!s || !cam || !opt || !d_planes) return say("Error: %s: a null pointer\n", who);
+  rc_window vw;
+  if (camera_gbuffer_refused(who, opt, cam, win, W, H, d_planes, &vw)) return -1;
+  return device_entry(opt, stream, timing, false, [&](DevCtx& c, hipStream_t st) {
+    return enqueue_camera_gbuffer(c, s, cam, &vw, W, H, d_planes, st);
+  });
+}
+
+int rc_render_camera_gbuffer(const rc_scene* s, const rc_camera* cam, const rc_window* win, int W,
+                             int H, const rc_options* opt, const rc_gbuffer* planes,
+                             rc_timing* timing) {
+  const char* who = "rc_render_camera_gbuffer";
+  if (!s || !cam || !opt || !planes) return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  rc_window vw;
+  if (camera_gbuffer_refused(who, opt, cam, win, W, H, planes, &vw)) return -1;
+  const size_t px = (size_t)W * H * sizeof(float);
+  return host_entry(
+      opt, W, H, nullptr, timing, t0,
+      "Error: out of device memory for the G-buffer's planes (%d x %d)\n", false,
+      [&](DevCtx& c) {   // device copies of the planes asked for (rc_render_gbuffer's)
+        GbufFrame& g = c.gbuf;
+        return (planes->id && g.id.ensure(px)) || (planes->t && g.t.ensure(px)) ||
+               (planes->P && g.P.ensure(3 * px)) || (planes->N && g.N.ensure(3 * px));
+      },
+      [&](DevCtx& c) -> int {
+        const GbufFrame& g = c.gbuf;
+        const rc_gbuffer d{planes->id ? (int32_t*)g.id.p : nullptr,
+                           planes->t ? (float*)g.t.p : nullptr,
+                           planes->P ? (float*)g.P.p : nullptr,
+                           planes->N ? (float*)g.N.p : nullptr};
+        if (enqueue_camera_gbuffer(c, s, cam, &vw, W, H, &d, c.stream)) return -1;
+        // behind the kernel on c.stream, in front of finish_host's wait
+        auto back = [&](void* host, const void* dev, size_t bytes) -> int {
+          if (host) HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c.stream));
+          return 0;
+        };
+        return back(planes->id, d.id, px) || back(planes->t, d.t, px) ||
+               back(planes->P, d.P, 3 * px) || back(planes->N, d.N, 3 * px);
+      });
+}
+
+static int ao_filter_make(const char* who, int radius, rc_ao_filter* out, bool tent) {
+  if (!out) return say("Error: %s: a null filter\n", who);
+  if (radius < 0 || radius > RC_AO_FILTER_MAX_RADIUS)
+    return say("Error: %s: radius %d is not 0..%d\n", who, radius, RC_AO_FILTER_MAX_RADIUS);
+  std::memset(out, 0, sizeof *out);
+  out->radius = radius;
+  out->nmin = 0.9f;
+  out->dplane = 0.05f;
+  for (int d = 0; d <= radius; ++d) out->taps[d] = (uint16_t)(tent ? radius + 1 - d : 1);
+  return 0;
+}
+
+int rc_ao_filter_box(int radius, rc_ao_filter* out) {
+  return ao_filter_make("rc_ao_filter_box", radius, out, false);
+}
+
+int rc_ao_filter_tent(int radius, rc_ao_filter* out) {
+  return ao_filter_make("rc_ao_filter_tent", radius, out, true);
+}
+
+int rc_ao_filter_check(const rc_ao_filter* f) {
+  const char* who = "rc_ao_filter_check";
+  if (!f) return say("Error: %s: a null filter\n", who);
+  char buf[160];
+  const char* why = ao_filter_problem(f, buf, sizeof buf);
+  return why ? say("Error: %s: %s\n", who, why) : 0;
+}
+
+// No scene and no frame of the workspace, like rc_ao_resolve_device.
+int rc_ao_filter_device(const rc_ao_px* d_ao, const rc_gbuffer* d_guide, int W, int H,
+                        const rc_ao_filter* f, uint8_t* d_out, void* stream) {
+  const char* who = "rc_ao_filter_device";
+  if (!d_ao || !d_guide || !f || !d_out) return say("Error: %s: a null pointer\n", who);
+  if (!d_guide->id || !d_guide->P || !d_guide->N)
+    return say("Error: %s: the guide needs its id, P and N planes (t is not read)\n", who);
+  if ((uintptr_t)d_ao & 3u) return say("Error: %s: the state is not 4-byte aligned\n", who);
+  if (guided_image_refused(who, W, H) || rc_ao_filter_check(f)) return -1;
+  Entered e;
+  if (enter(kCurrentDevice, false, e)) return -1;
+  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
+  HIP_TRY(rc::launch_ao_filter(d_ao, d_guide->id, d_guide->P, d_guide->N, W, H, ao_filter_arg(f),
+                               d_out, st));
+  return 0;
+}
+
+// clause 3 of the compose: every component finite and not negative (-0 passes)
+static int ambient_refused(const char* who, const float ambient[3]) {
+  for (int k = 0; k < 3; ++k)
+    if (!__builtin_isfinite(ambient[k]) || ambient[k] < 0.0f)
+      return say("Error: %s: ambient[%d] is %g: every component must be finite and not negative\n",
+                 who, k, (double)ambient[k]);
+  return 0;
+}
+
+int rc_ao_compose_device(const rc_scene* s, const rc_options* opt, const int32_t* d_id,
+                         const uint8_t* d_ao, const float ambient[3], const uint8_t* d_rgb_in,
+                         uint8_t* d_rgb_out, int W, int H, void* stream) {
+  const char* who = "rc_ao_compose_device";
+  if (!s || !opt || !d_id || !d_ao || !ambient || !d_rgb_in || !d_rgb_out)
+    return say("Error: %s: a null pointer\n", who);
+  if (one_ray_refused(kComposeRefusal, who, opt, [] { return 0; }) ||
+      ambient_refused(who, ambient) || guided_image_refused(who, W, H))
+    return -1;
+  Entered e;
+  if (enter(kCurrentDevice, true, e)) return -1;
+  hipStream_t st = stream ? (hipStream_t)stream : e.c->stream;
+  return enqueue_compose(*e.c, s, d_id, d_ao, ambient, d_rgb_in, d_rgb_out, W, H, st);
+}
+
+int rc_render_ambient(const rc_scene* s, const rc_camera* cam, const rc_window* win, int W, int H,
+                      const rc_options* opt, const rc_ao_dirs* sets, int nsets,
+                      const rc_ao_filter* filter, const float ambient[3], uint8_t* pixmap,
+                      rc_timing* timing) {
+  const char* who = "rc_render_ambient";
+  if (!s || !cam || !opt || !sets || !filter || !ambient || !pixmap)
+    return say("Error: %s: a null pointer\n", who);
+  const auto t0 = HostClock::now();
+  rc_window vw;
+  if (ao_pass_refused(who, opt, cam, win, W, H, &vw)) return -1;
+  if (nsets < 1 || nsets > 1024)
+    return say("Error: %s: nsets %d is not 1..1024: a reset pass and up to 1023 further ones (a "
+               "record holds 65535 rays)\n", who, nsets);
+  for (int k = 0; k < nsets; ++k) {
+    char buf[96];
+    if (const char* why = ao_dirs_problem(&sets[k], buf, sizeof buf))
+      return say("Error: %s: sets[%d] fails rc_ao_dirs_check: %s\n", who, k, why);
+  }
+  if (guided_image_refused(who, W, H) || rc_ao_filter_check(filter) ||
+      ambient_refused(who, ambient))
+    return -1;
+  const size_t px = (size_t)W * H;
+  return host_entry(
+      opt, W, H, pixmap, timing, t0,
+      "Error: out of device memory for the image, the occlusion state and the guide (%d x %d)\n",
+      false,
+      [&](DevCtx& c) {
+        GuidedFrame& g = c.guided;
+        return g.state.ensure(px * sizeof(rc_ao_px)) || g.id.ensure(px * 4) ||
+               g.P.ensure(px * 12) || g.N.ensure(px * 12) || g.plane.ensure(px);
+      },
+      [&](DevCtx& c) {
+        return enqueue_ambient(c, s, cam, &vw, W, H, opt, sets, nsets, filter, ambient);
       });
 }
 

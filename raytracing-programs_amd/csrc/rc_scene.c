@@ -172,7 +172,8 @@ rc_packed_header *rc_pack_scene(const json_data_t *js) {
   size_t off_shapes = sizeof(rc_packed_header);
   size_t off_lights = off_shapes + sizeof(rc_shape) * ((size_t)n + 1);
   size_t off_pairs = off_lights + sizeof(rc_light) * (size_t)m;
-  size_t bytes = off_pairs + sizeof(rc_shade_pair) * ((size_t)n + 1) * (size_t)m;
+  size_t off_diffuse = off_pairs + sizeof(rc_shade_pair) * ((size_t)n + 1) * (size_t)m;
+  size_t bytes = off_diffuse + 3 * sizeof(float) * (size_t)n;
   bytes = (bytes + 255) & ~(size_t)255;
   if (bytes > 0x7fffffff) { free(sh); free(li); return NULL; }
   unsigned char *buf = (unsigned char *)calloc(1, bytes);
@@ -185,6 +186,7 @@ rc_packed_header *rc_pack_scene(const json_data_t *js) {
   h->off_shapes = (int32_t)off_shapes;
   h->off_lights = (int32_t)off_lights;
   h->off_pairs = (int32_t)off_pairs;
+  h->off_diffuse = (int32_t)off_diffuse;
   h->bytes = (int32_t)bytes;
   h->phantom_defined = phantom_ok;
   rc_shape *ds = (rc_shape *)(buf + off_shapes);
@@ -200,6 +202,9 @@ rc_packed_header *rc_pack_scene(const json_data_t *js) {
   for (int k = 0; k < m; k++) fill_light(&dl[k], li[k]);
   for (int k = 0; k <= n; k++)
     for (int j = 0; j < m; j++) fill_pair(&dp[(size_t)k * m + j], k < n ? sh[k] : &phantom, li[j]);
+  float *dd = (float *)(buf + off_diffuse);
+  for (int k = 0; k < n; k++)
+    for (int c = 0; c < 3; c++) dd[3 * k + c] = sh[k]->diffuse_color[c];
   free(sh);
   free(li);
   return h;

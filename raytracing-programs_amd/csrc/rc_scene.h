@@ -82,7 +82,8 @@ typedef struct rc_shade_pair {
 /* Header of the packed image; followed in the same allocation by
  *   rc_shape shapes[n + 1]      (index n = phantom)
  *   rc_light lights[m]
- *   rc_shade_pair pairs[(n + 1) * m]                                       */
+ *   rc_shade_pair pairs[(n + 1) * m]
+ *   float diffuse[n][3]         (the shapes' own diffuse colours: rc_ao_compose_device)   */
 typedef struct rc_packed_header {
   int32_t n;            /* shapes                                       */
   int32_t m;            /* lights                                       */
@@ -93,7 +94,8 @@ typedef struct rc_packed_header {
   int32_t bytes;        /* total image size                             */
   int32_t phantom_defined;
   int32_t o0_ok;        /* every shape's o0 usable (finite coefficients) */
-  int32_t pad[6];
+  int32_t off_diffuse;  /* behind the pairs: 3 floats a shape, as the scene gives them */
+  int32_t pad[5];
 } rc_packed_header;
 
 #ifdef __cplusplus
