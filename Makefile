@@ -5,7 +5,8 @@
 #                   (tests/build/libprimcheck.so, the ray-level suite's device harness), pincheck
 #                   (tests/build/libpincheck.so, phase C's carry-point table wave by wave), resolvecheck
 #                   (tests/build/libresolvecheck.so and its four wrong variants, the carry resolver
-#                   entry by entry)
+#                   entry by entry), compactcheck (tests/build/libcompactcheck.so and its five wrong
+#                   variants, the DEP compaction and the row-shard kernels class map by class map)
 #   make ref        oracle/_ref: the reference C/ sources compiled in place (test oracle)
 #
 # Numerics flags (parity with the x86-64 gcc -O3 reference):
@@ -30,11 +31,11 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
 CFLAGS   := -O3 -ffp-contract=off -fPIC -Wall -Wno-unused-result -Iinclude -I$(SRC)
 
 HIP_SRCS  := $(SRC)/rc_kernels.hip $(SRC)/rc_sample_kernels.hip $(SRC)/rc_api.hip $(SRC)/rc_sampling.hip $(SRC)/rc_shard.hip $(SRC)/rc_filter.hip $(SRC)/rc_guided.hip
-HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_pixel.hpp $(SRC)/rc_resolve.hpp $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
+HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_pixel.hpp $(SRC)/rc_resolve.hpp $(SRC)/rc_compact.hpp $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
 FRONT_SRC := $(SRC)/front/parse.c $(SRC)/front/objects.c $(SRC)/front/ppm.c
 
-.PHONY: all oracle ref clean stamps stamps2 sanitize primcheck pincheck resolvecheck
-all: $(LIB)/libraycast_hip.so $(LIB)/libraycast_front.so $(BIN)/raytrace oracle primcheck pincheck resolvecheck
+.PHONY: all oracle ref clean stamps stamps2 sanitize primcheck pincheck resolvecheck compactcheck
+all: $(LIB)/libraycast_hip.so $(LIB)/libraycast_front.so $(BIN)/raytrace oracle primcheck pincheck resolvecheck compactcheck
 
 $(OBJ)/%.o: $(SRC)/%.hip $(HIP_HDRS)
 	@mkdir -p $(OBJ)
@@ -171,6 +172,20 @@ $(PRIM_OUT)/libresolvecheck.so: tests/tools/resolve_check.hip $(HIP_HDRS) $(OBJ)
 $(PRIM_OUT)/libresolvecheck_w%.so: tests/tools/resolve_check.hip $(HIP_HDRS) $(OBJ)/rc_scene.o | oracle
 	@mkdir -p $(PRIM_OUT)
 	$(HIPCC) $(HIPFLAGS) -DRV_WRONG=$* -shared $(OBJ)/rc_scene.o tests/tools/resolve_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
+
+# Test-only device harness of the DEP compaction and the row shards (tests/test_gpu_compact.py):
+# the product's rc_compact.hpp kernels over class maps and segment tables, launched as the
+# launchers launch them, built like primcheck (no scene: nothing but the HIP runtime is linked).
+# libcompactcheck_w1..w5.so are the same harness with one deliberate mistake each (CV_WRONG),
+# which the suite must catch.
+COMPACT_LIBS := $(PRIM_OUT)/libcompactcheck.so $(foreach k,1 2 3 4 5,$(PRIM_OUT)/libcompactcheck_w$(k).so)
+compactcheck: $(COMPACT_LIBS)
+$(PRIM_OUT)/libcompactcheck.so: tests/tools/compact_check.hip $(HIP_HDRS)
+	@mkdir -p $(PRIM_OUT)
+	$(HIPCC) $(HIPFLAGS) -shared tests/tools/compact_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
+$(PRIM_OUT)/libcompactcheck_w%.so: tests/tools/compact_check.hip $(HIP_HDRS)
+	@mkdir -p $(PRIM_OUT)
+	$(HIPCC) $(HIPFLAGS) -DCV_WRONG=$* -shared tests/tools/compact_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
 
 # occupancy variants of the pixel kernels (RC_HIP_LIB=libraycast_hip_<v>.so): w3 = phase A /
 # k_render compiled for 3 waves per SIMD (no VGPR spills), f3 = phase C (k_dep_chunks, k_finish)

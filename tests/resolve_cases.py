@@ -718,6 +718,9 @@ FRAMES = [("quadric", 256, 256), ("quadric", 333, 517), ("reflection", 256, 256)
           # helper takes them at 64 lanes an entry
           ("random33x", 96, 72), ("random64x", 96, 72)]
 FRAME_DEPTHS = (4, 6)
+# the first frames here to cross an LDS chunk of the compaction (4 096 pixels of a row: 770 DEP pixels
+# beyond it) and a scan chunk (2 048 rows: 160 segment starts beyond it); depth 6, default tuning only
+CHUNK_FRAMES = [("reflection", 8195, 3), ("reflection", 3, 4099)]
 # the schedules of tests/test_gpu.py's test_parity_schedules that change the resolver ...
 SCHEDULES = {"default": {}, "side-0": dict(side=0), "side-1": dict(side=1), "side-3": dict(side=3),
              "side-4": dict(side=4), "no-dep-fast": dict(dep_fast=0), "no-coop": dict(coop=0),

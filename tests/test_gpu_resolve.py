@@ -352,6 +352,9 @@ def test_frames(built, sched):
         for name, W, H in rv.FRAMES:
             for depth in rv.FRAME_DEPTHS:
                 n += check_frame(name, W, H, depth, sched)
+        if sched == "default":
+            for name, W, H in rv.CHUNK_FRAMES:
+                n += check_frame(name, W, H, 6, sched)
     print(f"[gpu_resolve] frames {sched}: {n} entries, 0 mismatches")
 
 
