@@ -6,7 +6,9 @@
 #                   (tests/build/libpincheck.so, phase C's carry-point table wave by wave), resolvecheck
 #                   (tests/build/libresolvecheck.so and its four wrong variants, the carry resolver
 #                   entry by entry), compactcheck (tests/build/libcompactcheck.so and its five wrong
-#                   variants, the DEP compaction and the row-shard kernels class map by class map)
+#                   variants, the DEP compaction and the row-shard kernels class map by class map), listcheck
+#                   (tests/build/liblistcheck.so and its eight wrong variants, the edge list and the
+#                   rate binning plane by plane)
 #   make ref        oracle/_ref: the reference C/ sources compiled in place (test oracle)
 #
 # Numerics flags (parity with the x86-64 gcc -O3 reference):
@@ -31,11 +33,11 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
 CFLAGS   := -O3 -ffp-contract=off -fPIC -Wall -Wno-unused-result -Iinclude -I$(SRC)
 
 HIP_SRCS  := $(SRC)/rc_kernels.hip $(SRC)/rc_sample_kernels.hip $(SRC)/rc_api.hip $(SRC)/rc_sampling.hip $(SRC)/rc_shard.hip $(SRC)/rc_filter.hip $(SRC)/rc_guided.hip
-HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_pixel.hpp $(SRC)/rc_resolve.hpp $(SRC)/rc_compact.hpp $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
+HIP_HDRS  := $(SRC)/rc_device.hpp $(SRC)/rc_cudasem.hpp $(SRC)/rc_pixel.hpp $(SRC)/rc_resolve.hpp $(SRC)/rc_compact.hpp $(SRC)/rc_lists.hpp $(SRC)/rc_rates_bin.inc $(SRC)/rc_kernels.h $(SRC)/rc_runtime.h $(SRC)/rc_scene.h include/raycast_hip.h
 FRONT_SRC := $(SRC)/front/parse.c $(SRC)/front/objects.c $(SRC)/front/ppm.c
 
-.PHONY: all oracle ref clean stamps stamps2 sanitize primcheck pincheck resolvecheck compactcheck
-all: $(LIB)/libraycast_hip.so $(LIB)/libraycast_front.so $(BIN)/raytrace oracle primcheck pincheck resolvecheck compactcheck
+.PHONY: all oracle ref clean stamps stamps2 sanitize primcheck pincheck resolvecheck compactcheck listcheck
+all: $(LIB)/libraycast_hip.so $(LIB)/libraycast_front.so $(BIN)/raytrace oracle primcheck pincheck resolvecheck compactcheck listcheck
 
 $(OBJ)/%.o: $(SRC)/%.hip $(HIP_HDRS)
 	@mkdir -p $(OBJ)
@@ -186,6 +188,20 @@ $(PRIM_OUT)/libcompactcheck.so: tests/tools/compact_check.hip $(HIP_HDRS)
 $(PRIM_OUT)/libcompactcheck_w%.so: tests/tools/compact_check.hip $(HIP_HDRS)
 	@mkdir -p $(PRIM_OUT)
 	$(HIPCC) $(HIPFLAGS) -DCV_WRONG=$* -shared tests/tools/compact_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
+
+# Test-only device harness of the sampling family's list builders (tests/test_gpu_lists.py): the
+# product's rc_lists.hpp and rc_rates_bin.inc (k_aa_mark and the binning block of k_rates_render) over
+# planes of bytes, launched as the launchers launch them, built like compactcheck.
+# liblistcheck_w1..w8.so are the same harness with one deliberate mistake each (LV_WRONG), which
+# the suite must catch.
+LIST_LIBS := $(PRIM_OUT)/liblistcheck.so $(foreach k,1 2 3 4 5 6 7 8,$(PRIM_OUT)/liblistcheck_w$(k).so)
+listcheck: $(LIST_LIBS)
+$(PRIM_OUT)/liblistcheck.so: tests/tools/list_check.hip $(HIP_HDRS)
+	@mkdir -p $(PRIM_OUT)
+	$(HIPCC) $(HIPFLAGS) -shared tests/tools/list_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
+$(PRIM_OUT)/liblistcheck_w%.so: tests/tools/list_check.hip $(HIP_HDRS)
+	@mkdir -p $(PRIM_OUT)
+	$(HIPCC) $(HIPFLAGS) -DLV_WRONG=$* -shared tests/tools/list_check.hip -o $@ -Wl,-rpath,$(ROCM)/lib
 
 # occupancy variants of the pixel kernels (RC_HIP_LIB=libraycast_hip_<v>.so): w3 = phase A /
 # k_render compiled for 3 waves per SIMD (no VGPR spills), f3 = phase C (k_dep_chunks, k_finish)

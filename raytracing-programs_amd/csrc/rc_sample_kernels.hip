@@ -51,6 +51,7 @@
 #include <cstring>
 
 #include "rc_cudasem.hpp"
+#include "rc_lists.hpp"
 #include "rc_pixel.hpp"
 
 namespace rc {
@@ -187,95 +188,8 @@ __global__ void __launch_bounds__(256) k_box_down(const uint8_t* __restrict__ sr
 // over A's pixel.  Mark reads neighbours that refine overwrites, so the two are separate
 // launches on one stream: the list is complete before the first refined store.
 //
-// k_aa_mark: one lane per pixel.  A workgroup is four waves side by side, each taking 64 adjacent
-// columns of kMarkRows rows of tile (tx, ty) (the tile index is divided once per workgroup, in
-// scalars).  A wave walks down its rows with a rolling window of three: of every row it loads
-// each lane's own pixel once (packed R | G << 8 | B << 16), takes the left and right neighbours
-// from the adjacent lanes, and only lanes 0 and 63 load the pixel beyond the wave, so a pixel
-// costs 3 * (kMarkRows + 2) / kMarkRows byte loads instead of 27.  Coordinates are clamped to
-// the image: a clamped neighbour is a pixel of the window taken twice, which changes neither max
-// nor min.  List slots are reserved per wave: a ballot of the flagged lanes of every row, one
-// atomicAdd of their popcounts' sum by lane 0, and each flagged lane writes at base + the flagged
-// pixels of the rows above + the popcount of the flagged lanes below it in its row.  Every lane
-// of a wave reaches the shuffles and the ballots (lanes past the image load and flag nothing;
-// skipping a row past the image is uniform).  The list's order follows
-// the atomics' arrival and is not deterministic; no output byte depends on it.
-constexpr int kMarkBlock = 256, kMarkRows = 8;
-struct MarkRow {
-  int lo[3], hi[3];   // per channel, over the pixel and its two neighbours in the row
-};
-__device__ __forceinline__ unsigned mark_load(const uint8_t* __restrict__ q) {
-  return (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
-}
-// in: x < W.  y < H.  Called by every lane of the wave.
-__device__ __forceinline__ MarkRow mark_row(const uint8_t* __restrict__ img, unsigned W, unsigned x,
-                                            unsigned y, int lane, bool in) {
-  const uint8_t* q = img + (size_t)y * W * 3;
-  const unsigned v = in ? mark_load(q + (size_t)x * 3) : 0u;
-  unsigned l = __shfl_up(v, 1, 64), r = __shfl_down(v, 1, 64);
-  if (in) {
-    if (x == 0u) l = v;
-    else if (lane == 0) l = mark_load(q + (size_t)(x - 1u) * 3);
-    if (x + 1u >= W) r = v;
-    else if (lane == 63) r = mark_load(q + (size_t)(x + 1u) * 3);
-  }
-  MarkRow m;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int a = (int)((v >> (8 * c)) & 255u), b = (int)((l >> (8 * c)) & 255u),
-              d = (int)((r >> (8 * c)) & 255u);
-    const int lo = a < b ? a : b, hi = a > b ? a : b;
-    m.lo[c] = lo < d ? lo : d;
-    m.hi[c] = hi > d ? hi : d;
-  }
-  return m;
-}
-__global__ void __launch_bounds__(kMarkBlock) k_aa_mark(const uint8_t* __restrict__ img, int W,
-                                                        int H, unsigned tiles_x, int thr,
-                                                        uint32_t* __restrict__ list,
-                                                        unsigned* __restrict__ count) {
-  const unsigned ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
-  const int lane = threadIdx.x & 63;
-  const unsigned x = tx * kMarkBlock + threadIdx.x;   // tx * 256 < W + 256 <= 2^31 + 255
-  const unsigned y0 = ty * kMarkRows, w = (unsigned)W, h = (unsigned)H;   // y0 < H
-  const bool in = x < w;
-  MarkRow p = mark_row(img, w, x, y0 > 0u ? y0 - 1u : 0u, lane, in);
-  MarkRow c = mark_row(img, w, x, y0, lane, in);
-  unsigned long long flagged[kMarkRows];   // per row, the ballot of its flagged lanes (uniform)
-  unsigned total = 0u;
-#pragma unroll
-  for (int k = 0; k < kMarkRows; ++k) {
-    const unsigned y = y0 + (unsigned)k;
-    flagged[k] = 0ull;
-    if (y >= h) continue;   // uniform
-    const MarkRow n = mark_row(img, w, x, y + 1u < h ? y + 1u : y, lane, in);
-    int con = 0;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      int lo = p.lo[ch] < c.lo[ch] ? p.lo[ch] : c.lo[ch];
-      int hi = p.hi[ch] > c.hi[ch] ? p.hi[ch] : c.hi[ch];
-      lo = n.lo[ch] < lo ? n.lo[ch] : lo;
-      hi = n.hi[ch] > hi ? n.hi[ch] : hi;
-      con = hi - lo > con ? hi - lo : con;
-    }
-    flagged[k] = __ballot(in && con >= thr);
-    total += (unsigned)__popcll(flagged[k]);
-    p = c;
-    c = n;
-  }
-  // one reservation per wave for all its rows: the atomics all hit one address
-  unsigned base = 0u;
-  if (lane == 0 && total) base = atomicAdd(count, total);
-  base = __shfl(base, 0, 64);
-#pragma unroll
-  for (int k = 0; k < kMarkRows; ++k) {
-    const unsigned long long m = flagged[k];
-    if ((m >> lane) & 1ull)   // y*W + x < W*H < 2^32 (launch_aa_mark)
-      list[base + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] =
-          (uint32_t)((size_t)(y0 + (unsigned)k) * w + x);
-    base += (unsigned)__popcll(m);
-  }
-}
+// k_aa_mark, with mark_load, MarkRow, mark_row, kMarkBlock and kMarkRows, is in rc_lists.hpp, where
+// its scheme is described: the plane-by-plane test harness compiles the same text.
 
 // k_aa_refine: over the list, not the image.  A wave serves 64 / (s*s) listed pixels per step
 // (s = 1 << ls: 16, 4 or 1): lane l belongs to group l / (s*s) and shoots subsample
@@ -355,7 +269,6 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
 // A workgroup without a rate-1 pixel ends before stage_scene; the decision is one
 // __syncthreads_or, so stage_scene's barrier stays uniform.  A rate-1 lane stores its own three
 // bytes: a wider store would write into a neighbour that may have rate 0.
-constexpr int kRateChunk = 8;   // tiles' worth of pixels per binning workgroup (a power of two)
 template <bool kCuda, bool kStage>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_PHASE_A_WAVES))) k_rates_render(
     Scene sc, Cam cam, int W, int H, int maxrec, const uint8_t* __restrict__ rates,
@@ -366,66 +279,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(RC_
   __shared__ StageBuf<kStage> stage;
   __shared__ unsigned wsum[kBlock / 64][5];   // per wave: the chunk's pixels per counter of cnt
   __shared__ unsigned wbase[3];               // the chunk's first slot in each list
-  {
-    const int lin = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
-    const int nwg = (int)gridDim.x * (int)gridDim.y;
-    const int chunk = lin / kRateChunk;
-    int duty = chunk % kRateChunk;   // which workgroup of the chunk's kRateChunk bins it
-    if (chunk * kRateChunk + duty >= nwg) duty = 0;
-    if (lin % kRateChunk == duty) {   // uniform over the workgroup: the barriers below are too
-      const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-      const unsigned long long below = (1ull << lane) - 1ull;
-      const size_t n = (size_t)W * H;   // < 2^32; the grid's workgroups * 256 >= n
-      const size_t first = (size_t)chunk * (kRateChunk * kBlock) + threadIdx.x;
-      unsigned tot[5] = {0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int it = 0; it < kRateChunk; ++it) {
-        const size_t i = first + (size_t)it * kBlock;
-        const unsigned rate = i < n ? (unsigned)rates[i] : 0u;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) tot[k] += (unsigned)__popcll(__ballot(rate == (2u << k)));
-        tot[3] += (unsigned)__popcll(__ballot(rate == 1u));
-        tot[4] += (unsigned)__popcll(__ballot(!(rate <= 2u || rate == 4u || rate == 8u)));
-      }
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) wsum[wave][k] = tot[k];
-      }
-      __syncthreads();
-      if (threadIdx.x < 5) {
-        unsigned sum = 0u;
-        for (int w = 0; w < kBlock / 64; ++w) sum += wsum[w][threadIdx.x];
-        unsigned base = 0u;
-        if (sum) base = atomicAdd(cnt + threadIdx.x, sum);
-        if (threadIdx.x < 3) wbase[threadIdx.x] = base;
-      }
-      __syncthreads();
-      unsigned base[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        base[k] = wbase[k];
-        for (int w = 0; w < wave; ++w) base[k] += wsum[w][k];
-      }
-      if (tot[0] | tot[1] | tot[2]) {   // uniform over the wave
-#pragma unroll
-        for (int it = 0; it < kRateChunk; ++it) {
-          const size_t i = first + (size_t)it * kBlock;
-          const unsigned rate = i < n ? (unsigned)rates[i] : 0u;
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            const unsigned long long m = __ballot(rate == (2u << k));
-            if ((m >> lane) & 1ull) {   // i < n: a pixel index below 2^32
-              const size_t at = (size_t)base[k] + (unsigned)__popcll(m & below);
-              if (k == 0) list2up[at] = (uint32_t)i;
-              else if (k == 1) list4[at] = (uint32_t)i;
-              else *(list8down - at) = (uint32_t)i;
-            }
-            base[k] += (unsigned)__popcll(m);
-          }
-        }
-      }
-    }
-  }
+#include "rc_rates_bin.inc"
   int lx, ly;
   tile_pixel(lx, ly);
   int bx, by;
